@@ -2,14 +2,17 @@
 """Headline benchmark: samples/sec, forward + moe_loss + backward (+ gradient all-reduce for N > 1),
 4-expert MixtureOfExperts ("PMoE" experts), 256x256 RGB x 4 frames, batch 64 per GPU, bf16.
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
 One process per GPU; weak scaling (64 samples per GPU); inputs are synthetic, resident in HBM before
 the timed region; rank 0 prints ONE JSON line.  A "step" = zero_grad + forward + moe_loss + backward
-(incl. the bucketed RCCL all-reduce).  The full reference step recipe (clip_grad_norm_ 1.0 + Adam
-amsgrad, train_2.py:157-165) is timed separately and reported as `h1_step`.
+(incl. the bucketed RCCL all-reduce).  A plain run sets up, warms up, times the steps and prints the headline line;
+--full adds everything else the line has carried: the per-kernel profile and roofline of one instrumented step, the
+full reference step recipe (clip_grad_norm_ 1.0 + Adam amsgrad, train_2.py:157-165) timed separately as `h1_step`,
+the all-reduce model, the stage-1 step, the sub-records of BASELINE configs C2-C5 and the CPU baseline.
+--dump-outputs DIR writes what the last timed step returned (dump_outputs) for output-for-output comparisons.
 """
 import argparse
 import json
@@ -43,18 +46,30 @@ def parse():
                     help="fp8 = BASELINE config 5: e4m3 weights + activations on the block-scaled fp8 matrix instruction for the "
                          "dense 3x3 stride-1 forward convolutions of ResNet layer2-4, bf16 elsewhere (quote it with --batch 128)")
     ap.add_argument("--dropout", type=float, default=0.3, help="stage_2*.yaml value")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure, also measure the rest (kernel profile + roofline, H1 steps, all-reduce "
+                         "model, stage-1 step, BASELINE sub-configs, CPU baseline); the --no-* switches below trim it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-stage1", action="store_true", help="skip the stage-1 PU-Net training step (section 8f N4)")
     ap.add_argument("--no-sub-configs", action="store_true",
                     help="skip the short sub-records of BASELINE configs C3 (per-GPU shard, E=8), C4 (punet) and C5 (fp8, B=128)")
     ap.add_argument("--no-kernel-profile", action="store_true")
     ap.add_argument("--only-steps", action="store_true",
-                    help="run warm-up + timed steps and print the basic line only (PMC traffic collection: tools/collect_traffic.py)")
+                    help="warm-up + timed steps and the basic line only, even with --full: what a plain run does "
+                         "(PMC traffic collection: tools/collect_traffic.py)")
     ap.add_argument("--measure-overlap", action="store_true",
-                    help="also time the step with weight gradients on a side stream (co-running kernels: keep it out of "
-                         "runs that are profiled per kernel)")
-    ap.add_argument("--detail", action="store_true", help="per-layer launch table on stderr")
-    return ap.parse_args()
+                    help="with --full: also time the step with weight gradients on a side stream (co-running kernels: keep "
+                         "it out of runs that are profiled per kernel)")
+    ap.add_argument("--detail", action="store_true", help="with --full: per-layer launch table on stderr")
+    args = ap.parse_args()
+    if args.only_steps:
+        args.full = False
+    for flag in ("measure_overlap", "detail"):
+        if getattr(args, flag) and not args.full:
+            ap.error(f"--{flag.replace('_', '-')} needs --full")
+    return args
 
 
 def make_batch(B, size, seed, device):
@@ -65,6 +80,31 @@ def make_batch(B, size, seed, device):
     command = torch.nn.functional.one_hot(torch.randint(0, 6, (B,), generator=g), 6).float()
     control = torch.rand(B, 2, generator=g) * 2 - 1
     return [t.to(device) for t in (images, speed, command, control, target)]
+
+
+DUMP_GRAD_SAMPLE = 1 << 22          # gradient entries written by dump_outputs (16 MiB in f32 of the 221 MB at E=4)
+
+
+def dump_outputs(path, model, loss, act_dist, speeds):
+    """What a caller of the timed step receives from its last step, as <path>/<name>.npy: the mixture parameters behind the
+    returned distribution (probs [B,E], mean / std [B,E,2]), the speed predictions [B,E,1], the loss and the parameter
+    gradients.  The full gradient does not fit the 64 MB budget: grad_norms holds every trainable parameter's gradient
+    norm (float64, named_parameters order) and grad_sample the entries of the flattened gradient (the same order) at
+    DUMP_GRAD_SAMPLE sorted positions drawn with seed 0.  A parameter without a gradient counts as zeros."""
+    import numpy as np
+    path.mkdir(parents=True, exist_ok=True)
+    probs, mean, std = act_dist.hip_params
+    params = [p for p in model.parameters() if p.requires_grad]
+    grads = [p.grad if p.grad is not None else torch.zeros_like(p) for p in params]
+    flat = torch.cat([g.reshape(-1).float() for g in grads])
+    if flat.numel() > DUMP_GRAD_SAMPLE:
+        idx = torch.randint(0, flat.numel(), (DUMP_GRAD_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+        flat = flat[idx.to(flat.device)]
+    arrays = {"probs": probs, "mean": mean, "std": std, "speeds": speeds, "loss": loss, "grad_sample": flat}
+    for name, t in arrays.items():
+        np.save(path / f"{name}.npy", t.detach().float().cpu().numpy())
+    norms = torch.stack([torch.linalg.vector_norm(g.double()) for g in grads])
+    np.save(path / "grad_norms.npy", norms.cpu().numpy())
 
 
 def _cpu_model_string():
@@ -316,7 +356,7 @@ def main():
         d, s = model(images, speed, command)
         loss = moe_loss(d, s, control, target, coefs)
         loss.backward()
-        return loss
+        return loss, d, s
 
     def fence():
         if use_dist:
@@ -339,7 +379,7 @@ def main():
     t0 = time.perf_counter()
     marks[0].record()
     for i in range(args.steps):
-        loss = step()
+        loss, act_dist, speeds_pred = step()
         marks[i + 1].record()
     fence()
     elapsed = time.perf_counter() - t0
@@ -390,7 +430,10 @@ def main():
         out["step_hbm_frac_model"] = round(HBM_BYTES_PER_SAMPLE_E4_256_BF16 * scale * value / world / 1e9 / PEAK_HBM_GBS, 4)
 
     log(f"timed: {ms:.2f} ms/step")
-    if args.only_steps:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(Path(args.dump_outputs), model, loss, act_dist, speeds_pred)
+        log(f"last step's outputs written to {args.dump_outputs}")
+    if not args.full:
         if rank == 0:
             print(json.dumps(out), flush=True)
         if use_dist:

@@ -113,7 +113,7 @@ def test_rccl_branch_runs_on_one_gpu():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), str(repo / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-           "--batch", "8", "--size", "128", "--no-cpu-baseline", "--no-stage1", "--no-sub-configs"]
+           "--batch", "8", "--size", "128", "--full", "--no-cpu-baseline", "--no-stage1", "--no-sub-configs"]
     r = subprocess.run(cmd, cwd=repo, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]

@@ -1,6 +1,6 @@
 #!/bin/bash
 cd "$(dirname "$0")/.."
-B="python bench.py --steps 15 --warmup 4 --no-cpu-baseline --no-stage1 --no-sub-configs --no-kernel-profile"
+B="python bench.py --steps 15 --warmup 4 --full --no-cpu-baseline --no-stage1 --no-sub-configs --no-kernel-profile"
 for r in 1 2; do
   for cfg in "PMOE_OVERLAP_WGRAD=0" "PMOE_OVERLAP_WGRAD=1"; do
     out=$(env $cfg $B 2>/dev/null | tail -1)

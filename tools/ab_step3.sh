@@ -2,7 +2,7 @@
 # Whole-step A/B of the round-3 switches on ONE box, back to back, twice (never compare bench lines across gpurun calls).
 #   bash tools/ab_step3.sh "PMOE_BN_REDUCE_IN_DGRAD=0" ...
 cd "$(dirname "$0")/.."
-B="python bench.py --steps 15 --warmup 4 --no-cpu-baseline --no-stage1 --no-sub-configs"
+B="python bench.py --steps 15 --warmup 4 --full --no-cpu-baseline --no-stage1 --no-sub-configs"
 for r in 1 2; do
   for cfg in "default" "$@"; do
     if [ "$cfg" = "default" ]; then out=$($B 2>/dev/null | tail -1); else out=$(env $cfg $B 2>/dev/null | tail -1); fi

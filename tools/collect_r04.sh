@@ -4,7 +4,7 @@
 set -o pipefail
 R="$(cd "$(dirname "$0")/.." && pwd)"; O="$R/gpurun_out/r04"; mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof" -o r04 -- python3 "$R/bench.py" --no-stage1 --no-cpu-baseline --no-sub-configs > "$O/r04_bench_line_under_rocprof.json" 2> "$O/rocprof_stderr.log"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof" -o r04 -- python3 "$R/bench.py" --full --no-stage1 --no-cpu-baseline --no-sub-configs > "$O/r04_bench_line_under_rocprof.json" 2> "$O/rocprof_stderr.log"
 echo "rocprof rc=$?"
 find "$O/prof" -name "*kernel_stats.csv" -exec cp {} "$O/r04_bench_kernel_stats.csv" \;
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$O/pmc_fetch" -o f -- python3 "$R/bench.py" --steps 4 --warmup 1 --only-steps > "$O/pmc_f.log" 2>&1
