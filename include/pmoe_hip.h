@@ -109,13 +109,15 @@ typedef struct pmoe_conv_desc {
                            * output pixel (oy, ox) is scattered to (2 oy + dy, 2 ox + dx): `out` is then the DESTINATION
                            * [n][2 ho][2 wo][out_ld] and receives channels [out_coff, out_coff + shuffle_c) (the "up" half of the
                            * skip-concatenation buffer); cout = 4*shuffle_c, ho / wo powers of two.  conv1x1_direct_kernel only
-                           * (pmoe_conv2d_plan returns 1452 | 1454, anything else PMOE_ERR_UNSUPPORTED); replaces the
+                           * (pmoe_conv2d_plan returns 1452 | 1454, anything else -- e4m3 operands, dilate,
+                           * a 3x3 filter, statistics -- PMOE_ERR_UNSUPPORTED); replaces the
                            * pmoe_pixel_shuffle2 launch and the [n][ho][wo][4c] intermediate. */
 } pmoe_conv_desc;
 
 int pmoe_conv2d_igemm(const pmoe_conv_desc* d, void* stream);
 /* number of [2][coutp] partial-sum rows the launch writes to d->stats (rows of expert e are
- * contiguous: [e*rows/E, (e+1)*rows/E) ); <0 = error */
+ * contiguous: [e*rows/E, (e+1)*rows/E) ): the kernel choice of pmoe_conv2d_igemm for this descriptor with d->stats set
+ * (a null d->stats asks for the rows all the same); <0 = error, or no kernel writes statistics for this descriptor */
 int pmoe_conv2d_stat_rows(const pmoe_conv_desc* d);
 /* which kernel instantiation pmoe_conv2d_igemm would run for this descriptor (nothing is launched; used by bench.py
  * to attribute measured launch times to kernel symbols that a rocprofv3 kernel trace shows):
@@ -136,7 +138,10 @@ int pmoe_conv2d_stat_rows(const pmoe_conv_desc* d);
  *   8000 + one of the above  the same tile with e4m3 operands (w_fp8)
  *   8507                     conv3x3_dma_f8_kernel                 (w_fp8 + in_fp8: LDS-DMA kernel on the block-scaled fp8 MFMA, conv_dma.hip)
  *   LOG_RB*100 + WM*10 + WN  conv_igemm_kernel<T, LOG_RB, WM, WN>  (halo-patch implicit GEMM, conv_igemm.hip)
- *   4000 + the latter        the four parity-class launches of a stride-2 3x3 data gradient */
+ *   4000 + the latter        the four parity-class launches of a stride-2 3x3 data gradient (the code of class (1, 1);
+ *                            9207: conv3x3s2_dma_kernel<true>)
+ * A stride-2 1x1 data gradient accumulated in place (dilate, PMOE_RES_ADD with res == out) is ONE class-(0,0) launch: the
+ * code of its tile, without the 4000.  One selection (conv_select) decides this code, the launch and pmoe_conv2d_stat_rows. */
 int pmoe_conv2d_plan(const pmoe_conv_desc* d);
 
 /* Weight gradient of the same layers (autograd of nn.Conv2d / nn.Linear at the call sites above).

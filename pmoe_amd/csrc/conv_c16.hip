@@ -184,7 +184,7 @@ __global__ void __launch_bounds__(256, 2) conv3x3_c16_kernel(ConvArgs a, int til
 }  // namespace
 
 // PMOE_CONV_C16=0: A/B switch back to conv3x3_res_kernel<5> (read per launch)
-bool conv_c16_plan(const ConvArgs& a, int dtype, int* wgs_per_expert, int* tiles_x, int* tiles_per_expert) {
+bool conv_c16_plan(const ConvArgs& a, int dtype, ConvLaunch* l) {
     const char* ev = getenv("PMOE_CONV_C16");
     if (ev && !atoi(ev)) return false;
     if (dtype != PMOE_DT_BF16 || a.w_fp8 || a.ks != 3 || a.stride != 1 || a.pad != 1 || a.dilate) return false;
@@ -201,15 +201,15 @@ bool conv_c16_plan(const ConvArgs& a, int dtype, int* wgs_per_expert, int* tiles
     if (wpe < 1) wpe = 1;
     if (wpe > tpe / 16) wpe = (int)(tpe / 16);                       // >= 4 tiles per wave: the stat fold is amortised
     if (wpe < 1) wpe = 1;
-    *wgs_per_expert = wpe; *tiles_x = tx; *tiles_per_expert = (int)tpe;
+    l->kind = CONV_C16; l->code = 1316; l->a = a;
+    l->wpe = wpe; l->tiles_x = tx; l->tpe = (int)tpe; l->mblocks = E * wpe;
     return true;
 }
 
-int conv_c16_launch(const ConvArgs& a, hipStream_t st) {
-    int wpe, tx, tpe;
-    if (!conv_c16_plan(a, PMOE_DT_BF16, &wpe, &tx, &tpe)) return PMOE_ERR_ARG;
+int conv_c16_launch(const ConvLaunch& l, hipStream_t st) {
+    const ConvArgs& a = l.a;
     const long long in_b = (long long)a.ipe * a.H * a.W * a.in_ld * 2 - (long long)a.in_coff * 2;
     const long long out_b = (long long)a.ipe * a.H * a.W * a.out_ld * 2 - (long long)a.out_coff * 2;
-    hipLaunchKernelGGL(conv3x3_c16_kernel, dim3(wpe, a.N / a.ipe), dim3(256), 0, st, a, tx, tpe, wpe, (unsigned)in_b, (unsigned)out_b);
+    hipLaunchKernelGGL(conv3x3_c16_kernel, dim3(l.wpe, a.N / a.ipe), dim3(256), 0, st, a, l.tiles_x, l.tpe, l.wpe, (unsigned)in_b, (unsigned)out_b);
     return (int)hipGetLastError();
 }

@@ -222,7 +222,7 @@ __global__ void __launch_bounds__(256, 2) conv1x1_direct_kernel(ConvArgs a, int 
 }  // namespace
 
 // PMOE_CONV_C1X1=0: A/B switch back to the LDS-tiled kernels (read per launch)
-bool conv_c1x1_plan(const ConvArgs& a, int dtype, int* wgs_per_expert, int* tiles_per_expert, int* n_slabs, int* mt, size_t* smem) {
+bool conv_c1x1_plan(const ConvArgs& a, int dtype, ConvLaunch* l) {
     const char* ev = getenv("PMOE_CONV_C1X1");
     if (ev && !atoi(ev)) return false;
     if (dtype != PMOE_DT_BF16 || a.w_fp8 || a.ks != 1 || a.pad != 0 || a.dilate || a.kh != 1 || a.kw != 1) return false;
@@ -250,14 +250,16 @@ bool conv_c1x1_plan(const ConvArgs& a, int dtype, int* wgs_per_expert, int* tile
     if (wpe < 1) wpe = 1;
     if (wpe > tpe / 16) wpe = (int)(tpe / 16);
     if (wpe < 1) wpe = 1;
-    *wgs_per_expert = wpe; *tiles_per_expert = (int)tpe; *n_slabs = slabs; *mt = m; *smem = sm;
+    // 1400 + MT = conv1x1_direct_kernel<MT>, + 10: <MT, true> (PMOE_RES_INBN), + 50: with shuf_c
+    l->kind = CONV_C1X1; l->code = 1400 + m + (inbn ? 10 : 0) + (a.shuf_c ? 50 : 0); l->a = a;
+    l->wpe = wpe; l->tpe = (int)tpe; l->slabs = slabs; l->mt = m; l->smem = sm; l->mblocks = E * wpe;
     return true;
 }
 
-int conv_c1x1_launch(const ConvArgs& a, hipStream_t st) {
-    int wpe, tpe, slabs, m;
-    size_t sm;
-    if (!conv_c1x1_plan(a, PMOE_DT_BF16, &wpe, &tpe, &slabs, &m, &sm)) return PMOE_ERR_ARG;
+int conv_c1x1_launch(const ConvLaunch& l, hipStream_t st) {
+    const ConvArgs& a = l.a;
+    const int wpe = l.wpe, tpe = l.tpe, slabs = l.slabs, m = l.mt;
+    const size_t sm = l.smem;
     const long long in_b = (long long)a.ipe * a.H * a.W * a.in_ld * 2 - (long long)a.in_coff * 2;
     const long long out_b = (long long)a.ipe * a.Ho * a.Wo * a.out_ld * 2 * (a.shuf_c ? 4 : 1) - (long long)a.out_coff * 2;
     const int kch = (a.Cin + 127) / 128;

@@ -83,7 +83,7 @@ __device__ __forceinline__ void vm_wait_prod(int n) {     // s_waitcnt vmcnt(n),
 template <bool MF16, bool PROD = false>
 __global__ void __launch_bounds__(PROD ? NTHR + 64 : NTHR, PROD ? 1 : 2) conv3x3_dma_kernel(const ConvArgs a_in, const int pbuf_bytes) {
     ConvArgs a = a_in;
-    if constexpr (PROD) {                                // forward launches only (conv_dma_uses_producer): the epilogue's side-input /
+    if constexpr (PROD) {                                // forward launches only (conv_dma_plan): the epilogue's side-input /
         a.res_mode = PMOE_RES_NONE; a.res = nullptr;     // bias / activation / dropout branches fold away at compile time (168 VGPRs)
         a.bias = nullptr; a.act = PMOE_ACT_NONE; a.drop_p = 0.f; a.bn = nullptr;
     }
@@ -447,7 +447,7 @@ __global__ void __launch_bounds__(NTHR + 4 * 64, 1) conv3x3_dma_stream_kernel(co
     constexpr int NT = NARROW ? 1 : 2, WPC = 4 * NT;     // WPC: pieces of a weight tile per producer wave
     static_assert(!(NARROW && MF16), "the 64-cout tile exists on the 32x32x16 shape only");
     constexpr int BN = 64 * NT, WSLOT = BN * RB;        // (shadow the 128-cout constants of this file)
-    STAMP_INIT                                           // (the -DPMOE_STAMP tools build never launches this kernel: conv_dma_uses_stream)
+    STAMP_INIT                                           // (the -DPMOE_STAMP tools build never launches this kernel: conv_dma_plan)
     ConvArgs a = a_in;
     a.res_mode = PMOE_RES_NONE; a.res = nullptr; a.bias = nullptr; a.act = PMOE_ACT_NONE; a.drop_p = 0.f; a.bn = nullptr;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1177,198 +1177,109 @@ __global__ void __launch_bounds__(NTHR, 2) conv3x3_dma_f8_kernel(const ConvArgs 
 
 }  // namespace
 
-// the persistent kernel's piece decode: the magic-number divisions reproduce / and %, the packed fields fit, and rows 0..159 (NT = 2)
-// or all 256 half-rows (NT = 1) of the epilogue's staging fit the patch buffer.  Expects the tile geometry of conv_dma_plan in `a`.
-static bool stream_geometry_ok(const ConvArgs& a, int pbuf) {
-    if (pbuf < 160 * 256) return false;
-    const int PW = (1 << a.lTW) + 2, PH = (1 << a.lTH) + 2;
-    const int npiece = (a.TN * PH * PW + 7) / 8;
-    const int mpw = 65536 / PW + 1, mph = 65536 / PH + 1;
-    for (int pp = 0; pp < npiece * 8; ++pp)
-        if (((pp * mpw) >> 16) != pp / PW || ((((pp / PW) * mph) >> 16) != (pp / PW) / PH)) return false;
-    return a.TN * PH < 1024 && PW < 1024 && a.ipe < 2047;      // the packed (image, row, column) fields of a piece
-}
-
-// 64 output-channel rows over >= 128 input channels, nothing but the convolution (+ statistics): conv3x3_dma_stream_kernel<false, true>.
-// PMOE_DMA_NARROW=0: back to the generic kernel (A/B runs)
-bool conv_dma_is_narrow(const ConvArgs& a) {
-#ifdef PMOE_STAMP
-    return false;                                        // (the stamped epilogue ends the workgroup after its first tile)
-#endif
-    const char* ev = getenv("PMOE_DMA_NARROW");
-    if (ev && !atoi(ev)) return false;
-    return a.CoutP == 64 && a.Cin >= 2 * CK && a.res_mode == PMOE_RES_NONE && !a.bias && a.act == PMOE_ACT_NONE && a.drop_p == 0.f;
+// Tile geometry of the LDS-DMA kernels: 256-pixel tiles of TW = 2^lTW (16 <= TW <= 2^ltw_max) x TH pixels x TN images, each
+// staged as a halo patch of (TH + halo) x (TW + halo) pixels in whole 1 KiB pieces (<= 6 per wave); `nbuf` patch buffers + a ring of
+// `ring` weight slots in LDS; 32-bit source offsets inside one expert's images of `esz`-byte elements.  Fills the tile fields of
+// l->a and the launch sizes.
+static bool dma_tile(const ConvArgs& a, int halo, int ltw_max, int nbuf, int ring, int esz, ConvLaunch* l) {
+    if ((long long)a.ipe * a.Ho * a.Wo < 4096) return false;
+    auto p2 = [](int v) { int l = 0; while ((1 << l) < v) ++l; return l; };
+    int lTW = p2(a.Wo); if (lTW > ltw_max) lTW = ltw_max;
+    if (lTW < 4) return false;
+    int lTH = p2(a.Ho); if (lTH > 8 - lTW) lTH = 8 - lTW;
+    const int TN = BM >> (lTW + lTH);
+    const int npiece = (TN * ((1 << lTH) + halo) * ((1 << lTW) + halo) + 7) / 8;
+    if (npiece > 48) return false;                      // 6 pieces per wave
+    const int pb = npiece * 1024;
+    const size_t need = (size_t)nbuf * pb + (size_t)ring * WSLOT;
+    if (need > 160 * 1024) return false;
+    if ((long long)a.ipe * a.H * a.W * a.in_ld * esz >= 0x7ff00000ll) return false;
+    ConvArgs& c = l->a;
+    c = a;
+    c.lTW = lTW; c.lTH = lTH; c.TN = TN;
+    c.n_groups = (a.ipe + TN - 1) / TN;
+    c.tiles_y = (a.Ho + (1 << lTH) - 1) >> lTH;
+    c.tiles_x = (a.Wo + (1 << lTW) - 1) >> lTW;
+    l->mblocks = (a.N / a.ipe) * c.n_groups * c.tiles_y * c.tiles_x;
+    l->smem = need < (size_t)BM / 2 * BN * 4 ? (size_t)BM / 2 * BN * 4 : need;
+    l->pbuf = pb;
+    return true;
 }
 
 // Which launches take this kernel: bf16, dense 3x3 stride 1 pad 1 (forward, or the flipped-filter data gradient), whole
 // 64-channel chunks, >= 128 output-channel rows, per-expert maps of >= 4096 pixels that tile into 16- or 32-pixel-wide
 // strips.  PMOE_CONV_DMA=0 sends them back to conv_igemm_lite_kernel (A/B runs; read per launch, so that tools/ab_conv.py can
-// interleave the two in one process).
-bool conv_dma_plan(ConvArgs& a, int dtype, int* mblocks, size_t* smem, int* pbuf) {
+// interleave the two in one process).  Which instantiation is chosen here too, with its switches (all read per launch):
+//  - 64 output-channel rows over >= 128 input channels, nothing but the convolution (+ statistics): conv3x3_dma_stream_kernel<false,
+//    true> (the 64 -> 64 layers belong to conv_res.hip's resident-filter kernels, which conv_select asks first).  PMOE_DMA_NARROW=0:
+//    back to the generic kernel.
+//  - the persistent, streaming instantiation (round 4): forward launches whose piece decode the magic-number division reproduces,
+//    two and four channel chunks (layer2: +24 %, layer3: +6 %); with eight (layer4: the prologue is 5 % of the tile) the 12-wave
+//    workgroup is 4 % slower than the 9-wave producer instantiation -- profiles/r04_kernel_ab.log, block 5.  PMOE_DMA_STREAM=0: off,
+//    2: always.
+//  - the producer-wave instantiation (round 4): forward launches -- nothing added to or derived from a side input in the epilogue --
+//    with >= 4 channel chunks: layer3 / layer4 forward +8 % / +12 %; with two chunks (layer2) the tile is prologue + epilogue for a
+//    third of its time and the ninth wave buys nothing (-2 %): profiles/r04_kernel_ab.log.  PMOE_DMA_PRODUCER=0: off, 2: every layer.
+//  - v_mfma_f32_16x16x32_bf16 for the layers with >= 4 channel chunks (interleaved A/B, profiles/r03_kernel_ab.log: layer3 forward
+//    +0.6 %, data gradient +3.5 %; layer4 +3.5 % / +5 %; layer2 -3 % / +0.7 %: the shorter the main loop, the less the shape's
+//    higher sustained clock buys).  PMOE_DMA_MF16=0 | 1 forces one shape.
+// The persistent kernel also needs rows 0..159 (NT = 2) or all 256 half-rows (NT = 1) of the epilogue's staging to fit the patch
+// buffer and its packed (image, row, column) piece fields to fit.
+bool conv_dma_plan(const ConvArgs& a, int dtype, ConvLaunch* l) {
     const char* ev = getenv("PMOE_CONV_DMA");
     if ((ev && !atoi(ev)) || dtype != PMOE_DT_BF16 || a.w_fp8) return false;
     if (a.ks != 3 || a.kh != 3 || a.kw != 3 || a.use_tapmap || a.stride != 1 || a.pad != 1 || a.dilate || a.in_shared) return false;
     if (a.out_step != 1 || a.Ho != a.H || a.Wo != a.W) return false;
     if (a.Cin % CK || a.Cout % 8 || a.N % a.ipe) return false;
-    // 64 output-channel rows: the NT = 1 instantiation of the persistent kernel only (forward launches, >= 2 channel chunks; the
-    // 64 -> 64 layers belong to conv_res.hip's resident-filter kernels, which conv_igemm_launch asks first)
-    const bool narrow = conv_dma_is_narrow(a);
+    const bool plain = a.res_mode == PMOE_RES_NONE && !a.bias && a.act == PMOE_ACT_NONE && a.drop_p == 0.f;
+    const char* evn = getenv("PMOE_DMA_NARROW");
+    bool narrow = !(evn && !atoi(evn)) && a.CoutP == 64 && a.Cin >= 2 * CK && plain;
+    const char* evs = getenv("PMOE_DMA_STREAM");
+    bool stream = !(evs && !atoi(evs)) && plain && (a.Cin <= 256 || (evs && atoi(evs) == 2));
+#ifdef PMOE_STAMP
+    narrow = stream = false;                             // (the stamped epilogue ends the workgroup after its first tile)
+#endif
     if (a.CoutP % BN && !narrow) return false;
-    if ((long long)a.ipe * a.Ho * a.Wo < 4096) return false;
-    auto p2 = [](int v) { int l = 0; while ((1 << l) < v) ++l; return l; };
-    int lTW = p2(a.Wo); if (lTW > 5) lTW = 5;
-    if (lTW < 4) return false;
-    int lTH = p2(a.Ho); if (lTH > 8 - lTW) lTH = 8 - lTW;
-    const int TN = BM >> (lTW + lTH);
-    const int NPIX = TN * ((1 << lTH) + 2) * ((1 << lTW) + 2);
-    const int npiece = (NPIX + 7) / 8;
-    if (npiece > 48) return false;                      // 6 pieces per wave
-    const int pb = npiece * 1024;
-    const size_t need = (size_t)2 * pb + RING * WSLOT;
-    if (need > 160 * 1024) return false;
-    // 32-bit source offsets inside one expert's images
-    if ((long long)a.ipe * a.H * a.W * a.in_ld * 2 >= 0x7ff00000ll) return false;
-    a.lTW = lTW; a.lTH = lTH; a.TN = TN;
-    a.n_groups = (a.ipe + TN - 1) / TN;
-    a.tiles_y = (a.Ho + (1 << lTH) - 1) >> lTH;
-    a.tiles_x = (a.Wo + (1 << lTW) - 1) >> lTW;
-    if (narrow && !stream_geometry_ok(a, pb)) return false;
-    *mblocks = (a.N / a.ipe) * a.n_groups * a.tiles_y * a.tiles_x;
-    *smem = need < (size_t)BM / 2 * BN * 4 ? (size_t)BM / 2 * BN * 4 : need;
-    *pbuf = pb;
+    if (!dma_tile(a, 2, 5, 2, RING, 2, l)) return false;
+    const ConvArgs& c = l->a;
+    const int PW = (1 << c.lTW) + 2, PH = (1 << c.lTH) + 2;
+    const int npiece = (c.TN * PH * PW + 7) / 8;
+    const bool stream_ok = l->pbuf >= 160 * 256 && magic_div_exact(npiece * 8, PW, PH, &l->mpw, &l->mph) &&
+                           c.TN * PH < 1024 && PW < 1024 && a.ipe < 2047;
+    if (narrow && !stream_ok) return false;
+    const char* evm = getenv("PMOE_DMA_MF16");
+    const char* evp = getenv("PMOE_DMA_PRODUCER");
+    l->kind = CONV_DMA;
+    l->narrow = narrow;
+    l->stream = narrow || (stream && stream_ok);
+    l->producer = !l->stream && !(evp && !atoi(evp)) && plain && (a.Cin >= 256 || (evp && atoi(evp) == 2));
+    l->mf16 = !narrow && (evm ? atoi(evm) != 0 : a.Cin >= 256);
+    // 5007 / 5017 = conv3x3_dma_kernel<MF16>, + 20 with the producer wave, + 40 = conv3x3_dma_stream_kernel<MF16>,
+    // 5067 = conv3x3_dma_stream_kernel<false, true> (64-cout tiles)
+    l->code = narrow ? 5067 : (l->mf16 ? 5017 : 5007) + (l->stream ? 40 : l->producer ? 20 : 0);
     return true;
 }
-
-bool conv_dma_uses_mf16(const ConvArgs& a) {
-    const char* ev = getenv("PMOE_DMA_MF16");
-    return ev ? atoi(ev) != 0 : a.Cin >= 256;
-}
-
-// the persistent, streaming instantiation (round 4): forward launches whose piece decode the magic-number division reproduces
-bool conv_dma_uses_stream(const ConvArgs& a0) {
-#ifdef PMOE_STAMP
-    return false;                                        // (the stamped epilogue ends the workgroup after its first tile)
-#endif
-    if (conv_dma_is_narrow(a0)) return true;             // (conv_dma_plan has checked the geometry)
-    const char* ev = getenv("PMOE_DMA_STREAM");
-    if (ev && !atoi(ev)) return false;
-    if (!(a0.res_mode == PMOE_RES_NONE && !a0.bias && a0.act == PMOE_ACT_NONE && a0.drop_p == 0.f)) return false;
-    // two and four channel chunks (layer2: +24 %, layer3: +6 %); with eight (layer4: the prologue is 5 % of the tile) the 12-wave
-    // workgroup is 4 % slower than the 9-wave producer instantiation -- profiles/r04_kernel_ab.log, block 5.  PMOE_DMA_STREAM=2: always
-    if (a0.Cin > 256 && !(ev && atoi(ev) == 2)) return false;
-    ConvArgs a = a0;
-    int mblocks = 0, pbuf = 0;
-    size_t smem = 0;
-    if (!conv_dma_plan(a, PMOE_DT_BF16, &mblocks, &smem, &pbuf)) return false;
-    return stream_geometry_ok(a, pbuf);
-}
-
-// the producer-wave instantiation (round 4): forward launches -- nothing added to or derived from a side input in the epilogue
-bool conv_dma_uses_producer(const ConvArgs& a) {
-    const char* ev = getenv("PMOE_DMA_PRODUCER");
-    if (ev && !atoi(ev)) return false;
-    // >= 4 channel chunks: layer3 / layer4 forward +8 % / +12 %; with two chunks (layer2) the tile is prologue + epilogue for a
-    // third of its time and the ninth wave buys nothing (-2 %): profiles/r04_kernel_ab.log.  PMOE_DMA_PRODUCER=2: every layer
-    if (a.Cin < 256 && !(ev && atoi(ev) == 2)) return false;
-    return a.res_mode == PMOE_RES_NONE && !a.bias && a.act == PMOE_ACT_NONE && a.drop_p == 0.f;
-}
-
-// plan code of a launch conv_dma_plan accepts: 5007 / 5017 = conv3x3_dma_kernel<MF16>, + 20 with the producer wave, + 40 =
-// conv3x3_dma_stream_kernel<MF16>, 5067 = conv3x3_dma_stream_kernel<false, true> (64-cout tiles)
-int conv_dma_plan_code(const ConvArgs& a) {
-    if (conv_dma_is_narrow(a)) return 5067;
-    return (conv_dma_uses_mf16(a) ? 5017 : 5007) + (conv_dma_uses_stream(a) ? 40 : conv_dma_uses_producer(a) ? 20 : 0);
-}
-
-int conv_dma_launch(ConvArgs a, hipStream_t st) {
-    int mblocks = 0, pbuf = 0;
-    size_t smem = 0;
-    if (!conv_dma_plan(a, PMOE_DT_BF16, &mblocks, &smem, &pbuf)) return PMOE_ERR_UNSUPPORTED;
-    // v_mfma_f32_16x16x32_bf16 for the layers with >= 4 channel chunks (interleaved A/B, profiles/r03_kernel_ab.log: layer3 forward
-    // +0.6 %, data gradient +3.5 %; layer4 +3.5 % / +5 %; layer2 -3 % / +0.7 %: the shorter the main loop, the less the shape's
-    // higher sustained clock buys).  PMOE_DMA_MF16=0 | 1 forces one shape (read per launch).
-    if (conv_dma_uses_stream(a)) {
-        // persistent workgroups, one per CU; the request stream of each runs across its tiles
-        const bool narrow = conv_dma_is_narrow(a);
-        const int ntiles = narrow ? mblocks : mblocks * (a.CoutP / BN);
-        const int PWp = (1 << a.lTW) + 2, PHp = (1 << a.lTH) + 2;
-        const int mpw = 65536 / PWp + 1, mph = 65536 / PHp + 1;
-        int grid = ntiles < 256 ? ntiles : 256;
-        if (narrow) {
-            HIP_RET((ensure_dyn_lds<conv3x3_dma_stream_kernel<false, true>>(160 * 1024)));
-            hipLaunchKernelGGL((conv3x3_dma_stream_kernel<false, true>), dim3(grid), dim3(NTHR + 4 * 64), smem, st, a, pbuf, ntiles, mpw, mph);
-        } else if (conv_dma_uses_mf16(a)) {
-            HIP_RET((ensure_dyn_lds<conv3x3_dma_stream_kernel<true>>(160 * 1024)));
-            hipLaunchKernelGGL((conv3x3_dma_stream_kernel<true>), dim3(grid), dim3(NTHR + 4 * 64), smem, st, a, pbuf, ntiles, mpw, mph);
-        } else {
-            HIP_RET((ensure_dyn_lds<conv3x3_dma_stream_kernel<false>>(160 * 1024)));
-            hipLaunchKernelGGL((conv3x3_dma_stream_kernel<false>), dim3(grid), dim3(NTHR + 4 * 64), smem, st, a, pbuf, ntiles, mpw, mph);
-        }
-    } else if (conv_dma_uses_producer(a)) {
-        if (conv_dma_uses_mf16(a)) {
-            HIP_RET((ensure_dyn_lds<conv3x3_dma_kernel<true, true>>(160 * 1024)));
-            hipLaunchKernelGGL((conv3x3_dma_kernel<true, true>), dim3(mblocks * (a.CoutP / BN)), dim3(NTHR + 64), smem, st, a, pbuf);
-        } else {
-            HIP_RET((ensure_dyn_lds<conv3x3_dma_kernel<false, true>>(160 * 1024)));
-            hipLaunchKernelGGL((conv3x3_dma_kernel<false, true>), dim3(mblocks * (a.CoutP / BN)), dim3(NTHR + 64), smem, st, a, pbuf);
-        }
-    } else if (conv_dma_uses_mf16(a)) {
-        HIP_RET((ensure_dyn_lds<conv3x3_dma_kernel<true>>(160 * 1024)));
-        hipLaunchKernelGGL(conv3x3_dma_kernel<true>, dim3(mblocks * (a.CoutP / BN)), dim3(NTHR), smem, st, a, pbuf);
-    } else {
-        HIP_RET((ensure_dyn_lds<conv3x3_dma_kernel<false>>(160 * 1024)));
-        hipLaunchKernelGGL(conv3x3_dma_kernel<false>, dim3(mblocks * (a.CoutP / BN)), dim3(NTHR), smem, st, a, pbuf);
-    }
-    return (int)hipGetLastError();
-}
-
 
 // Stride-2 3x3 forward convolutions (pad 1) of >= 128 output-channel rows over whole 64-channel chunks, bf16, output maps of
 // >= 4096 pixels per expert that tile into 16 x 16 squares: conv3x3s2_dma_kernel.  PMOE_CONV_S2DMA=0: back to the generic
 // kernel (A/B runs; read per launch).
-bool conv_dma_s2_plan(ConvArgs& a, int dtype, int* mblocks, size_t* smem, int* pbuf) {
+bool conv_dma_s2_plan(const ConvArgs& a, int dtype, ConvLaunch* l) {
     const char* ev = getenv("PMOE_CONV_S2DMA");
     if ((ev && !atoi(ev)) || dtype != PMOE_DT_BF16 || a.w_fp8) return false;
     if (a.ks != 3 || a.kh != 3 || a.kw != 3 || a.use_tapmap || a.stride != 2 || a.pad != 1 || a.dilate || a.in_shared) return false;
     if (a.out_step != 1 || a.Ho != (a.H - 1) / 2 + 1 || a.Wo != (a.W - 1) / 2 + 1) return false;
     if (a.Cin % CK || a.CoutP % BN || a.Cout % 8 || a.N % a.ipe) return false;
     if (a.res_mode == PMOE_RES_DBN) return false;
-    if ((long long)a.ipe * a.Ho * a.Wo < 4096) return false;
-    auto p2 = [](int v) { int l = 0; while ((1 << l) < v) ++l; return l; };
-    int lTW = p2(a.Wo); if (lTW > 4) lTW = 4;
-    if (lTW < 4) return false;
-    int lTH = p2(a.Ho); if (lTH > 8 - lTW) lTH = 8 - lTW;
-    const int TN = BM >> (lTW + lTH);
-    const int NPIX = TN * ((1 << lTH) + 1) * ((1 << lTW) + 1);
-    const int npiece = (NPIX + 7) / 8;
-    if (npiece > 48) return false;
-    const int pb = npiece * 1024;
-    const size_t need = (size_t)3 * pb + RING3 * WSLOT;
-    if (need > 160 * 1024) return false;
-    if ((long long)a.ipe * a.H * a.W * a.in_ld * 2 >= 0x7ff00000ll) return false;
-    a.lTW = lTW; a.lTH = lTH; a.TN = TN;
-    a.n_groups = (a.ipe + TN - 1) / TN;
-    a.tiles_y = (a.Ho + (1 << lTH) - 1) >> lTH;
-    a.tiles_x = (a.Wo + (1 << lTW) - 1) >> lTW;
-    *mblocks = (a.N / a.ipe) * a.n_groups * a.tiles_y * a.tiles_x;
-    *smem = need < (size_t)BM / 2 * BN * 4 ? (size_t)BM / 2 * BN * 4 : need;
-    *pbuf = pb;
+    if (!dma_tile(a, 1, 4, 3, RING3, 2, l)) return false;
+    l->kind = CONV_DMA_S2;
+    l->code = 5207;
     return true;
 }
 
-int conv_dma_s2_launch(ConvArgs a, hipStream_t st) {
-    int mblocks = 0, pbuf = 0;
-    size_t smem = 0;
-    if (!conv_dma_s2_plan(a, PMOE_DT_BF16, &mblocks, &smem, &pbuf)) return PMOE_ERR_UNSUPPORTED;
-    HIP_RET((ensure_dyn_lds<conv3x3s2_dma_kernel<false>>(160 * 1024)));
-    hipLaunchKernelGGL(conv3x3s2_dma_kernel<false>, dim3(mblocks * (a.CoutP / BN)), dim3(NTHR), smem, st, a, pbuf);
-    return (int)hipGetLastError();
-}
-
-// One parity class of a stride-2 3x3 data gradient (the class fields of ConvArgs set by launch_stride2_dgrad, conv_igemm.hip):
-// bf16, whole 64-channel chunks of dy, gradient rows in multiples of 64, class lattices of >= 4096 pixels per expert that tile
-// into 16 x 16 squares.  PMOE_CONV_S2DMA=0: back to the generic kernel.
-bool conv_dma_s2cls_plan(ConvArgs& a, int dtype, int* mblocks, size_t* smem, int* pbuf) {
+// One parity class of a stride-2 3x3 data gradient (the class fields of ConvArgs set by conv_select, conv_igemm.hip): bf16, whole
+// 64-channel chunks of dy, gradient rows in multiples of 64, class lattices of >= 4096 pixels per expert that tile into 16 x 16
+// squares.  PMOE_CONV_S2DMA=0: back to the generic kernel.
+bool conv_dma_s2cls_plan(const ConvArgs& a, int dtype, ConvLaunch* l) {
     const char* ev = getenv("PMOE_CONV_S2DMA");
     if ((ev && !atoi(ev)) || dtype != PMOE_DT_BF16 || a.w_fp8) return false;
     if (a.ks != 3 || !a.use_tapmap || a.out_step != 2 || a.stride != 1 || a.pad != 0 || a.dilate || a.in_shared) return false;
@@ -1377,76 +1288,56 @@ bool conv_dma_s2cls_plan(ConvArgs& a, int dtype, int* mblocks, size_t* smem, int
     //  PMOE_S2CLS_64=1 admits them for that A/B)
     const char* e64 = getenv("PMOE_S2CLS_64");
     if (a.Cin % CK || a.CoutP % ((e64 && atoi(e64)) ? 64 : BN) || a.Cout % 8 || a.N % a.ipe || a.stats || a.res_mode > PMOE_RES_ADD) return false;
-    if ((long long)a.ipe * a.Ho * a.Wo < 4096) return false;
-    auto p2 = [](int v) { int l = 0; while ((1 << l) < v) ++l; return l; };
-    int lTW = p2(a.Wo); if (lTW > 4) lTW = 4;
-    if (lTW < 4) return false;
-    int lTH = p2(a.Ho); if (lTH > 8 - lTW) lTH = 8 - lTW;
-    const int TN = BM >> (lTW + lTH);
-    const int NPIX = TN * ((1 << lTH) + 1) * ((1 << lTW) + 1);
-    const int npiece = (NPIX + 7) / 8;
-    if (npiece > 48) return false;
-    const int pb = npiece * 1024;
-    const size_t need = (size_t)3 * pb + RING3 * WSLOT;
-    if (need > 160 * 1024) return false;
-    if ((long long)a.ipe * a.H * a.W * a.in_ld * 2 >= 0x7ff00000ll) return false;
-    a.lTW = lTW; a.lTH = lTH; a.TN = TN;
-    a.n_groups = (a.ipe + TN - 1) / TN;
-    a.tiles_y = (a.Ho + (1 << lTH) - 1) >> lTH;
-    a.tiles_x = (a.Wo + (1 << lTW) - 1) >> lTW;
-    *mblocks = (a.N / a.ipe) * a.n_groups * a.tiles_y * a.tiles_x;
-    *smem = need < (size_t)BM / 2 * BN * 4 ? (size_t)BM / 2 * BN * 4 : need;
-    *pbuf = pb;
+    if (!dma_tile(a, 1, 4, 3, RING3, 2, l)) return false;
+    l->kind = CONV_DMA_S2CLS;
+    l->code = 5207;
     return true;
 }
-
-int conv_dma_s2cls_launch(ConvArgs a, hipStream_t st) {
-    int mblocks = 0, pbuf = 0;
-    size_t smem = 0;
-    if (!conv_dma_s2cls_plan(a, PMOE_DT_BF16, &mblocks, &smem, &pbuf)) return PMOE_ERR_UNSUPPORTED;
-    HIP_RET((ensure_dyn_lds<conv3x3s2_dma_kernel<true>>(160 * 1024)));
-    hipLaunchKernelGGL(conv3x3s2_dma_kernel<true>, dim3(mblocks * ((a.CoutP + BN - 1) / BN)), dim3(NTHR), smem, st, a, pbuf);
-    return (int)hipGetLastError();
-}
-
 
 // BASELINE config 5 on the block-scaled fp8 matrix instruction: e4m3 weights AND e4m3 activations in HBM (ConvArgs.in_fp8), dense
 // 3x3 stride 1, whole 128-channel chunks, >= 128 output-channel rows, maps of >= 4096 pixels per expert.  PMOE_CONV_F8DMA=0: the
 // activations go through the bf16 -> e4m3 converting loaders of round 2 instead.
-bool conv_dma_f8_plan(ConvArgs& a, int dtype, int* mblocks, size_t* smem, int* pbuf) {
+bool conv_dma_f8_plan(const ConvArgs& a, int dtype, ConvLaunch* l) {
     const char* ev = getenv("PMOE_CONV_F8DMA");
     if ((ev && !atoi(ev)) || dtype != PMOE_DT_BF16 || !a.w_fp8 || !a.in_fp8 || !a.oscale) return false;
     if (a.ks != 3 || a.kh != 3 || a.kw != 3 || a.use_tapmap || a.stride != 1 || a.pad != 1 || a.dilate || a.in_shared) return false;
     if (a.out_step != 1 || a.Ho != a.H || a.Wo != a.W || a.res_mode != PMOE_RES_NONE) return false;
     if (a.Cin % 128 || a.CoutP % BN || a.Cout % 8 || a.N % a.ipe || a.in_ld % 16 || a.in_coff % 16) return false;
-    if ((long long)a.ipe * a.Ho * a.Wo < 4096) return false;
-    auto p2 = [](int v) { int l = 0; while ((1 << l) < v) ++l; return l; };
-    int lTW = p2(a.Wo); if (lTW > 5) lTW = 5;
-    if (lTW < 4) return false;
-    int lTH = p2(a.Ho); if (lTH > 8 - lTW) lTH = 8 - lTW;
-    const int TN = BM >> (lTW + lTH);
-    const int NPIX = TN * ((1 << lTH) + 2) * ((1 << lTW) + 2);
-    const int npiece = (NPIX + 7) / 8;
-    if (npiece > 48) return false;
-    const int pb = npiece * 1024;
-    const size_t need = (size_t)2 * pb + RING * WSLOT;
-    if (need > 160 * 1024) return false;
-    if ((long long)a.ipe * a.H * a.W * a.in_ld >= 0x7ff00000ll) return false;
-    a.lTW = lTW; a.lTH = lTH; a.TN = TN;
-    a.n_groups = (a.ipe + TN - 1) / TN;
-    a.tiles_y = (a.Ho + (1 << lTH) - 1) >> lTH;
-    a.tiles_x = (a.Wo + (1 << lTW) - 1) >> lTW;
-    *mblocks = (a.N / a.ipe) * a.n_groups * a.tiles_y * a.tiles_x;
-    *smem = need < (size_t)BM / 2 * BN * 4 ? (size_t)BM / 2 * BN * 4 : need;
-    *pbuf = pb;
+    if (!dma_tile(a, 2, 5, 2, RING, 1, l)) return false;
+    l->kind = CONV_DMA_F8;
+    l->code = 8507;
     return true;
 }
 
-int conv_dma_f8_launch(ConvArgs a, hipStream_t st) {
-    int mblocks = 0, pbuf = 0;
-    size_t smem = 0;
-    if (!conv_dma_f8_plan(a, PMOE_DT_BF16, &mblocks, &smem, &pbuf)) return PMOE_ERR_UNSUPPORTED;
-    HIP_RET((ensure_dyn_lds<conv3x3_dma_f8_kernel>(160 * 1024)));
-    hipLaunchKernelGGL(conv3x3_dma_f8_kernel, dim3(mblocks * (a.CoutP / BN)), dim3(NTHR), smem, st, a, pbuf);
+template <auto KERNEL, typename... Args> static int dma_go(dim3 grid, int nthr, size_t smem, hipStream_t st, Args... args) {
+    HIP_RET((ensure_dyn_lds<KERNEL>(160 * 1024)));
+    hipLaunchKernelGGL(KERNEL, grid, dim3(nthr), smem, st, args...);
     return (int)hipGetLastError();
+}
+
+int conv_dma_launch(const ConvLaunch& l, hipStream_t st) {
+    const ConvArgs& a = l.a;
+    const int wgs = l.mblocks * (a.CoutP / BN);
+    switch (l.kind) {
+    case CONV_DMA_F8: return dma_go<conv3x3_dma_f8_kernel>(dim3(wgs), NTHR, l.smem, st, a, l.pbuf);
+    case CONV_DMA_S2: return dma_go<conv3x3s2_dma_kernel<false>>(dim3(wgs), NTHR, l.smem, st, a, l.pbuf);
+    case CONV_DMA_S2CLS:
+        return dma_go<conv3x3s2_dma_kernel<true>>(dim3(l.mblocks * ((a.CoutP + BN - 1) / BN)), NTHR, l.smem, st, a, l.pbuf);
+    case CONV_DMA: break;
+    default: return PMOE_ERR_ARG;
+    }
+    if (l.stream) {
+        // persistent workgroups, one per CU; the request stream of each runs across its tiles
+        const int ntiles = l.narrow ? l.mblocks : wgs;
+        const dim3 grid(ntiles < 256 ? ntiles : 256);
+        if (l.narrow) return dma_go<conv3x3_dma_stream_kernel<false, true>>(grid, NTHR + 4 * 64, l.smem, st, a, l.pbuf, ntiles, l.mpw, l.mph);
+        if (l.mf16) return dma_go<conv3x3_dma_stream_kernel<true>>(grid, NTHR + 4 * 64, l.smem, st, a, l.pbuf, ntiles, l.mpw, l.mph);
+        return dma_go<conv3x3_dma_stream_kernel<false>>(grid, NTHR + 4 * 64, l.smem, st, a, l.pbuf, ntiles, l.mpw, l.mph);
+    }
+    if (l.producer) {
+        if (l.mf16) return dma_go<conv3x3_dma_kernel<true, true>>(dim3(wgs), NTHR + 64, l.smem, st, a, l.pbuf);
+        return dma_go<conv3x3_dma_kernel<false, true>>(dim3(wgs), NTHR + 64, l.smem, st, a, l.pbuf);
+    }
+    if (l.mf16) return dma_go<conv3x3_dma_kernel<true>>(dim3(wgs), NTHR, l.smem, st, a, l.pbuf);
+    return dma_go<conv3x3_dma_kernel<false>>(dim3(wgs), NTHR, l.smem, st, a, l.pbuf);
 }

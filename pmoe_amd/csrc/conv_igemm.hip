@@ -16,6 +16,7 @@
 // over experts with TN samples per tile).
 #include "conv_common.h"
 #include <stdlib.h>
+#include <string.h>
 #include "kernels.h"
 
 template <int LOG_RB> __device__ __forceinline__ int swz(int x) { return swz_chunk<LOG_RB, 0>(x); }
@@ -442,20 +443,26 @@ static int launch_cfg(const ConvArgs& a, int mblocks, size_t smem, hipStream_t s
     return (int)hipGetLastError();
 }
 
-template <typename T, typename TL = T> static int launch_dtype(ConvArgs a, hipStream_t st, int* out_mblocks, int* out_cfg = nullptr) {
-    const int esz = (int)sizeof(TL);                // operand element size in LDS
-    constexpr bool F8 = sizeof(TL) != sizeof(T);
-    if (a.Cin <= 0 || a.CoutP % 64 || a.Cout % (16 / (int)sizeof(T)) || a.Cin % (32 / esz)) return PMOE_ERR_ARG;
-    if (F8 && (a.Cin % 64 || (!out_mblocks && (!a.oscale || !(a.in_scale > 0.f))))) return PMOE_ERR_ARG;
+static int env_switch(const char* name) { const char* ev = getenv(name); return ev ? atoi(ev) : 1; }
+
+// The tile of conv_igemm_body for a descriptor whose activations have `tsz`-byte elements (2 = bf16, 4 = f32) and whose MFMA
+// operands `esz`-byte elements in LDS (tsz, or 1: e4m3 weights).  Fills the tile fields of l->a with its chunk prefetch and
+// stagger, the instantiation and the launch sizes.
+static int tile_plan(const ConvArgs& a, int tsz, int esz, ConvLaunch* l) {
+    const bool F8 = esz != tsz;
+    if (a.Cin <= 0 || a.CoutP % 64 || a.Cout % (16 / tsz) || a.Cin % (32 / esz)) return PMOE_ERR_ARG;
+    if (F8 && a.Cin % 64) return PMOE_ERR_ARG;
     if ((a.ks != 1 && a.ks != 3) || (a.stride != 1 && a.stride != 2) || (a.dilate && a.stride != 1)) return PMOE_ERR_ARG;
     if (a.N % a.ipe) return PMOE_ERR_ARG;
+    // A/B switches, read once: PMOE_CONV_CFG42=0 back to the 4-wave tile, PMOE_CONV_LITE=0 / PMOE_CONV_STAGGER=0 /
+    // PMOE_CONV_PREFETCH=0 without the LITE instantiation / the stagger / the chunk prefetch
+    static const int cfg42 = env_switch("PMOE_CONV_CFG42"), lite_on = env_switch("PMOE_CONV_LITE"),
+                     stg_on = env_switch("PMOE_CONV_STAGGER"), pf_on = env_switch("PMOE_CONV_PREFETCH");
     const int E = a.N / a.ipe;
     const bool wide = (a.CoutP % 128 == 0);
     // bf16, >= 128 output channels: 8 waves on a 256-pixel x 128-channel tile (each weight tile and each barrier serves
     // twice the pixels of the 4-wave 128 x 128 tile: +5-8 % on the 3x3 layers, +30 % on the stride-2 forward convs)
-    static int cfg42 = -1;      // PMOE_CONV_CFG42=0 switches back to the 4-wave tile (A/B measurements)
-    if (cfg42 < 0) { const char* ev = getenv("PMOE_CONV_CFG42"); cfg42 = ev ? atoi(ev) : 1; }
-    const bool big = wide && cfg42 && sizeof(T) == 2 && (long long)a.ipe * a.Ho * a.Wo >= 4096;   // not the MLP GEMMs
+    const bool big = wide && cfg42 && tsz == 2 && (long long)a.ipe * a.Ho * a.Wo >= 4096;   // not the MLP GEMMs
     const int log_rb_min = F8 ? 6 : 5;              // fp8: 64 or 128 channels per chunk
     // (measured on the stage-1 U-Net at B = 10, where the 28x28 / 14x14 layers give < 256 workgroups: falling back to the
     // 128-pixel 4-wave tile to double the workgroup count is SLOWER, 41.9 vs 32.3 ms of conv time per step)
@@ -477,69 +484,82 @@ template <typename T, typename TL = T> static int launch_dtype(ConvArgs a, hipSt
         const int nthr = big ? 512 : 256;
         // 64-channel chunks: the LITE instantiation (<= 128 VGPRs, 73 KiB LDS) puts TWO 8-wave workgroups on a CU, which
         // beats one workgroup with chunk prefetch + stagger by 12-30 % (l2 +12 %, l3 +30 %, l4 +25 %: 980-1000 TFLOP/s).
-        // PMOE_CONV_LITE=0 switches back for A/B runs.
-        static int lite_on = -1;
-        if (lite_on < 0) { const char* ev = getenv("PMOE_CONV_LITE"); lite_on = ev ? atoi(ev) : 1; }
         const bool lite = lite_on && big && log_rb == 7 && pbytes + 2 * (size_t)BN * rb <= 80 * 1024;   // two must fit a CU
-        static int stg_on = -1;     // PMOE_CONV_STAGGER=0: A/B switch
-        if (stg_on < 0) { const char* ev = getenv("PMOE_CONV_STAGGER"); stg_on = ev ? atoi(ev) : 1; }
-        a.stagger = stg_on && big && !lite;
         // (LITE with every load of a chunk's halo patch in flight at once -- one L2 round trip instead of two -- measured
         // within noise, +-2 %, and tools/stamp_conv.py still showed 28 % of the wave cycles in patch staging: the cost is
         // not the number of round trips)
-        static int pf_on = -1;      // PMOE_CONV_PREFETCH=0: A/B switch
-        if (pf_on < 0) { const char* ev = getenv("PMOE_CONV_PREFETCH"); pf_on = ev ? atoi(ev) : 1; }
         // (also the expert MLP GEMMs: 1x1 "images", K = 512..1536 in 64-channel chunks -- a latency chain of 8..24 chunks)
-        a.prefetch = !F8 && !lite && pf_on && (big || (a.H == 1 && a.W == 1 && a.ks == 1)) && a.Cin / ck >= 2 && (size_t)TN * PH * PW * (rb / 16) <= (size_t)6 * nthr &&
-                     2 * pbytes + 2 * (size_t)BN * rb <= 150 * 1024;
-        size_t smem = pbytes * (a.prefetch ? 2 : 1) + 2 * (size_t)BN * rb;
+        const bool prefetch = !F8 && !lite && pf_on && (big || (a.H == 1 && a.W == 1 && a.ks == 1)) && a.Cin / ck >= 2 &&
+                              (size_t)TN * PH * PW * (rb / 16) <= (size_t)6 * nthr && 2 * pbytes + 2 * (size_t)BN * rb <= 150 * 1024;
+        size_t smem = pbytes * (prefetch ? 2 : 1) + 2 * (size_t)BN * rb;
         const size_t stg = (size_t)BM * BN * 4 / (lite ? 2 : 1);
         if (smem < stg) smem = stg;
         if (smem > 150 * 1024) continue;
-        a.lTW = lTW; a.lTH = lTH; a.TN = TN;
-        a.n_groups = (a.ipe + TN - 1) / TN;
-        a.tiles_y = (a.Ho + TH - 1) / TH;
-        a.tiles_x = (a.Wo + TW - 1) / TW;
-        const int mblocks = E * a.n_groups * a.tiles_y * a.tiles_x;
-        if (out_cfg) *out_cfg = (F8 ? 8000 : 0) + (lite ? 2000 + log_rb : log_rb * 100 + (wide ? (big ? 42 : 22) : 41));   // see conv_igemm_plan
-        if (out_mblocks) { *out_mblocks = mblocks; return 0; }
-        if constexpr (F8) {
-            if (lite) return launch_lite<T, 7, TL>(a, mblocks, smem, st);
-            if (log_rb == 7 && big) return launch_cfg<T, 7, 4, 2, TL>(a, mblocks, smem, st);
-            if (log_rb == 6 && big) return launch_cfg<T, 6, 4, 2, TL>(a, mblocks, smem, st);
-            if (log_rb == 7) return wide ? launch_cfg<T, 7, 2, 2, TL>(a, mblocks, smem, st) : launch_cfg<T, 7, 4, 1, TL>(a, mblocks, smem, st);
-            return wide ? launch_cfg<T, 6, 2, 2, TL>(a, mblocks, smem, st) : launch_cfg<T, 6, 4, 1, TL>(a, mblocks, smem, st);
-        }
-        if (lite) return launch_lite<T, 7>(a, mblocks, smem, st);
-        if (log_rb == 7 && big) return launch_cfg<T, 7, 4, 2>(a, mblocks, smem, st);
-        if (log_rb == 6 && big) return launch_cfg<T, 6, 4, 2>(a, mblocks, smem, st);
-        if (log_rb == 5 && big) return launch_cfg<T, 5, 4, 2>(a, mblocks, smem, st);
-        if (log_rb == 7) return wide ? launch_cfg<T, 7, 2, 2>(a, mblocks, smem, st) : launch_cfg<T, 7, 4, 1>(a, mblocks, smem, st);
-        if (log_rb == 6) return wide ? launch_cfg<T, 6, 2, 2>(a, mblocks, smem, st) : launch_cfg<T, 6, 4, 1>(a, mblocks, smem, st);
-        return wide ? launch_cfg<T, 5, 2, 2>(a, mblocks, smem, st) : launch_cfg<T, 5, 4, 1>(a, mblocks, smem, st);
+        ConvArgs& c = l->a;
+        c = a;
+        c.stagger = stg_on && big && !lite;
+        c.prefetch = prefetch;
+        c.lTW = lTW; c.lTH = lTH; c.TN = TN;
+        c.n_groups = (a.ipe + TN - 1) / TN;
+        c.tiles_y = (a.Ho + TH - 1) / TH;
+        c.tiles_x = (a.Wo + TW - 1) / TW;
+        l->kind = CONV_TILE;
+        l->mblocks = E * c.n_groups * c.tiles_y * c.tiles_x;
+        l->smem = smem;
+        l->log_rb = log_rb; l->lite = lite;
+        l->wm = big || !wide ? 4 : 2; l->wn = wide ? 2 : 1;
+        l->code = (F8 ? 8000 : 0) + (lite ? 2000 + log_rb : log_rb * 100 + l->wm * 10 + l->wn);
+        return 0;
     }
     return PMOE_ERR_UNSUPPORTED;
 }
 
-// resident-weight ping-pong kernel for the <=64-channel 3x3 stride-1 layers (conv_res.hip)
-struct ResPlan {
-    int lTW, lTH, TN, n_groups, tiles_y, tiles_x, tiles_per_expert, wgs_per_expert, log_rb;
-    size_t smem;
-};
-bool conv_res_plan(const ConvArgs& a, int dtype, ResPlan* plan);
-bool conv_res_pipe_ok(const ConvArgs& a);
-bool conv_res_dma_ok(const ConvArgs& a, const ResPlan& p, int* pbuf, int* magic_pw, int* magic_ph, size_t* smem);
-bool conv_c16_plan(const ConvArgs& a, int dtype, int* wgs_per_expert, int* tiles_x, int* tiles_per_expert);
-int conv_c16_launch(const ConvArgs& a, hipStream_t st);
-bool conv_c1x1_plan(const ConvArgs& a, int dtype, int* wgs_per_expert, int* tiles_per_expert, int* n_slabs, int* mt, size_t* smem);
-int conv_c1x1_launch(const ConvArgs& a, hipStream_t st);
-int conv_res_launch(ConvArgs a, const ResPlan& p, hipStream_t st);
+static int tile_plan_dtype(const ConvArgs& a, int dtype, ConvLaunch* l) {
+    return dtype == PMOE_DT_BF16 ? tile_plan(a, 2, 2, l) : dtype == PMOE_DT_F32 ? tile_plan(a, 4, 4, l) : PMOE_ERR_ARG;
+}
+
+template <typename T, typename TL = T> static int tile_launch(const ConvLaunch& l, hipStream_t st) {
+    const ConvArgs& a = l.a;
+    if (l.lite) return launch_lite<T, 7, TL>(a, l.mblocks, l.smem, st);
+    switch (l.log_rb * 100 + l.wm * 10 + l.wn) {
+    case 742: return launch_cfg<T, 7, 4, 2, TL>(a, l.mblocks, l.smem, st);
+    case 642: return launch_cfg<T, 6, 4, 2, TL>(a, l.mblocks, l.smem, st);
+    case 722: return launch_cfg<T, 7, 2, 2, TL>(a, l.mblocks, l.smem, st);
+    case 741: return launch_cfg<T, 7, 4, 1, TL>(a, l.mblocks, l.smem, st);
+    case 622: return launch_cfg<T, 6, 2, 2, TL>(a, l.mblocks, l.smem, st);
+    case 641: return launch_cfg<T, 6, 4, 1, TL>(a, l.mblocks, l.smem, st);
+    }
+    if constexpr (sizeof(TL) == sizeof(T)) {         // (e4m3 operands come in 64- and 128-channel chunks only)
+        switch (l.log_rb * 100 + l.wm * 10 + l.wn) {
+        case 542: return launch_cfg<T, 5, 4, 2>(a, l.mblocks, l.smem, st);
+        case 522: return launch_cfg<T, 5, 2, 2>(a, l.mblocks, l.smem, st);
+        case 541: return launch_cfg<T, 5, 4, 1>(a, l.mblocks, l.smem, st);
+        }
+    }
+    return PMOE_ERR_UNSUPPORTED;
+}
+
+static int launch_one(const ConvLaunch& l, int dtype, hipStream_t st) {
+    switch (l.kind) {
+    case CONV_SKINNY: return gemm_skinny_launch(l, st);
+    case CONV_C16: return conv_c16_launch(l, st);
+    case CONV_C1X1: return conv_c1x1_launch(l, st);
+    case CONV_RES: return conv_res_launch(l, st);
+    case CONV_DMA: case CONV_DMA_S2: case CONV_DMA_S2CLS: case CONV_DMA_F8: return conv_dma_launch(l, st);
+    case CONV_TILE:
+        if (l.a.w_fp8) return !l.a.oscale || !(l.a.in_scale > 0.f) ? PMOE_ERR_ARG : tile_launch<bf16, fp8>(l, st);
+        return dtype == PMOE_DT_BF16 ? tile_launch<bf16>(l, st) : tile_launch<float>(l, st);
+    }
+    return PMOE_ERR_ARG;
+}
 
 // stride-2 3x3 data gradient (forward pad 1) by output parity class instead of a zero-dilated source: dx[2a+py][2b+px]
 // only receives the taps ky = 1 (py = 0) or ky in {2, 0} at dy rows {a, a+1} (py = 1), same along x -> 1+2+2+4 = 9 tap
-// visits per 2x2 output pixels instead of 36.  Weight taps are those of the flipped dgrad packing (fy = 2 - ky).
+// visits per 2x2 output pixels instead of 36.  Weight taps are those of the flipped dgrad packing (fy = 2 - ky).  Each class
+// runs on the LDS-DMA kernel or the generic tile.
 // (One launch with the class in the block index was measured slower: LDS sized for the widest class, uneven work.)
-static int launch_stride2_dgrad(const ConvArgs& a, int dtype, hipStream_t st) {
+static int select_stride2_dgrad(const ConvArgs& a, int dtype, ConvPlan* p) {
+    p->n = 0;
     for (int py = 0; py < 2; ++py)
         for (int px = 0; px < 2; ++px) {
             ConvArgs c = a;
@@ -554,213 +574,86 @@ static int launch_stride2_dgrad(const ConvArgs& a, int dtype, hipStream_t st) {
                     const int fy = py ? (r == 0 ? 0 : 2) : 1, fx = px ? (q == 0 ? 0 : 2) : 1;
                     c.tapmap[r * c.kw + q] = fy * 3 + fx;
                 }
-            {
-                ConvArgs d = c;
-                int mb, pb;
-                size_t sm;
-                if (conv_dma_s2cls_plan(d, dtype, &mb, &sm, &pb)) {          // LDS-DMA kernel (conv_dma.hip)
-                    const int rcd = conv_dma_s2cls_launch(c, st);
-                    if (rcd) return rcd;
-                    continue;
-                }
+            ConvLaunch* l = &p->l[p->n++];
+            if (!conv_dma_s2cls_plan(c, dtype, l)) {
+                const int rc = tile_plan_dtype(c, dtype, l);
+                if (rc) return rc;
             }
-            const int rc = dtype == PMOE_DT_BF16 ? launch_dtype<bf16>(c, st, nullptr)
-                         : dtype == PMOE_DT_F32 ? launch_dtype<float>(c, st, nullptr) : PMOE_ERR_ARG;
-            if (rc) return rc;
         }
-    return 0;
+    if (!p->n) return PMOE_ERR_ARG;
+    // the class launches do not combine statistics: rows of the zero-dilated single launch they replace, >= each one's
+    ConvLaunch t;
+    const int esz = dtype == PMOE_DT_BF16 ? 2 : 4, rc = tile_plan(a, esz, esz, &t);
+    p->mblocks = rc ? rc : t.mblocks;
+    return 4000 + p->l[p->n - 1].code;                   // (the widest class: (1, 1) wherever the gradient has two rows and columns)
 }
 
-// stride-2 1x1 data gradient (the ResNet downsample conv) ACCUMULATED IN PLACE into an existing gradient: only the
-// even-even pixels receive anything, so one class-(0,0) launch adds there and the other 3/4 of the tensor is not touched
-// (the zero-dilated form reads and rewrites all of it).
-static int launch_stride2_1x1_inplace(const ConvArgs& a, int dtype, hipStream_t st) {
-    ConvArgs c = a;
-    c.dilate = 0; c.stride = 1; c.pad = 0; c.kh = c.kw = 1;
-    c.Ho = (a.Ho + 1) / 2; c.Wo = (a.Wo + 1) / 2;
-    c.OH = a.Ho; c.OW = a.Wo; c.out_step = 2; c.out_offy = c.out_offx = 0;
-    return dtype == PMOE_DT_BF16 ? launch_dtype<bf16>(c, st, nullptr)
-         : dtype == PMOE_DT_F32 ? launch_dtype<float>(c, st, nullptr) : PMOE_ERR_ARG;
+// Which kernel launches serve a descriptor -- the one decision tree behind pmoe_conv2d_igemm, pmoe_conv2d_plan and
+// pmoe_conv2d_stat_rows.  Returns p->code: the plan code (include/pmoe_hip.h), or a PMOE_ERR_* when nothing can run.
+int conv_select(const ConvArgs& a, int dtype, ConvPlan* p) {
+    memset(p, 0, sizeof(*p));
+    p->n = 1;
+    ConvLaunch* l = p->l;
+    int code = 0;
+    if (a.shuf_c) {                                  // ConvTranspose2d scatter fused into the store: the 1x1 direct kernel only
+        code = conv_c1x1_plan(a, dtype, l) ? 0 : PMOE_ERR_UNSUPPORTED;
+    } else if (a.w_fp8) {                            // e4m3 weights: forward convs
+        if (dtype != PMOE_DT_BF16 || a.dilate) code = PMOE_ERR_ARG;
+        else if (a.in_fp8) code = conv_dma_f8_plan(a, dtype, l) ? 0 : PMOE_ERR_UNSUPPORTED;   // e4m3 activations too: that kernel or nothing
+        else code = tile_plan(a, 2, 1, l);
+    } else if (a.res_mode == PMOE_RES_INBN) {        // BatchNorm + ReLU of the INPUT on load: conv3x3_respipe_kernel<false, 3> or
+        if (!(!a.bias && conv_res_plan(a, dtype, l) && l->res_pipe) && !conv_c1x1_plan(a, dtype, l))     // conv1x1_direct_kernel<MT, true>
+            code = PMOE_ERR_UNSUPPORTED;
+    } else if (a.res_mode == PMOE_RES_DBN) {         // BatchNorm-backward reductions in the epilogue: the two LDS-DMA kernels only
+        if (!(conv_res_plan(a, dtype, l) && l->res_dma) && (gemm_skinny_plan(a, dtype, l) || !conv_dma_plan(a, dtype, l)))
+            code = PMOE_ERR_UNSUPPORTED;
+    } else if (a.dilate && a.ks == 3 && a.pad == 1 && a.kh == 3) {
+        const int code = select_stride2_dgrad(a, dtype, p);
+        if (code < 0) p->n = 0;
+        return p->code = code;
+    } else if (a.dilate && a.ks == 1 && a.pad == 0 && a.res_mode == PMOE_RES_ADD && a.res == a.out && a.res_ld == a.out_ld &&
+               a.res_coff == a.out_coff && !a.bias && a.act == PMOE_ACT_NONE && a.drop_p == 0.f) {
+        // stride-2 1x1 data gradient (the ResNet downsample conv) ACCUMULATED IN PLACE into an existing gradient: only the
+        // even-even pixels receive anything, so one class-(0,0) launch adds there and the other 3/4 of the tensor is not touched
+        // (the zero-dilated form reads and rewrites all of it).
+        ConvArgs c = a;
+        c.dilate = 0; c.stride = 1; c.pad = 0; c.kh = c.kw = 1;
+        c.Ho = (a.Ho + 1) / 2; c.Wo = (a.Wo + 1) / 2;
+        c.OH = a.Ho; c.OW = a.Wo; c.out_step = 2; c.out_offy = c.out_offx = 0;
+        code = tile_plan_dtype(c, dtype, l);
+    } else if (!gemm_skinny_plan(a, dtype, l) && !conv_c16_plan(a, dtype, l) && !conv_c1x1_plan(a, dtype, l) &&
+               !conv_res_plan(a, dtype, l) && !conv_dma_plan(a, dtype, l) && !conv_dma_s2_plan(a, dtype, l)) {
+        code = tile_plan_dtype(a, dtype, l);
+    }
+    if (code < 0) { p->n = 0; return p->code = code; }
+    p->mblocks = l->mblocks;
+    return p->code = l->code;
 }
 
 int conv_igemm_launch(const ConvArgs& a, int dtype, hipStream_t st) {
-    if (a.w_fp8) {                                   // e4m3 weights: forward convs
-        if (dtype != PMOE_DT_BF16 || a.dilate) return PMOE_ERR_ARG;
-        if (a.in_fp8) {                              // e4m3 activations too: the block-scaled MFMA kernel, or nothing
-            ConvArgs c = a;
-            int mb, pb;
-            size_t sm;
-            return conv_dma_f8_plan(c, dtype, &mb, &sm, &pb) ? conv_dma_f8_launch(a, st) : PMOE_ERR_UNSUPPORTED;
-        }
-        return launch_dtype<bf16, fp8>(a, st, nullptr);
+    ConvPlan p;
+    const int code = conv_select(a, dtype, &p);
+    if (code < 0) return code;
+    for (int i = 0; i < p.n; ++i) {
+        const int rc = launch_one(p.l[i], dtype, st);
+        if (rc) return rc;
     }
-    if (a.shuf_c) {                                  // ConvTranspose2d scatter fused into the store: the 1x1 direct kernel only
-        int wpe, tpe, slabs, mt;
-        size_t sm;
-        return conv_c1x1_plan(a, dtype, &wpe, &tpe, &slabs, &mt, &sm) ? conv_c1x1_launch(a, st) : PMOE_ERR_UNSUPPORTED;
-    }
-    if (a.res_mode == PMOE_RES_INBN) {               // BatchNorm + ReLU of the INPUT on load: conv3x3_respipe_kernel<false, 3> only
-        ResPlan plan;
-        int pb, mpw, mph;
-        size_t sm;
-        if (!a.bias && conv_res_plan(a, dtype, &plan) && conv_res_dma_ok(a, plan, &pb, &mpw, &mph, &sm) && conv_res_pipe_ok(a))
-            return conv_res_launch(a, plan, st);
-        {
-            int wpe, tpe, slabs, mt;                    // 1x1 layers: conv1x1_direct_kernel<MT, true>
-            size_t smx;
-            if (conv_c1x1_plan(a, dtype, &wpe, &tpe, &slabs, &mt, &smx)) return conv_c1x1_launch(a, st);
-        }
-        return PMOE_ERR_UNSUPPORTED;
-    }
-    if (a.res_mode == PMOE_RES_DBN) {                // BatchNorm-backward reductions in the epilogue: the two LDS-DMA kernels only
-        ResPlan plan;
-        int pb, mpw, mph, mb;
-        size_t sm;
-        if (conv_res_plan(a, dtype, &plan) && conv_res_dma_ok(a, plan, &pb, &mpw, &mph, &sm)) return conv_res_launch(a, plan, st);
-        ConvArgs c = a;
-        if (!gemm_skinny_ok(a, dtype) && conv_dma_plan(c, dtype, &mb, &sm, &pb)) return conv_dma_launch(a, st);
-        return PMOE_ERR_UNSUPPORTED;
-    }
-    if (a.dilate && a.ks == 3 && a.pad == 1 && a.kh == 3) return launch_stride2_dgrad(a, dtype, st);
-    if (a.dilate && a.ks == 1 && a.pad == 0 && a.res_mode == PMOE_RES_ADD && a.res == a.out && a.res_ld == a.out_ld &&
-        a.res_coff == a.out_coff && !a.bias && a.act == PMOE_ACT_NONE && a.drop_p == 0.f)
-        return launch_stride2_1x1_inplace(a, dtype, st);
-    if (gemm_skinny_ok(a, dtype)) return gemm_skinny_launch(a, st);
-    {
-        int wpe, tx, tpe, slabs, mt;
-        size_t sm;
-        if (conv_c16_plan(a, dtype, &wpe, &tx, &tpe)) return conv_c16_launch(a, st);
-        if (conv_c1x1_plan(a, dtype, &wpe, &tpe, &slabs, &mt, &sm)) return conv_c1x1_launch(a, st);
-    }
-    ResPlan plan;
-    if (conv_res_plan(a, dtype, &plan)) return conv_res_launch(a, plan, st);
-    {
-        ConvArgs c = a;
-        int mb, pb;
-        size_t sm;
-        if (conv_dma_plan(c, dtype, &mb, &sm, &pb)) return conv_dma_launch(a, st);
-        c = a;
-        if (conv_dma_s2_plan(c, dtype, &mb, &sm, &pb)) return conv_dma_s2_launch(a, st);
-    }
-    if (dtype == PMOE_DT_BF16) return launch_dtype<bf16>(a, st, nullptr);
-    if (dtype == PMOE_DT_F32) return launch_dtype<float>(a, st, nullptr);
-    return PMOE_ERR_ARG;
+    return 0;
 }
 
-// which kernel a descriptor runs on (no launch): 3000 = gemm_skinny_kernel; 1000 + LOG_RB = conv3x3_res_kernel<LOG_RB>; 1207 + 10 bias + 20 mode =
-// conv3x3_respipe_kernel<bias, mode> (1107 | 1117 = conv3x3_resdma_kernel with PMOE_RES_PIPE=0); 1316 = conv3x3_c16_kernel; 1400 + MT = conv1x1_direct_kernel<MT>; 5007 = conv3x3_dma_kernel; 2000 + LOG_RB =
-// conv_igemm_lite_kernel<T, LOG_RB>; LOG_RB*100 + WM*10 + WN = conv_igemm_kernel<T, LOG_RB, WM, WN>; + 4000 = the four
-// parity-class launches of a stride-2 data gradient
+// which kernel a descriptor runs on, without a launch (the codes: include/pmoe_hip.h)
 int conv_igemm_plan(const ConvArgs& a, int dtype) {
-    ConvArgs c = a;
-    int extra = 0;
-    if (a.w_fp8 && a.in_fp8) {
-        ConvArgs d = a;
-        int mb, pb;
-        size_t sm;
-        return conv_dma_f8_plan(d, dtype, &mb, &sm, &pb) ? 8507 : PMOE_ERR_UNSUPPORTED;      // conv3x3_dma_f8_kernel
-    }
-    if (a.w_fp8) {                                   // 8000 + the bf16 code of the same tile
-        int mb = 0, cfg = 0;
-        const int rc = dtype == PMOE_DT_BF16 && !a.dilate ? launch_dtype<bf16, fp8>(c, nullptr, &mb, &cfg) : PMOE_ERR_ARG;
-        return rc ? rc : cfg;
-    }
-    if (a.shuf_c) {
-        int wpe, tpe, slabs, mt;
-        size_t smx;
-        return conv_c1x1_plan(a, dtype, &wpe, &tpe, &slabs, &mt, &smx) ? 1450 + mt + (a.res_mode == PMOE_RES_INBN ? 10 : 0)
-                                                                       : PMOE_ERR_UNSUPPORTED;
-    }
-    if (a.res_mode == PMOE_RES_INBN) {
-        ResPlan plan;
-        int pb, mpw, mph;
-        size_t sm;
-        if (!a.bias && conv_res_plan(a, dtype, &plan) && conv_res_dma_ok(a, plan, &pb, &mpw, &mph, &sm) && conv_res_pipe_ok(a))
-            return 1267;                                 // conv3x3_respipe_kernel<false, 3>
-        int wpe, tpe, slabs, mt;
-        size_t smx;
-        return conv_c1x1_plan(a, dtype, &wpe, &tpe, &slabs, &mt, &smx) ? 1410 + mt : PMOE_ERR_UNSUPPORTED;      // conv1x1_direct_kernel<MT, true>
-    }
-    if (a.res_mode == PMOE_RES_DBN) {
-        ResPlan plan;
-        int pb, mpw, mph, mb;
-        size_t sm;
-        if (conv_res_plan(a, dtype, &plan) && conv_res_dma_ok(a, plan, &pb, &mpw, &mph, &sm))
-            return 1000 + plan.log_rb + (conv_res_pipe_ok(a) ? 240 : 100) + (a.bias ? 10 : 0);
-        if (!gemm_skinny_ok(a, dtype) && conv_dma_plan(c, dtype, &mb, &sm, &pb)) return conv_dma_plan_code(a);
-        return PMOE_ERR_UNSUPPORTED;
-    }
-    if (gemm_skinny_ok(a, dtype)) return 3000;           // gemm_skinny_kernel
-    if (a.dilate && a.ks == 3 && a.pad == 1 && a.kh == 3) {
-        c.dilate = 0; c.stride = 1; c.pad = 0; c.kh = c.kw = 2;
-        c.Ho = a.Ho / 2; c.Wo = a.Wo / 2; c.OH = a.Ho; c.OW = a.Wo; c.out_step = 2;
-        if (c.Ho <= 0 || c.Wo <= 0) return PMOE_ERR_ARG;
-        extra = 4000;
-        {
-            ConvArgs d = c;
-            d.use_tapmap = 1; d.out_offy = d.out_offx = 1;
-            int mb, pb;
-            size_t sm;
-            if (conv_dma_s2cls_plan(d, dtype, &mb, &sm, &pb)) return 4000 + 5207;      // 4 launches of conv3x3s2_dma_kernel<true>
-        }
-    } else {
-        int wpe, tx, tpe, slabs, mt;
-        size_t smx;
-        if (conv_c16_plan(a, dtype, &wpe, &tx, &tpe)) return 1316;             // conv3x3_c16_kernel
-        if (conv_c1x1_plan(a, dtype, &wpe, &tpe, &slabs, &mt, &smx)) return 1400 + mt;   // conv1x1_direct_kernel<MT>
-        ResPlan plan;
-        if (conv_res_plan(a, dtype, &plan)) {
-            int pb, mpw, mph;
-            size_t sm;
-            const int mode = a.res_mode == PMOE_RES_ADD ? 1 : 0;      // (PMOE_RES_DBN returned above)
-            return 1000 + plan.log_rb + (conv_res_dma_ok(a, plan, &pb, &mpw, &mph, &sm) ? (conv_res_pipe_ok(a) ? 200 + 20 * mode : 100) + (a.bias ? 10 : 0) : 0);
-        }
-        ConvArgs d = a;
-        int mbd, pb;
-        size_t sm;
-        if (conv_dma_plan(d, dtype, &mbd, &sm, &pb)) return conv_dma_plan_code(a);       // conv3x3_dma_kernel<MF16, PROD> | conv3x3_dma_stream_kernel<MF16, NT>
-        d = a;
-        if (conv_dma_s2_plan(d, dtype, &mbd, &sm, &pb)) return 5207;       // conv3x3s2_dma_kernel
-    }
-    int mb = 0, cfg = 0;
-    const int rc = dtype == PMOE_DT_BF16 ? launch_dtype<bf16>(c, nullptr, &mb, &cfg)
-                 : dtype == PMOE_DT_F32 ? launch_dtype<float>(c, nullptr, &mb, &cfg) : PMOE_ERR_ARG;
-    return rc ? rc : cfg + extra;
+    ConvPlan p;
+    return conv_select(a, dtype, &p);
 }
 
+// statistics rows of a launch that writes statistics: the selection with `stats` set (some kernels write none and decline such a
+// launch; nothing here dereferences the pointer)
 int conv_igemm_mblocks(const ConvArgs& a, int dtype) {
-    if (a.w_fp8 && a.in_fp8) {
-        ConvArgs d = a;
-        int mb, pb;
-        size_t sm;
-        return conv_dma_f8_plan(d, dtype, &mb, &sm, &pb) ? mb : PMOE_ERR_UNSUPPORTED;
-    }
-    if (a.w_fp8) {
-        int mb = 0;
-        const int rc = dtype == PMOE_DT_BF16 ? launch_dtype<bf16, fp8>(a, nullptr, &mb) : PMOE_ERR_ARG;
-        return rc ? rc : mb;
-    }
-    {
-        int wpe, tx, tpe;
-        // (a launch that asks for statistics never takes the skinny kernel: no gemm_skinny_ok test here, as for the resident kernel)
-        if (conv_c16_plan(a, dtype, &wpe, &tx, &tpe)) return (a.N / a.ipe) * wpe;
-        int slabs, mt;
-        size_t smx;
-        if (conv_c1x1_plan(a, dtype, &wpe, &tpe, &slabs, &mt, &smx)) return (a.N / a.ipe) * wpe;
-    }
-    ResPlan plan;
-    if (conv_res_plan(a, dtype, &plan)) return (a.N / a.ipe) * plan.wgs_per_expert;
-    {
-        ConvArgs d = a;
-        int mbd, pb;
-        size_t sm;
-        // (no gemm_skinny_ok test: this function sizes the STATISTICS rows, and a launch that asks for statistics never takes
-        //  the skinny kernel -- plan and launch must see the same predicate)
-        if (conv_dma_plan(d, dtype, &mbd, &sm, &pb)) return mbd;
-        d = a;
-        if (conv_dma_s2_plan(d, dtype, &mbd, &sm, &pb)) return mbd;
-    }
-    int mb = 0;
-    int rc = (dtype == PMOE_DT_BF16) ? launch_dtype<bf16>(a, nullptr, &mb) : launch_dtype<float>(a, nullptr, &mb);
-    return rc ? rc : mb;
+    static float rows_only;
+    ConvArgs s = a;
+    if (!s.stats) s.stats = &rows_only;
+    ConvPlan p;
+    const int code = conv_select(s, dtype, &p);
+    return code < 0 ? code : p.mblocks;
 }

@@ -19,11 +19,6 @@
 
 template <int LOG_RB> __device__ __forceinline__ int rswz(int x) { return swz_chunk<LOG_RB, 0>(x); }
 
-struct ResPlan {
-    int lTW, lTH, TN, n_groups, tiles_y, tiles_x, tiles_per_expert, wgs_per_expert, log_rb;
-    size_t smem;
-};
-
 // BIAS: per-expert (= per-image for the gate-folded layers) channel bias in the store path.  A separate instantiation,
 // so the register allocation of the common (bias-free) kernel is untouched.
 template <int LOG_RB, bool BIAS = false>
@@ -839,7 +834,7 @@ __global__ void __launch_bounds__(512, 2) conv3x3_respipe_kernel(const ConvArgs 
                     s2[k][q] = __builtin_elementwise_fma(v, d * is, s2[k][q]);
                     pk[mt][q] = pack2(v);
                 } else if (MODE == 1) {
-                    v += unpack2(rprev[mt][k][q]);         // (no statistics in this mode: conv_res_pipe_ok)
+                    v += unpack2(rprev[mt][k][q]);         // (no statistics in this mode: conv_res_plan)
                     pk[mt][q] = pack2(v);
                 } else {
                     pk[mt][q] = w;
@@ -1006,7 +1001,14 @@ __global__ void __launch_bounds__(512, 2) conv3x3_respipe_kernel(const ConvArgs 
 }
 
 // ------------------------------------------------------------------------------------------------
-bool conv_res_plan(const ConvArgs& a, int dtype, ResPlan* plan) {
+// Which of this file's kernels takes the descriptor (l->res_dma, l->res_pipe; conv_select adds the per-mode requirements):
+//  - the all-waves-compute / LDS-DMA variant conv3x3_resdma_kernel (res_dma).  PMOE_RES_DMA=0: A/B switch back to the ping-pong
+//    kernel.  Its prefetch: PMOE_RES_PREFETCH=0 turns it off.
+//  - the software-pipelined variant conv3x3_respipe_kernel (register read-out under the next tile's MFMAs) of what the LDS-DMA
+//    variant takes (res_pipe).  PMOE_RES_PIPE=0: A/B switch back to conv3x3_resdma_kernel.  Its residual / z loads:
+//    PMOE_RES_RZ_LATE=0 puts them back at the start of the tile.
+// (All read per launch.)
+bool conv_res_plan(const ConvArgs& a, int dtype, ConvLaunch* l) {
     static int res_on = -1;       // PMOE_CONV_RES=0: route the <=64-channel layers to the generic kernel (A/B runs)
     if (res_on < 0) { const char* ev = getenv("PMOE_CONV_RES"); res_on = ev ? atoi(ev) : 1; }
     if (!res_on) return false;
@@ -1015,7 +1017,7 @@ bool conv_res_plan(const ConvArgs& a, int dtype, ResPlan* plan) {
     if (a.act != PMOE_ACT_NONE || a.drop_p > 0.f) return false;
     if (a.bias && ((a.res_mode != PMOE_RES_NONE && a.res_mode != PMOE_RES_DBN) || a.Cin != 64)) return false;
     if (a.res_mode != PMOE_RES_NONE && a.res_mode != PMOE_RES_ADD && a.res_mode != PMOE_RES_DBN && a.res_mode != PMOE_RES_INBN) return false;
-    if (a.res_mode == PMOE_RES_DBN && a.Cin != 64) return false;    // (conv3x3_resdma_kernel only: conv_igemm_launch)
+    if (a.res_mode == PMOE_RES_DBN && a.Cin != 64) return false;    // (conv3x3_resdma_kernel only: conv_select)
     if (a.res_mode == PMOE_RES_INBN && (a.Cin != 64 || a.in_shared || !a.bn)) return false;      // (conv3x3_respipe_kernel<false, 3> only)
     if (a.N % a.ipe || a.Ho != a.H || a.Wo != a.W) return false;
     auto p2 = [](int v) { int l = 0; while ((1 << l) < v) ++l; return l; };
@@ -1033,100 +1035,96 @@ bool conv_res_plan(const ConvArgs& a, int dtype, ResPlan* plan) {
     const size_t smem = (size_t)9 * 64 * rb + 2 * region;
     if (smem + (a.bias ? 256 : 0) > 163840) return false;
     const int E = a.N / a.ipe;
-    plan->lTW = lTW; plan->lTH = lTH; plan->TN = TN;
-    plan->n_groups = (a.ipe + TN - 1) / TN;
-    plan->tiles_y = (a.Ho + TH - 1) / TH;
-    plan->tiles_x = (a.Wo + TW - 1) / TW;
-    plan->tiles_per_expert = plan->n_groups * plan->tiles_y * plan->tiles_x;
+    ResPlan& p = l->res;
+    p.lTW = lTW; p.lTH = lTH; p.TN = TN;
+    p.n_groups = (a.ipe + TN - 1) / TN;
+    p.tiles_y = (a.Ho + TH - 1) / TH;
+    p.tiles_x = (a.Wo + TW - 1) / TW;
+    p.tiles_per_expert = p.n_groups * p.tiles_y * p.tiles_x;
     int wpe = 256 / E; if (wpe < 1) wpe = 1;
-    if (wpe > plan->tiles_per_expert) wpe = plan->tiles_per_expert;
-    plan->wgs_per_expert = wpe;
-    plan->log_rb = log_rb;
-    plan->smem = smem;
-    return true;
-}
+    if (wpe > p.tiles_per_expert) wpe = p.tiles_per_expert;
+    p.wgs_per_expert = wpe;
+    p.log_rb = log_rb;
+    p.smem = smem;
+    ConvArgs& c = l->a;
+    c = a;
+    c.lTW = p.lTW; c.lTH = p.lTH; c.TN = p.TN; c.n_groups = p.n_groups; c.tiles_y = p.tiles_y; c.tiles_x = p.tiles_x;
+    l->kind = CONV_RES;
+    l->mblocks = E * wpe;
 
-// does the all-waves-compute / LDS-DMA variant (conv3x3_resdma_kernel) take this plan?  PMOE_RES_DMA=0: A/B switch back to
-// the ping-pong kernel (read per launch)
-bool conv_res_dma_ok(const ConvArgs& a, const ResPlan& p, int* pbuf, int* magic_pw, int* magic_ph, size_t* smem) {
-    if (p.log_rb != 7 || a.in_shared) return false;
-    const char* ev = getenv("PMOE_RES_DMA");
-    if (ev && !atoi(ev)) return false;
+    // the LDS-DMA variant: patch pieces of 1 KiB (a region of at least the 256 x 128-byte staging), the piece decode exact
+    const char* evd = getenv("PMOE_RES_DMA");
     const int PW = (1 << p.lTW) + 2, PH = (1 << p.lTH) + 2;
     const int npiece = (p.TN * PH * PW + 7) / 8;
     int pb = npiece * 1024;
     if (pb < 256 * 128) pb = 256 * 128;
-    const int mpw = 65536 / PW + 1, mph = 65536 / PH + 1;
-    for (int pp = 0; pp < npiece * 8; ++pp)
-        if (((pp * mpw) >> 16) != pp / PW || ((((pp / PW) * mph) >> 16) != (pp / PW) / PH)) return false;
     const size_t sm = (size_t)9 * 64 * 128 + 2 * (size_t)pb + 256 + 1024;     // + bias row + BatchNorm coefficient rows
-    if (npiece > 48 || sm > 163840 || p.lTW < 4 || (long long)a.ipe * a.H * a.W * a.in_ld * 2 >= 0x7ff00000ll) return false;
-    *pbuf = pb; *magic_pw = mpw; *magic_ph = mph; *smem = sm;
-    return true;
-}
-
-// does the software-pipelined variant (conv3x3_respipe_kernel: register read-out under the next tile's MFMAs) take what
-// conv_res_dma_ok accepted?  PMOE_RES_PIPE=0: A/B switch back to conv3x3_resdma_kernel (read per launch)
-bool conv_res_pipe_ok(const ConvArgs& a) {
-    const char* ev = getenv("PMOE_RES_PIPE");
-    if (ev && !atoi(ev)) return false;
-    if (a.ipe > 2047 || (a.res_mode == PMOE_RES_ADD && a.stats)) return false;
+    l->res_dma = p.log_rb == 7 && !a.in_shared && !(evd && !atoi(evd)) && magic_div_exact(npiece * 8, PW, PH, &l->mpw, &l->mph) &&
+                 npiece <= 48 && sm <= 163840 && p.lTW >= 4 && (long long)a.ipe * a.H * a.W * a.in_ld * 2 < 0x7ff00000ll;
+    if (l->res_dma) { l->pbuf = pb; l->smem = sm; }
+    // the pipelined variant: (no statistics with a residual), 11-bit image index, 32-bit offsets of the output and residual
     // (measured and not kept, same box, profiles/r03_kernel_ab.log: the requests for the next patch as straight-line code inside
     //  the MFMA block -- range checks as one guarded subtraction per bound, a wave without a 6th piece requesting its 5th again --
     //  and the residual / z vectors loaded into the registers the read-out has just freed: within 1 % on the stem, 3-5 % slower
     //  on layer1)
-    if ((long long)a.ipe * a.Ho * a.Wo * a.out_ld * 2 >= 0x7ff00000ll) return false;
-    if (a.res_mode != PMOE_RES_NONE && (long long)a.ipe * a.Ho * a.Wo * a.res_ld * 2 >= 0x7ff00000ll) return false;
+    const char* evp = getenv("PMOE_RES_PIPE");
+    l->res_pipe = l->res_dma && !(evp && !atoi(evp)) && a.ipe <= 2047 && !(a.res_mode == PMOE_RES_ADD && a.stats) &&
+                  (long long)a.ipe * a.Ho * a.Wo * a.out_ld * 2 < 0x7ff00000ll &&
+                  (a.res_mode == PMOE_RES_NONE || (long long)a.ipe * a.Ho * a.Wo * a.res_ld * 2 < 0x7ff00000ll);
+    const char* evz = getenv("PMOE_RES_RZ_LATE");
+    l->rz_late = !(evz && !atoi(evz));
+    const char* evf = getenv("PMOE_RES_PREFETCH");
+    if (l->res_dma && !l->res_pipe) c.prefetch = !(evf && !atoi(evf));
+    // 1000 + LOG_RB = conv3x3_res_kernel; + 100 (+ 10 bias) = conv3x3_resdma_kernel; + 200 + 10 bias + 20 mode = conv3x3_respipe_kernel
+    const int mode = a.res_mode == PMOE_RES_INBN ? 3 : a.res_mode == PMOE_RES_DBN ? 2 : a.res_mode == PMOE_RES_ADD ? 1 : 0;
+    l->code = 1000 + p.log_rb + (l->res_dma ? (l->res_pipe ? 200 + 20 * mode : 100) + (a.bias ? 10 : 0) : 0);
     return true;
 }
 
 template <bool BIAS, int MODE>
-static int launch_respipe(const ConvArgs& a, const ResPlan& p, dim3 grid, size_t sm, int pb, int mpw, int mph, hipStream_t st) {
+static int launch_respipe(const ConvLaunch& l, dim3 grid, hipStream_t st) {
+    const ResPlan& p = l.res;
     if constexpr (MODE == 1 || MODE == 2) {              // PMOE_RES_RZ_LATE=0: the side-input loads back at the start of the tile (A/B)
-        const char* ev = getenv("PMOE_RES_RZ_LATE");
-        if (ev && !atoi(ev)) {
+        if (!l.rz_late) {
             HIP_RET((ensure_dyn_lds<conv3x3_respipe_kernel<BIAS, MODE, false>>(163840)));
-            hipLaunchKernelGGL((conv3x3_respipe_kernel<BIAS, MODE, false>), grid, dim3(512), sm, st, a, p.tiles_per_expert, p.wgs_per_expert, pb,
-                               mpw, mph);
+            hipLaunchKernelGGL((conv3x3_respipe_kernel<BIAS, MODE, false>), grid, dim3(512), l.smem, st, l.a, p.tiles_per_expert,
+                               p.wgs_per_expert, l.pbuf, l.mpw, l.mph);
             return (int)hipGetLastError();
         }
     }
     HIP_RET((ensure_dyn_lds<conv3x3_respipe_kernel<BIAS, MODE>>(163840)));
-    hipLaunchKernelGGL((conv3x3_respipe_kernel<BIAS, MODE>), grid, dim3(512), sm, st, a, p.tiles_per_expert, p.wgs_per_expert, pb, mpw, mph);
+    hipLaunchKernelGGL((conv3x3_respipe_kernel<BIAS, MODE>), grid, dim3(512), l.smem, st, l.a, p.tiles_per_expert, p.wgs_per_expert,
+                       l.pbuf, l.mpw, l.mph);
     return (int)hipGetLastError();
 }
 
-int conv_res_launch(ConvArgs a, const ResPlan& p, hipStream_t st) {
-    a.lTW = p.lTW; a.lTH = p.lTH; a.TN = p.TN; a.n_groups = p.n_groups; a.tiles_y = p.tiles_y; a.tiles_x = p.tiles_x;
+int conv_res_launch(const ConvLaunch& l, hipStream_t st) {
+    const ConvArgs& a = l.a;
+    const ResPlan& p = l.res;
     const int E = a.N / a.ipe;
-    const int region = (int)((p.smem - (size_t)9 * 64 * (1 << p.log_rb)) / 2);
     dim3 grid(p.wgs_per_expert, E), block(512);
-    int pb = 0, mpw = 0, mph = 0;
-    size_t sm = 0;
-    if (conv_res_dma_ok(a, p, &pb, &mpw, &mph, &sm)) {
-        if (conv_res_pipe_ok(a)) {
-            const int mode = a.res_mode == PMOE_RES_DBN ? 2 : a.res_mode == PMOE_RES_ADD ? 1 : 0;
-            if (a.res_mode == PMOE_RES_INBN) return launch_respipe<false, 3>(a, p, grid, sm, pb, mpw, mph, st);
-            if (a.bias) return mode == 2 ? launch_respipe<true, 2>(a, p, grid, sm, pb, mpw, mph, st)
-                             : mode == 1 ? launch_respipe<true, 1>(a, p, grid, sm, pb, mpw, mph, st)
-                                         : launch_respipe<true, 0>(a, p, grid, sm, pb, mpw, mph, st);
-            return mode == 2 ? launch_respipe<false, 2>(a, p, grid, sm, pb, mpw, mph, st)
-                 : mode == 1 ? launch_respipe<false, 1>(a, p, grid, sm, pb, mpw, mph, st)
-                             : launch_respipe<false, 0>(a, p, grid, sm, pb, mpw, mph, st);
-        }
-        if (a.res_mode == PMOE_RES_INBN) return PMOE_ERR_UNSUPPORTED;
-        const char* evp = getenv("PMOE_RES_PREFETCH");
-        a.prefetch = !(evp && !atoi(evp));
+    if (l.res_pipe) {
+        const int mode = a.res_mode == PMOE_RES_DBN ? 2 : a.res_mode == PMOE_RES_ADD ? 1 : 0;
+        if (a.res_mode == PMOE_RES_INBN) return launch_respipe<false, 3>(l, grid, st);
+        if (a.bias) return mode == 2 ? launch_respipe<true, 2>(l, grid, st)
+                         : mode == 1 ? launch_respipe<true, 1>(l, grid, st)
+                                     : launch_respipe<true, 0>(l, grid, st);
+        return mode == 2 ? launch_respipe<false, 2>(l, grid, st)
+             : mode == 1 ? launch_respipe<false, 1>(l, grid, st)
+                         : launch_respipe<false, 0>(l, grid, st);
+    }
+    if (a.res_mode == PMOE_RES_INBN) return PMOE_ERR_UNSUPPORTED;
+    if (l.res_dma) {
         if (a.bias) {
             HIP_RET((ensure_dyn_lds<conv3x3_resdma_kernel<true>>(163840)));
-            hipLaunchKernelGGL(conv3x3_resdma_kernel<true>, grid, block, sm, st, a, p.tiles_per_expert, p.wgs_per_expert, pb, mpw, mph);
+            hipLaunchKernelGGL(conv3x3_resdma_kernel<true>, grid, block, l.smem, st, a, p.tiles_per_expert, p.wgs_per_expert, l.pbuf, l.mpw, l.mph);
         } else {
             HIP_RET((ensure_dyn_lds<conv3x3_resdma_kernel<false>>(163840)));
-            hipLaunchKernelGGL(conv3x3_resdma_kernel<false>, grid, block, sm, st, a, p.tiles_per_expert, p.wgs_per_expert, pb, mpw, mph);
+            hipLaunchKernelGGL(conv3x3_resdma_kernel<false>, grid, block, l.smem, st, a, p.tiles_per_expert, p.wgs_per_expert, l.pbuf, l.mpw, l.mph);
         }
         return (int)hipGetLastError();
     }
-    if (a.res_mode == PMOE_RES_INBN) return PMOE_ERR_UNSUPPORTED;
+    const int region = (int)((p.smem - (size_t)9 * 64 * (1 << p.log_rb)) / 2);
     if (p.log_rb == 7 && a.bias) {
         HIP_RET((ensure_dyn_lds<conv3x3_res_kernel<7, true>>(163840)));
         hipLaunchKernelGGL((conv3x3_res_kernel<7, true>), grid, block, p.smem + 256, st, a, p.tiles_per_expert,

@@ -1190,10 +1190,8 @@ template <typename T> static int wgrad_dtype(WgradArgs a, hipStream_t st, bool p
             const int dma_on = evd ? atoi(evd) : 1;
             const long long xbytes = (long long)a.ipe * a.H * a.W * a.x_ld * 2, dybytes = (long long)a.ipe * a.Ho * a.Wo * a.dy_ld * 2;
             const int npiece = (NPIX + 7) / 8;
-            const int mpw = 65536 / PW + 1, mph = 65536 / PH + 1;
-            bool exact = true;
-            for (int pp = 0; pp < npiece * 8 && exact; ++pp)
-                exact = ((pp * mpw) >> 16) == pp / PW && ((((pp / PW) * mph) >> 16) == (pp / PW) / PH);
+            int mpw, mph;
+            const bool exact = magic_div_exact(npiece * 8, PW, PH, &mpw, &mph);
             if (dma_on && a.ks == 3 && a.stride == 1 && BMP == 256 && lTW >= 2 && npiece <= 48 && exact &&
                 xbytes < 0x7ff00000ll && dybytes < 0x7ff00000ll && 2 * ((size_t)BMP * 128 + (size_t)npiece * 1024) <= 160 * 1024) {
                 const char* evn = getenv("PMOE_WGRAD_NARROW");           // A/B: 0 = the 2 x 2 x 2 wave layout for every layer

@@ -170,22 +170,29 @@ __global__ void __launch_bounds__(NW * 64) gemm_skinny_kernel(const ConvArgs a) 
 // bf16, no fused statistics, dense output lattice, and FEW output rows per expert: the expert MLP layers (1x1 "images") and
 // their data gradients, and the 3x3 / 1x1 convolutions of tiny feature maps at tiny batches (closed-loop inference, B = 1:
 // layer3 / layer4 are 14x14 / 7x7 -- on the generic kernel a serial chain of 36..72 tap-chunks on a dozen workgroups)
-bool gemm_skinny_ok(const ConvArgs& a, int dtype) {
-    static int on = -1, maxrows = 0;   // PMOE_GEMM_SKINNY=0: back to the generic implicit-GEMM kernel (A/B measurements)
+// PMOE_SKINNY_NW8: reduction length (taps * Cin) from which 8 waves split K (default 0 = never: measured no faster)
+bool gemm_skinny_plan(const ConvArgs& a, int dtype, ConvLaunch* l) {
+    static int on = -1, maxrows = 0, nw8 = 0;   // PMOE_GEMM_SKINNY=0: back to the generic implicit-GEMM kernel (A/B measurements)
     if (on < 0) {
         const char* ev = getenv("PMOE_GEMM_SKINNY");
         on = ev ? atoi(ev) : 1;
         const char* mr = getenv("PMOE_SKINNY_MAXROWS");
         maxrows = mr ? atoi(mr) : 3200;
+        const char* nw = getenv("PMOE_SKINNY_NW8");
+        nw8 = nw ? atoi(nw) : 0;
     }
     if (!on || dtype != PMOE_DT_BF16 || a.stats || a.dilate || a.use_tapmap || a.out_step != 1) return false;
     if ((a.ks != 1 && a.ks != 3) || a.kh != a.ks || a.kw != a.ks || (a.stride != 1 && a.stride != 2)) return false;
     const bool mlp = a.H == 1 && a.W == 1 && a.Ho == 1 && a.Wo == 1 && a.ks == 1;
     if (!mlp && (long long)a.ipe * a.Ho * a.Wo > maxrows) return false;
     if (a.Ho != (a.H + 2 * a.pad - a.ks) / a.stride + 1 || a.Wo != (a.W + 2 * a.pad - a.ks) / a.stride + 1) return false;
-    return a.Cin > 0 && a.Cin % 16 == 0 && a.CoutP % BN == 0 && a.Cout % VE == 0 && a.ipe > 0 && a.N % a.ipe == 0 &&
-           a.in_ld % VE == 0 && a.in_coff % VE == 0 && a.out_ld % VE == 0 && a.out_coff % VE == 0 &&
-           (!a.res_mode || (a.res && a.res_ld % VE == 0 && a.res_coff % VE == 0));
+    if (!(a.Cin > 0 && a.Cin % 16 == 0 && a.CoutP % BN == 0 && a.Cout % VE == 0 && a.ipe > 0 && a.N % a.ipe == 0 &&
+          a.in_ld % VE == 0 && a.in_coff % VE == 0 && a.out_ld % VE == 0 && a.out_coff % VE == 0 &&
+          (!a.res_mode || (a.res && a.res_ld % VE == 0 && a.res_coff % VE == 0))))
+        return false;
+    l->kind = CONV_SKINNY; l->code = 3000; l->a = a; l->mblocks = 0;      // (no statistics: a.stats is null)
+    l->nw = nw8 > 0 && a.ks * a.ks * a.Cin >= nw8 ? 8 : 4;
+    return true;
 }
 
 template <int NW> static int skinny_launch_nw(const ConvArgs& a, const dim3& grid, hipStream_t st) {
@@ -195,12 +202,10 @@ template <int NW> static int skinny_launch_nw(const ConvArgs& a, const dim3& gri
     return (int)hipGetLastError();
 }
 
-int gemm_skinny_launch(const ConvArgs& a, hipStream_t st) {
+int gemm_skinny_launch(const ConvLaunch& l, hipStream_t st) {
+    const ConvArgs& a = l.a;
     const dim3 grid(a.CoutP / BN, (a.ipe * a.Ho * a.Wo + BM - 1) / BM, a.N / a.ipe);
-    static int nw8 = -1;            // PMOE_SKINNY_NW8: reduction length (taps * Cin) from which 8 waves split K (default 0 = never: measured no faster)
-    if (nw8 < 0) { const char* ev = getenv("PMOE_SKINNY_NW8"); nw8 = ev ? atoi(ev) : 0; }
-    if (nw8 > 0 && a.ks * a.ks * a.Cin >= nw8) return skinny_launch_nw<8>(a, grid, st);
-    return skinny_launch_nw<4>(a, grid, st);
+    return l.nw == 8 ? skinny_launch_nw<8>(a, grid, st) : skinny_launch_nw<4>(a, grid, st);
 }
 
 

@@ -24,7 +24,7 @@ struct ConvArgs {
     int act, res_mode;
     float drop_p;
     unsigned long long seed;
-    // filled by the launcher
+    // filled by the planner (conv_select)
     int lTW, lTH, TN, n_groups, tiles_y, tiles_x;
     // tap window + output lattice (defaults: kh = kw = ks, identity tap order, dense output).  A stride-2 data gradient
     // is issued as 4 launches, one per output parity class (py,px): a kh x kw = (1+py) x (1+px) stride-1 correlation over
@@ -33,8 +33,8 @@ struct ConvArgs {
     int out_step, out_offy, out_offx, OH, OW;
     const float* bn;       // PMOE_RES_DBN: [4][N / bn_ipe][Cout] f32 (mean, invstd, scale, beta)
     int bn_ipe;
-    int stagger;           // launcher: waves 4-7 of the 8-wave tile run one k-substep behind their SIMD partners
-    int prefetch;          // launcher: 2 patch buffers, the next channel chunk's halo patch is fetched under the MFMAs
+    int stagger;           // planner: waves 4-7 of the 8-wave tile run one k-substep behind their SIMD partners
+    int prefetch;          // planner: 2 patch buffers, the next channel chunk's halo patch is fetched under the MFMAs
     int shuf_c;            // > 0 (1x1 direct kernel, round 4): ConvTranspose2d(k2,s2) scatter fused -- out is [N][2Ho][2Wo][out_ld], output
                            // channel q*shuf_c + c (q = 2 dy + dx) goes to pixel (2 oy + dy, 2 ox + dx), channel out_coff + c
 };
@@ -58,29 +58,68 @@ struct WgradArgs {
     int slice_fastest;     // launcher: grid order of round 1 (A/B switch)
 };
 
-// grouped skinny GEMM for the expert MLP layers (gemm_skinny.hip)
-bool gemm_skinny_ok(const ConvArgs& a, int dtype);
-int gemm_skinny_launch(const ConvArgs& a, hipStream_t st);
+// The piece decode of the LDS-DMA kernels divides by multiply-and-shift: patch pixel pp of PH rows x PW pixels per image lies in
+// row (pp * mpw) >> 16, that row in image (row * mph) >> 16.  Sets mpw / mph; true if both are exact for every pp < n.
+inline bool magic_div_exact(int n, int PW, int PH, int* mpw, int* mph) {
+    *mpw = 65536 / PW + 1; *mph = 65536 / PH + 1;
+    for (int pp = 0; pp < n; ++pp)
+        if (((pp * *mpw) >> 16) != pp / PW || (((pp / PW) * *mph) >> 16) != (pp / PW) / PH) return false;
+    return true;
+}
 
-// LDS-DMA 3x3 kernel for the >= 128-channel stride-1 layers (conv_dma.hip)
-bool conv_dma_plan(ConvArgs& a, int dtype, int* mblocks, size_t* smem, int* pbuf);
-int conv_dma_launch(ConvArgs a, hipStream_t st);
-bool conv_dma_uses_mf16(const ConvArgs& a);
-bool conv_dma_uses_producer(const ConvArgs& a);
-bool conv_dma_uses_stream(const ConvArgs& a);
-bool conv_dma_is_narrow(const ConvArgs& a);
-int conv_dma_plan_code(const ConvArgs& a);
-// ... on the block-scaled fp8 matrix instruction (e4m3 weights and activations)
-bool conv_dma_f8_plan(ConvArgs& a, int dtype, int* mblocks, size_t* smem, int* pbuf);
-int conv_dma_f8_launch(ConvArgs a, hipStream_t st);      // which instantiation: <true> = v_mfma_f32_16x16x32_bf16
-// ... and its stride-2 forward sibling (parity planes gathered by the DMA's per-lane source addresses)
-bool conv_dma_s2_plan(ConvArgs& a, int dtype, int* mblocks, size_t* smem, int* pbuf);
-int conv_dma_s2_launch(ConvArgs a, hipStream_t st);
-// ... and one parity class of a stride-2 3x3 data gradient on the same kernel (ConvArgs with the class fields set)
-bool conv_dma_s2cls_plan(ConvArgs& a, int dtype, int* mblocks, size_t* smem, int* pbuf);
-int conv_dma_s2cls_launch(ConvArgs a, hipStream_t st);
+// resident-weight ping-pong kernel and its LDS-DMA successors for the <=64-channel 3x3 stride-1 layers (conv_res.hip)
+struct ResPlan {
+    int lTW, lTH, TN, n_groups, tiles_y, tiles_x, tiles_per_expert, wgs_per_expert, log_rb;
+    size_t smem;
+};
 
-struct ResPlan;
+// the kernel families a conv launch can run on
+enum ConvKind { CONV_SKINNY = 1, CONV_C16, CONV_C1X1, CONV_RES, CONV_DMA, CONV_DMA_S2, CONV_DMA_S2CLS, CONV_DMA_F8, CONV_TILE };
+
+// One kernel launch as conv_select decided it: the family, the descriptor the kernel receives (tile fields filled in) and what
+// that family's launcher needs to pick the instantiation and its grid.  Filled by the family's planner, read by its launcher.
+struct ConvLaunch {
+    int kind;              // ConvKind
+    int code;              // pmoe_conv2d_plan code of this launch (include/pmoe_hip.h)
+    int mblocks;           // m-blocks = statistics rows this launch writes
+    ConvArgs a;
+    size_t smem;           // dynamic LDS bytes of the launch (RES: of the LDS-DMA variants; the ping-pong kernel's are res.smem)
+    int pbuf, mpw, mph;    // LDS-DMA (+ RES with res_dma): patch buffer bytes, magic numbers of the piece decode
+    int mf16, stream, producer, narrow;        // DMA: conv3x3_dma_kernel<MF16, PROD> | conv3x3_dma_stream_kernel<MF16, NARROW>
+    ResPlan res;           // RES
+    int res_dma, res_pipe, rz_late;            // RES: conv3x3_resdma_kernel, conv3x3_respipe_kernel<BIAS, MODE, RZ_LATE>
+    int wpe, tpe, tiles_x, slabs, mt;           // C16 / C1X1: workgroups and tiles per expert, (C16) tiles per row, (C1X1) slabs, MT
+    int log_rb, wm, wn, lite;                   // TILE: conv_igemm_kernel<T, LOG_RB, WM, WN> | conv_igemm_lite_kernel<T, LOG_RB>
+    int nw;                // SKINNY: gemm_skinny_kernel<NW>
+};
+
+// what conv_select decided for a descriptor: up to four launches (a stride-2 data gradient: one per output parity class)
+struct ConvPlan {
+    int code;              // pmoe_conv2d_plan code, or a PMOE_ERR_* (< 0): nothing runs
+    int mblocks;           // statistics rows (pmoe_conv2d_stat_rows)
+    int n;
+    ConvLaunch l[4];
+};
+int conv_select(const ConvArgs& a, int dtype, ConvPlan* p);
+
+// the family planners (false / no launch: the family does not serve this descriptor) and launchers
+bool gemm_skinny_plan(const ConvArgs& a, int dtype, ConvLaunch* l);          // gemm_skinny.hip: the expert MLP layers
+int gemm_skinny_launch(const ConvLaunch& l, hipStream_t st);
+bool conv_c16_plan(const ConvArgs& a, int dtype, ConvLaunch* l);             // conv_c16.hip: the 16-channel stem conv
+int conv_c16_launch(const ConvLaunch& l, hipStream_t st);
+bool conv_c1x1_plan(const ConvArgs& a, int dtype, ConvLaunch* l);            // conv_c1x1.hip: 1x1 direct kernel
+int conv_c1x1_launch(const ConvLaunch& l, hipStream_t st);
+bool conv_res_plan(const ConvArgs& a, int dtype, ConvLaunch* l);             // conv_res.hip (l->res_dma / res_pipe: which kernel)
+int conv_res_launch(const ConvLaunch& l, hipStream_t st);
+// LDS-DMA 3x3 kernels (conv_dma.hip): stride 1 (>= 128 output channels, or the 64-channel streaming tile), the block-scaled fp8
+// one (e4m3 weights and activations), the stride-2 forward one, and one parity class of a stride-2 data gradient on the same
+// kernel (ConvArgs with the class fields set).  One launcher serves all four.
+bool conv_dma_plan(const ConvArgs& a, int dtype, ConvLaunch* l);
+bool conv_dma_f8_plan(const ConvArgs& a, int dtype, ConvLaunch* l);
+bool conv_dma_s2_plan(const ConvArgs& a, int dtype, ConvLaunch* l);
+bool conv_dma_s2cls_plan(const ConvArgs& a, int dtype, ConvLaunch* l);
+int conv_dma_launch(const ConvLaunch& l, hipStream_t st);
+
 int conv_igemm_launch(const ConvArgs& a, int dtype, hipStream_t st);
 int conv_igemm_mblocks(const ConvArgs& a, int dtype);
 int conv_igemm_plan(const ConvArgs& a, int dtype);

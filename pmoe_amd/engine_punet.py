@@ -217,14 +217,13 @@ class PUNetEngine(ExpertGroupEngine):
         if (self.fuse_in_bn and not self.taping and self.training and self.dtype == torch.bfloat16 and self.fuse_conv_stats
                 and self.debug_acts is None and c2.w_f8 is None and c1.cout_st == c2.cinp == bn1.C):
             n, h, w, _ = x.t.shape
+            key = (n, h, w, self.dtype)
             ok = blk.get("_inbn")
-            if ok is None or ok[0] != (n, h, w):
-                probe = torch.empty(4, self.E, bn1.C, dtype=torch.float32, device=self.dev)
-                zz = torch.empty(n, h, w, c1.cout_st, dtype=self.dtype, device=self.dev)
-                oo = torch.empty(n, h, w, c2.cout_st, dtype=self.dtype, device=self.dev)
-                code = ops.conv2d(zz, c2.w_fwd, oo, cin=c2.cinp, cout=c2.cout_st, coutp=c2.coutp, ipe=self.B, ks=c2.ks,
-                                  stride=c2.stride, pad=c2.pad, res_mode=hip.RES_INBN, bn_coef=probe, plan_only=True)
-                ok = blk["_inbn"] = ((n, h, w), code == 1267)
+            if ok is None or ok[0] != key:
+                ho, wo = ops.conv_out_size(h, c2.ks, c2.stride, c2.pad), ops.conv_out_size(w, c2.ks, c2.stride, c2.pad)
+                code = ops.conv2d_plan(n, h, w, ho, wo, c2.cinp, c2.cout_st, c2.coutp, self.B, c2.ks, c2.stride, c2.pad, self.dtype,
+                                       in_ld=c1.cout_st, out_ld=c2.cout_st, res_mode=hip.RES_INBN)
+                ok = blk["_inbn"] = (key, code == 1267)
             if ok[1]:
                 z1, st1 = self._conv_stats(x, c1)
                 self._bn_coeffs(bn1, self.B * h * w, st1, st1.shape[0] // self.E, z1)

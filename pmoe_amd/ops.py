@@ -26,6 +26,43 @@ def _nhwc(t, name):
     return t.shape
 
 
+def _conv_desc(n, h, w_, ho, wo, cin, cout, coutp, ipe, ks, stride, pad, dtype, *, dilate=False, in_shared=False, in_ld=0,
+               in_coff=0, out_ld=0, out_coff=0, res_mode=hip.RES_NONE, res_ld=0, res_coff=0, act=hip.ACT_NONE, drop_p=0.0, seed=0,
+               w_fp8=False, in_fp8=False, in_scale=1.0, bn_ipe=0, shuffle2_c=0):
+    """The pmoe_conv_desc of a launch from its shapes alone (``dtype``: PMOE_DT_*); the pointers are left null for the caller.
+    in_ld / out_ld 0 = dense rows."""
+    d = ConvDesc()
+    d.n, d.h, d.w_, d.cin = n, h, w_, cin
+    d.ho, d.wo, d.cout, d.coutp = ho, wo, cout, coutp
+    d.in_ld, d.in_coff, d.out_ld, d.out_coff = in_ld, in_coff, out_ld, out_coff
+    d.res_ld, d.res_coff = res_ld, res_coff
+    d.ipe, d.in_shared = ipe, int(in_shared)
+    d.ks, d.stride, d.pad, d.dilate = ks, stride, pad, int(dilate)
+    d.act, d.res_mode = act, res_mode
+    d.drop_p, d.seed, d.dtype = float(drop_p), int(seed), dtype
+    d.shuffle_c = int(shuffle2_c)
+    if w_fp8:
+        d.w_fp8, d.in_scale, d.in_fp8 = 1, float(in_scale), int(in_fp8)
+    if res_mode in (hip.RES_DBN, hip.RES_INBN):
+        d.bn_ipe = int(bn_ipe or ipe)
+    return d
+
+
+def _planning_desc(n, h, w_, ho, wo, cin, cout, coutp, ipe, ks, stride, pad, dtype, bias=False, stats=False, **kw):
+    """descriptor of a planning call: the pointers the launch would pass (only their presence matters to the kernel choice) are
+    set to a placeholder that nothing dereferences"""
+    d = _conv_desc(n, h, w_, ho, wo, cin, cout, coutp, ipe, ks, stride, pad, hip._TORCH_DT[dtype], **kw)
+    one = C.c_void_p(1)
+    if d.res_mode not in (hip.RES_NONE, hip.RES_INBN):
+        d.res = one
+    if d.res_mode in (hip.RES_DBN, hip.RES_INBN):
+        d.bn_coef = one
+    if d.w_fp8:
+        d.out_scale = one
+    d.bias, d.stats = (one if bias else None), (one if stats else None)
+    return d
+
+
 def conv2d(x, w_packed, out, *, cin, cout, coutp, ipe, ks, stride, pad, dilate=False, in_shared=False,
            in_coff=0, out_coff=0, res=None, res_coff=0, res_mode=hip.RES_NONE, bias=None, act=hip.ACT_NONE,
            drop_p=0.0, seed=0, stats=None, plan_only=False, out_scale=None, in_scale=1.0, bn_coef=None, bn_ipe=0, shuffle2_c=0):
@@ -46,24 +83,18 @@ def conv2d(x, w_packed, out, *, cin, cout, coutp, ipe, ks, stride, pad, dilate=F
         raise ValueError("conv2d: x, w and out must share one dtype")
     if w_fp8 and (out_scale is None or out.dtype != torch.bfloat16):
         raise ValueError("conv2d: e4m3 weights need bf16 activations and the per-channel out_scale of the pack")
-    d = ConvDesc()
-    d.in_, d.w, d.out = ptr(x, "x"), ptr(w_packed, "w"), ptr(out, "out")
-    d.res = ptr(res, "res", out.dtype) if res is not None else None
-    d.bias = ptr(bias, "bias", torch.float32) if bias is not None else None
-    d.stats = ptr(stats, "stats", torch.float32) if stats is not None else None
-    d.n, d.h, d.w_, d.cin = n, h, w_, cin
-    d.ho, d.wo, d.cout, d.coutp = ho, wo, cout, coutp
-    d.in_ld, d.in_coff, d.out_ld, d.out_coff = ldx, in_coff, ldo, out_coff
-    d.res_ld = res.shape[-1] if res is not None else 0
-    d.res_coff = res_coff
-    d.ipe, d.in_shared = ipe, int(in_shared)
-    d.ks, d.stride, d.pad, d.dilate = ks, stride, pad, int(dilate)
-    d.act, d.res_mode = act, res_mode if (res is not None or res_mode == hip.RES_INBN) else hip.RES_NONE
-    d.drop_p, d.seed, d.dtype = float(drop_p), int(seed), dt(out)
-    d.shuffle_c = int(shuffle2_c)
+    in_, w, o = ptr(x, "x"), ptr(w_packed, "w"), ptr(out, "out")
+    res_p = ptr(res, "res", out.dtype) if res is not None else None
+    bias_p = ptr(bias, "bias", torch.float32) if bias is not None else None
+    stats_p = ptr(stats, "stats", torch.float32) if stats is not None else None
+    d = _conv_desc(n, h, w_, ho, wo, cin, cout, coutp, ipe, ks, stride, pad, dt(out), dilate=dilate, in_shared=in_shared,
+                   in_ld=ldx, in_coff=in_coff, out_ld=ldo, out_coff=out_coff,
+                   res_mode=res_mode if (res is not None or res_mode == hip.RES_INBN) else hip.RES_NONE,
+                   res_ld=res.shape[-1] if res is not None else 0, res_coff=res_coff, act=act, drop_p=drop_p, seed=seed,
+                   w_fp8=w_fp8, in_fp8=in_fp8, in_scale=in_scale, bn_ipe=bn_ipe, shuffle2_c=shuffle2_c)
+    d.in_, d.w, d.out, d.res, d.bias, d.stats = in_, w, o, res_p, bias_p, stats_p
     if w_fp8:
-        d.w_fp8, d.in_scale, d.out_scale = 1, float(in_scale), ptr(out_scale, "out_scale", torch.float32)
-        d.in_fp8 = int(in_fp8)
+        d.out_scale = ptr(out_scale, "out_scale", torch.float32)
     if d.res_mode == hip.RES_DBN:
         # data gradient into relu(BatchNorm(z)): res = z, bn_coef = [4][n / bn_ipe][cout] (mean, invstd, gamma*invstd, beta);
         # the launch masks the gradient and leaves the BatchNorm backward's channel reductions in `stats`
@@ -72,13 +103,13 @@ def conv2d(x, w_packed, out, *, cin, cout, coutp, ipe, ks, stride, pad, dilate=F
             raise ValueError(f"conv2d: RES_DBN needs bn_coef [4, {nset}, {cout}] f32")
         if stats is None and not plan_only:
             raise ValueError("conv2d: RES_DBN writes the BatchNorm-backward reductions to `stats`")
-        d.bn_coef, d.bn_ipe = ptr(bn_coef, "bn_coef", torch.float32), int(bn_ipe or ipe)
+        d.bn_coef = ptr(bn_coef, "bn_coef", torch.float32)
     if d.res_mode == hip.RES_INBN:
         # the INPUT is the pre-activation z of a BatchNorm + ReLU: bn_coef = [4][n / bn_ipe][cin], applied on load
         nset = n // (bn_ipe or ipe)
         if res is not None or bn_coef is None or bn_coef.dtype != torch.float32 or tuple(bn_coef.shape) != (4, nset, cin):
             raise ValueError(f"conv2d: RES_INBN takes no `res` and needs bn_coef [4, {nset}, {cin}] f32")
-        d.bn_coef, d.bn_ipe = ptr(bn_coef, "bn_coef", torch.float32), int(bn_ipe or ipe)
+        d.bn_coef = ptr(bn_coef, "bn_coef", torch.float32)
     if in_shared and nin != ipe:
         raise ValueError("conv2d: shared input must hold exactly ipe images")
     if not in_shared and nin != n:
@@ -99,17 +130,20 @@ def conv2d(x, w_packed, out, *, cin, cout, coutp, ipe, ks, stride, pad, dilate=F
     return out
 
 
+def conv2d_plan(n, h, w_, ho, wo, cin, cout, coutp, ipe, ks, stride, pad, dtype, *, bias=False, stats=False, **kw):
+    """pmoe_conv2d_plan from shapes, without tensors: the kernel-instantiation code (include/pmoe_hip.h) a conv2d launch with these
+    shapes would run, or a negative PMOE_ERR_* if none would.  ``bias`` / ``stats``: the launch passes that tensor; the other
+    keywords are conv2d's (in_ld / out_ld: row lengths of its tensors, 0 = dense; shuffle2_c: the 1x1 map's own ho / wo)."""
+    return load().pmoe_conv2d_plan(C.byref(_planning_desc(n, h, w_, ho, wo, cin, cout, coutp, ipe, ks, stride, pad, dtype,
+                                                          bias=bias, stats=stats, **kw)))
+
+
 def conv2d_stat_rows(n, h, w_, ho, wo, cin, cout, coutp, ipe, ks, stride, pad, dtype, w_fp8=False, in_ld=0, out_ld=0,
                      in_shared=False, in_fp8=False):
     """Partial-sum rows the launch will write.  in_ld / out_ld: row lengths (elements) of the tensors the launch will get --
     the kernel choice can depend on them (0 = dense)."""
-    d = ConvDesc()
-    d.w_fp8, d.in_scale, d.in_fp8 = int(w_fp8), 1.0, int(in_fp8)
-    if in_fp8:
-        d.out_scale = C.c_void_p(1)          # (planning only: the fp8 kernel's plan asks for a scale pointer, nothing dereferences it)
-    d.in_ld, d.out_ld, d.in_shared = in_ld, out_ld, int(in_shared)
-    d.n, d.h, d.w_, d.cin, d.ho, d.wo, d.cout, d.coutp = n, h, w_, cin, ho, wo, cout, coutp
-    d.ipe, d.ks, d.stride, d.pad, d.dtype = ipe, ks, stride, pad, hip._TORCH_DT[dtype]
+    d = _planning_desc(n, h, w_, ho, wo, cin, cout, coutp, ipe, ks, stride, pad, dtype, w_fp8=w_fp8, in_fp8=in_fp8,
+                       in_ld=in_ld, out_ld=out_ld, in_shared=in_shared)
     rows = load().pmoe_conv2d_stat_rows(C.byref(d))
     if rows < 0:
         check(rows, "pmoe_conv2d_stat_rows")

@@ -119,6 +119,85 @@ def test_planning_calls_see_the_same_descriptor_as_the_launch():
     assert load().pmoe_conv2d_plan(C.byref(wide)) == 1005
 
 
+def _plan_and_rows(d):
+    import ctypes as C
+    from pmoe_amd.hip import load
+    return load().pmoe_conv2d_plan(C.byref(d)), load().pmoe_conv2d_stat_rows(C.byref(d))
+
+
+def test_shuffle_c_runs_on_the_1x1_direct_kernel_or_nothing():
+    """pmoe_conv_desc.shuffle_c: the scatter exists in conv1x1_direct_kernel only -- with e4m3 operands, a dilated source or a 3x3
+    filter nothing serves the descriptor (the plan once reported the e4m3 tile, which would have ignored the scatter), and a
+    launch that writes statistics never takes it."""
+    from pmoe_amd import hip
+    from pmoe_amd.hip import ConvDesc
+
+    def desc(ks=1, w_fp8=0, in_fp8=0, dilate=0):
+        d = ConvDesc()
+        c = 32
+        d.n, d.h, d.w_, d.cin, d.ho, d.wo, d.cout, d.coutp = 4, 64, 64, 64, 64, 64, 4 * c, 128
+        d.in_ld, d.out_ld, d.out_coff, d.ipe, d.ks, d.stride, d.pad, d.dilate = 64, 2 * c, c, 4, ks, 1, ks // 2, dilate
+        d.shuffle_c, d.w_fp8, d.in_fp8, d.in_scale, d.out_scale = c, w_fp8, in_fp8, 1.0, 1
+        return d
+    plan, rows = _plan_and_rows(desc())
+    assert plan in (1452, 1454) and rows == hip.ERR_UNSUPPORTED
+    for d in (desc(w_fp8=1), desc(w_fp8=1, in_fp8=1), desc(dilate=1), desc(ks=3)):
+        assert _plan_and_rows(d) == (hip.ERR_UNSUPPORTED, hip.ERR_UNSUPPORTED)
+
+
+def test_stride2_1x1_inplace_data_gradient_plans_its_single_launch():
+    """The stride-2 1x1 data gradient accumulated in place (res == out, PMOE_RES_ADD) runs ONE class-(0,0) launch of the generic
+    tile over the even-even pixels: the plan and the statistics rows are that launch's -- those of a stride-1 1x1 conv over the
+    half-size map -- not a zero-dilated tile that never runs, and not the 4000 + code of four class launches."""
+    from pmoe_amd.hip import ConvDesc
+
+    def desc(cin, cout, H, dtype, dilate, inplace=True, E=4, B=64):
+        d = ConvDesc()
+        Ho = 2 * H if dilate else H
+        d.n, d.h, d.w_, d.cin, d.ho, d.wo, d.cout, d.coutp = E * B, H, H, cin, Ho, Ho, cout, (cout + 63) // 64 * 64
+        d.in_ld, d.out_ld, d.ipe, d.ks, d.stride, d.pad, d.dilate, d.dtype = cin, cout, B, 1, 1, 0, int(dilate), dtype
+        if dilate:
+            d.out, d.res = 0x1000, (0x1000 if inplace else 0x2000)     # in place: the residual IS the output
+            d.res_ld, d.res_mode = cout, 1
+        return d
+    for cin, cout, H in ((128, 64, 32), (256, 128, 16), (512, 256, 8), (256, 256, 4)):
+        plan, rows = _plan_and_rows(desc(cin, cout, H, 1, True))
+        assert plan < 4000 and (plan, rows) == _plan_and_rows(desc(cin, cout, H, 1, False))
+    # 4 x 4 maps: the zero-dilated 8 x 8 form would have taken the 8-wave LITE tile; the launch runs the 4-wave 128 x 128 one
+    assert _plan_and_rows(desc(256, 256, 4, 0, True)) == (722, 32)
+    assert _plan_and_rows(desc(256, 256, 4, 0, True, inplace=False)) == (2007, 64)     # (a separate residual: that form runs)
+
+
+def test_stat_rows_are_those_of_the_kernel_that_runs(monkeypatch):
+    """pmoe_conv2d_stat_rows goes through the same selection as the launch: the BatchNorm modes (PMOE_RES_DBN, PMOE_RES_INBN) get the
+    rows of the kernel that serves them, and PMOE_ERR_UNSUPPORTED where none does -- a row count of another kernel would size a
+    buffer that the launch never writes, or write past it."""
+    from pmoe_amd import hip
+    from pmoe_amd.hip import ConvDesc
+
+    def desc(cin, cout, H, ks=3, stride=1, res_mode=0, E=4, B=64):
+        d = ConvDesc()
+        Ho = (H + 2 * (ks // 2) - ks) // stride + 1
+        d.n, d.h, d.w_, d.cin, d.ho, d.wo, d.cout, d.coutp = E * B, H, H, cin, Ho, Ho, cout, (cout + 63) // 64 * 64
+        d.in_ld, d.out_ld, d.ipe, d.ks, d.stride, d.pad = cin, cout, B, ks, stride, ks // 2
+        d.res_mode, d.stats, d.bn_coef = res_mode, 1, 1
+        if res_mode == hip.RES_DBN:
+            d.res, d.res_ld = 1, cout
+        return d
+    plain = _plan_and_rows(desc(64, 64, 128))
+    assert plain[0] == 1207
+    assert _plan_and_rows(desc(64, 64, 128, res_mode=hip.RES_INBN)) == (1267, plain[1])      # the same resident-filter tiles
+    assert _plan_and_rows(desc(64, 64, 128, res_mode=hip.RES_DBN)) == (1247, plain[1])
+    assert _plan_and_rows(desc(128, 128, 64, res_mode=hip.RES_DBN))[0] in (5007, 5017)
+    assert _plan_and_rows(desc(128, 128, 64, res_mode=hip.RES_DBN))[1] == _plan_and_rows(desc(128, 128, 64))[1]
+    # nothing serves these: no rows either
+    for d in (desc(128, 128, 64, res_mode=hip.RES_INBN), desc(128, 128, 64, stride=2, res_mode=hip.RES_DBN)):
+        assert _plan_and_rows(d) == (hip.ERR_UNSUPPORTED, hip.ERR_UNSUPPORTED)
+    monkeypatch.setenv("PMOE_RES_DMA", "0")           # (read per launch) the resident kernels without LDS-DMA serve neither mode
+    for mode in (hip.RES_INBN, hip.RES_DBN):
+        assert _plan_and_rows(desc(64, 64, 128, res_mode=mode)) == (hip.ERR_UNSUPPORTED, hip.ERR_UNSUPPORTED)
+
+
 def test_wgrad_plan_reports_the_kernel_instantiation():
     """pmoe_conv2d_wgrad_plan: the LDS-DMA weight-gradient kernel for the dense 3x3 bf16 layers, its 2 x 4 wave layout for layers
     with <= 32 input channels (the stem's first convolution), the register-staged kernel for the strided ones."""
