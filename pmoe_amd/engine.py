@@ -74,7 +74,14 @@ class Var:
 
 
 class GroupedConv:
-    """One conv / linear layer of all experts: packed operands + launch helpers."""
+    """One conv / linear layer of all experts: packed operands + launch helpers.
+
+    A layer kind declares how gradients reach its parameters.  A plain layer says nothing: its slots ("w", "b") have the
+    kernels' own [E, cout, cin * taps] / [E, cout] layout and the weight-gradient launch writes them.  A kind whose
+    parameters are laid out differently implements ``scatter_grads(eng, full_w, full_b)``: _wgrad_block hands it the dense
+    [E, cout, cin] weight gradient and, where the route produced one, the [E, cout] bias gradient."""
+    scatter_grads = None
+    route_bias = True            # the weight-gradient route also produces the bias gradient (mlp_wgrad, or column sums of dy)
 
     def __init__(self, eng, name, weights, biases, cin, cout, ks, stride, pad):
         self.eng, self.name = eng, name
@@ -111,8 +118,8 @@ class GroupedConv:
         if self.biases is not None:
             self.bias_packed = torch.empty(E, self.coutp, dtype=F32, device=dev)
 
-    def pack(self, wtab, btab):
-        E = self.eng.E
+    def pack(self):
+        E, wtab = self.eng.E, self.eng._tab("w", self)
         if self.w_f8 is not None:
             # e4m3 forward operand + per-channel scales; the data-gradient operand holds the exactly dequantised weights
             ops.pack_conv_weights_fp8(wtab, self.w_f8, self.w_dg, self.wscale, self.oscale, self.eng.fp8_in_scale, E,
@@ -121,12 +128,62 @@ class GroupedConv:
         ops.pack_conv_weights(wtab, self.w_fwd, self.w_dg, E, self.cout, self.cin, self.ks, self.coutp, self.cinp,
                               self.dg_rows, self.dg_red, self.w_fwd.dtype)
         if self.biases is not None:
-            ops.pack_bias(btab, self.bias_packed, E, self.cout, self.coutp)
+            ops.pack_bias(self.eng._tab("b", self), self.bias_packed, E, self.cout, self.coutp)
 
     @property
     def trainable(self):
         return any(p.requires_grad for p in self.weights) or (
             self.biases is not None and any(p.requires_grad for p in self.biases))
+
+
+class HeadPart:
+    """rows [r0, r0 + rows) of a FusedHead: one Linear of every expert, with its own parameter slots (w_part, b_part)"""
+
+    def __init__(self, name, mods, r0):
+        self.name, self.weights, self.biases = name, [m.weight for m in mods], [m.bias for m in mods]
+        self.r0, self.rows = r0, mods[0].out_features
+
+
+class FusedHead(GroupedConv):
+    """action_pred and alpha read the same input: one GEMM whose output rows are action_pred's, then alpha's (4 + 1 per expert;
+    4K + K with the shared trunk's K components)"""
+
+    def __init__(self, eng, ex):
+        self.parts = [HeadPart("action_pred", [e.action_pred for e in ex], 0)]
+        self.parts.append(HeadPart("alpha", [e.alpha for e in ex], self.parts[0].rows))
+        super().__init__(eng, "head", [w for p in self.parts for w in p.weights], [b for p in self.parts for b in p.biases],
+                         ex[0].action_pred.in_features, sum(p.rows for p in self.parts), 1, 1, 0)
+
+    def alloc(self, dtype, dev):
+        super().alloc(dtype, dev)
+        E = self.eng.E      # the pack kernel writes whole [coutp] panels: each part is packed into scratch, its rows copied
+        self._scratch = (torch.empty(E, 64, 1, self.cinp, dtype=dtype, device=dev),
+                         torch.empty(E, self.dg_rows, 1, self.dg_red, dtype=dtype, device=dev),
+                         torch.empty(E, 64, dtype=F32, device=dev))
+
+    def pack(self):
+        """two packs into row windows of the fused operands (zeroed once: the padding rows stay zero)"""
+        eng, E = self.eng, self.eng.E
+        sf, sd, sb = self._scratch
+        for p in self.parts:
+            rows = slice(p.r0, p.r0 + p.rows)
+            ops.pack_conv_weights(eng._tab("w_part", p), sf, sd, E, p.rows, self.cin, 1, 64, self.cinp, self.dg_rows,
+                                  self.dg_red, self.w_fwd.dtype)
+            if p.r0 == 0:
+                self.w_fwd.zero_()
+                self.w_dg.zero_()
+                self.bias_packed.zero_()
+            self.w_fwd[:, rows] = sf[:, :p.rows]
+            self.w_dg[:, :, :, rows] = sd[:, :, :, :p.rows]
+            ops.pack_bias(eng._tab("b_part", p), sb, E, p.rows, 64)
+            self.bias_packed[:, rows] = sb[:, :p.rows]
+
+    def scatter_grads(self, eng, full_w, full_b):
+        """the row split: each part's rows of the dense gradients into its own slots"""
+        for kind, full in (("w_part", full_w), ("b_part", full_b)):
+            for p in self.parts:
+                rows = full[:, p.r0:p.r0 + p.rows]
+                eng._grad_slot(kind, p).view(rows.shape).copy_(rows)
 
 
 class GroupedBN:
@@ -211,6 +268,7 @@ class ExpertGroupEngine:
     def _collect(self):
         ex = self.experts
         self.params = []              # ordered list of (kind, layer, [E params]) in FORWARD order
+        self.all_convs = []           # every GroupedConv that packs from self.params, in the same order
 
         def conv(name, mods, ks=None):
             m0 = mods[0]
@@ -225,6 +283,7 @@ class ExpertGroupEngine:
             self.params.append(("w", layer, layer.weights))
             if layer.biases is not None:
                 self.params.append(("b", layer, layer.biases))
+            self.all_convs.append(layer)
             return layer
 
         def bn(name, mods):
@@ -258,7 +317,6 @@ class ExpertGroupEngine:
         del self._mk
         if self.conv1 is not None:
             self.conv1.need_dgrad = self._stem_needs_dgrad()
-        self.all_convs = [p[1] for p in self.params if p[0] == "w"]
         self.all_bns = [p[1] for p in self.params if p[0] == "gamma"]
         self.flat_params = [p for _, _, plist in self.params for p in plist]
 
@@ -313,28 +371,18 @@ class ExpertGroupEngine:
             self.head = conv("action_pred", [e.action_pred for e in ex])
         else:
             # action_pred (4 rows) and alpha (1 row) read the same input: one GEMM with 5 output rows
-            self.head = self._fused_head(ex)
-
-    def _fused_head(self, ex):
-        class _Cat:  # weights of action_pred (rows 0..3) and alpha (row 4) as one 5-row layer
-            pass
-        k = self.K if self.shared else 1      # shared trunk: rows 0..4K-1 action_pred, rows 4K..5K-1 alpha
-        layer = GroupedConv(self, "head", None, None, ex[0].action_pred.in_features, 5 * k, 1, 1, 0)
-        layer.parts = [([e.action_pred.weight for e in ex], [e.action_pred.bias for e in ex], 4 * k),
-                       ([e.alpha.weight for e in ex], [e.alpha.bias for e in ex], k)]
-        layer.weights = layer.parts[0][0] + layer.parts[1][0]
-        layer.biases = layer.parts[0][1] + layer.parts[1][1]
-        for (ws, bs, _), nm in zip(layer.parts, ("action_pred", "alpha")):
-            self.params.append(("w_part", (layer, nm), ws))
-            self.params.append(("b_part", (layer, nm), bs))
-        return layer
+            self.head = FusedHead(self, ex)
+            for part in self.head.parts:
+                self.params.append(("w_part", part, part.weights))
+                self.params.append(("b_part", part, part.biases))
+            self.all_convs.append(self.head)
 
     # ------------------------------------------------------------------ buffers
     def _ensure_built(self, dev, dtype):
         key = (str(dev), dtype, self.fp8, self.fp8_min_cin)
         if self._built_for == key:
             return
-        for layer in self.all_convs + ([self.head] if getattr(self.head, "parts", None) else []):
+        for layer in self.all_convs:
             if getattr(layer, "_alloc_key", None) != (dtype, dev, bool(layer.fp8 and dtype == torch.bfloat16)):
                 layer.alloc(dtype, dev)
         self._ptr_key = None
@@ -351,10 +399,10 @@ class ExpertGroupEngine:
             tensors.extend(lst)
 
         for kind, layer, plist in self.params:
-            add((kind, id(layer) if not isinstance(layer, tuple) else (id(layer[0]), layer[1])), plist)
+            add(self._key(kind, layer), plist)
         for bnl in self.all_bns:
-            add(("rm", id(bnl)), [m.running_mean for m in bnl.mods])
-            add(("rv", id(bnl)), [m.running_var for m in bnl.mods])
+            add(self._key("rm", bnl), [m.running_mean for m in bnl.mods])
+            add(self._key("rv", bnl), [m.running_var for m in bnl.mods])
         for key, lst in self._extra_tables():
             add(key, lst)
         ptrs = tuple(t.data_ptr() for t in tensors)
@@ -373,8 +421,7 @@ class ExpertGroupEngine:
         return []
 
     def _tab(self, kind, layer):
-        k = (kind, id(layer) if not isinstance(layer, tuple) else (id(layer[0]), layer[1]))
-        s, n = self._ptr_index[k]
+        s, n = self._ptr_index[self._key(kind, layer)]
         return self._ptr_tab[s:s + n]
 
     def _pack_all(self):
@@ -382,31 +429,8 @@ class ExpertGroupEngine:
         if ver == self._packed_version:
             return
         for layer in self.all_convs:
-            layer.pack(self._tab("w", layer), self._tab("b", layer) if layer.biases is not None else None)
-        if getattr(self.head, "parts", None):
-            h = self.head
-            E = self.E
-            # two packs into row windows of the fused 5-row head: rows 0..3 action_pred, row 4 alpha
-            for (ws, bs, rows), nm, r0 in ((h.parts[0], "action_pred", 0), (h.parts[1], "alpha", h.parts[0][2])):
-                self._pack_head_part(h, nm, rows, r0)
+            layer.pack()
         self._packed_version = ver
-
-    def _pack_head_part(self, h, nm, rows, r0):
-        # The pack kernel writes a whole [coutp] panel, so pack each part into scratch and copy its rows.
-        E = self.E
-        scratch_f = torch.empty(E, 64, 1, h.cinp, dtype=h.w_fwd.dtype, device=h.w_fwd.device)
-        scratch_d = torch.empty(E, h.dg_rows, 1, h.dg_red, dtype=h.w_fwd.dtype, device=h.w_fwd.device)
-        ops.pack_conv_weights(self._tab("w_part", (h, nm)), scratch_f, scratch_d, E, rows, h.cin, 1, 64, h.cinp,
-                              h.dg_rows, h.dg_red, h.w_fwd.dtype)
-        if r0 == 0:
-            h.w_fwd.zero_()
-            h.w_dg.zero_()
-            h.bias_packed.zero_()
-        h.w_fwd[:, r0:r0 + rows] = scratch_f[:, :rows]
-        h.w_dg[:, :, :, r0:r0 + rows] = scratch_d[:, :, :, :rows]
-        sb = torch.empty(E, 64, dtype=F32, device=h.w_fwd.device)
-        ops.pack_bias(self._tab("b_part", (h, nm)), sb, E, rows, 64)
-        h.bias_packed[:, r0:r0 + rows] = sb[:, :rows]
 
     # ------------------------------------------------------------------ primitive ops (forward + tape)
     def _new(self, n, h, w, c, dtype=None):
@@ -417,12 +441,7 @@ class ExpertGroupEngine:
         """``in_bn``: x is the pre-activation z of a BatchNorm + ReLU and in_bn its [4, E, C] coefficient block -- the launch applies
         them on load (PMOE_RES_INBN: untaped forward launches; the caller has asked pmoe_conv2d_plan)."""
         H, W = x.t.shape[1], x.t.shape[2]
-        Ho = ops.conv_out_size(H, layer.ks, layer.stride, layer.pad)
-        Wo = ops.conv_out_size(W, layer.ks, layer.stride, layer.pad)
-        if out is None:
-            o = Var(self._new(self.N, Ho, Wo, layer.cout_st), layer.cout_st, 0)
-        else:
-            o = out.window(out_coff, layer.cout_st)
+        Ho, Wo, o = self._conv_out(x, layer, out, out_coff)
         stats = None
         f8 = layer.w_f8 is not None
         if f8 and (bias is not False or act != hip.ACT_NONE):
@@ -458,6 +477,14 @@ class ExpertGroupEngine:
             self.tape.append(lambda: self._conv_bwd(x, layer, o, in_shared, flop))
         return (o, stats) if want_stats else o
 
+    def _conv_out(self, x, layer, out=None, out_coff=0):
+        """(Ho, Wo, o) of ``layer`` applied to x: o is a fresh activation, or the channel window of ``out`` at out_coff"""
+        Ho = ops.conv_out_size(x.t.shape[1], layer.ks, layer.stride, layer.pad)
+        Wo = ops.conv_out_size(x.t.shape[2], layer.ks, layer.stride, layer.pad)
+        if out is None:
+            return Ho, Wo, Var(self._new(self.N, Ho, Wo, layer.cout_st), layer.cout_st, 0)
+        return Ho, Wo, out.window(out_coff, layer.cout_st)
+
     def _conv_bwd(self, x, layer, o, in_shared, flop=0.0):
         """dy is the gradient w.r.t. the layer's PRE-activation output (the consumer's dgrad epilogue
         already applied act'); emits weight/bias gradients and, if needed, the input gradient."""
@@ -484,62 +511,47 @@ class ExpertGroupEngine:
             st = self.__dict__["_side"] = torch.cuda.Stream(device=self.dev)
         return st
 
-    def _wgrad_block(self, x, layer, o, dy, in_shared, flop):
-        E = self.E
-        if (self.mlp_wgrad_fused and layer.ks == 1 and self.dtype == torch.bfloat16 and dy.shape[1] == 1 and dy.shape[2] == 1
-                and x.t.shape[1] == 1 and x.t.shape[2] == 1 and not hasattr(layer, "store_grads")):
-            # round 4: a Linear layer of the expert MLPs -- weight AND bias gradient in one launch, written in the parameters'
-            # own layout (csrc/gemm_skinny.hip mlp_wgrad_kernel); the fused 5-row head goes through a dense temporary
-            parts = getattr(layer, "parts", None)
-            ops.set_meta(flop=flop, name=layer.name)
-            if parts is None:
-                ops.mlp_wgrad(x.t, dy, self._grad_slot("w", layer), self._grad_slot("b", layer) if layer.biases is not None else None,
-                              cin=layer.cinp, cout=layer.cout_st, cin_real=layer.cin, cout_real=layer.cout, ipe=self.B,
-                              x_shared=in_shared, x_coff=x.coff, dy_coff=o.coff)
-                return
-            full = torch.empty(E, layer.cout, layer.cin, dtype=F32, device=self.dev)
-            fb = torch.empty(E, layer.cout, dtype=F32, device=self.dev)
-            ops.mlp_wgrad(x.t, dy, full, fb, cin=layer.cinp, cout=layer.cout_st, cin_real=layer.cin, cout_real=layer.cout,
-                          ipe=self.B, x_shared=in_shared, x_coff=x.coff, dy_coff=o.coff)
-            ra = parts[0][2]
-            self._grad_slot("w_part", (layer, "action_pred")).view(E, ra, layer.cin).copy_(full[:, 0:ra])
-            self._grad_slot("w_part", (layer, "alpha")).view(E, layer.cout - ra, layer.cin).copy_(full[:, ra:])
-            self._grad_slot("b_part", (layer, "action_pred")).view(E, ra).copy_(fb[:, 0:ra])
-            self._grad_slot("b_part", (layer, "alpha")).view(E, layer.cout - ra).copy_(fb[:, ra:])
-            return
+    def _wgrad_tile(self, layer):
+        """(coutp, cinp) of ``layer``'s weight-gradient workspace: both channel counts rounded up to the kernels' tile width
+        (conv_wgrad.hip rejects a launch whose CinP is not round_up(Cin, CKW))"""
         ckw = 64 if self.dtype == torch.bfloat16 else 32
-        cpw = (layer.cinp + ckw - 1) // ckw * ckw
-        cow = (layer.cout_st + ckw - 1) // ckw * ckw
-        ws = self._wgrad_ws(E * layer.taps * cow * cpw)      # overwritten by the launch (no atomics, nothing to zero)
-        parts = getattr(layer, "parts", None)
-        # plain layers: the launch's own fold writes the parameter-layout gradient (no separate unpack launch)
-        direct = parts is None and not hasattr(layer, "store_grads")
-        ops.set_meta(flop=flop, name=layer.name)
-        d = ops.conv2d_wgrad(x.t, dy, ws, cin=layer.cinp, cout=layer.cout_st, cinp=cpw, coutp=cow, ipe=self.B,
-                             ks=layer.ks, stride=layer.stride, pad=layer.pad, x_shared=in_shared, x_coff=x.coff,
-                             dy_coff=o.coff, grads=self._grad_slot("w", layer) if direct else None, grads_cout=layer.cout,
-                             grads_cin=layer.cin, defer_fold=direct)
-        if direct:
-            ops.conv2d_wgrad_fold(d)
-        if hasattr(layer, "store_grads"):       # derived layouts (ConvTranspose2d as a 4*Cout-row 1x1 layer, engine_punet)
-            layer.store_grads(self, ws, cow, cpw)
-            return
-        if parts is None:
-            pass                                           # written by the launch (direct)
+        return (layer.cout_st + ckw - 1) // ckw * ckw, (layer.cinp + ckw - 1) // ckw * ckw
+
+    def _wgrad_block(self, x, layer, o, dy, in_shared, flop):
+        """the only weight-gradient route of a taped layer: pick the kernel, pick the destination (a plain layer's own slots,
+        else dense temporaries), then let the layer scatter the dense gradient into its parameters' layout"""
+        E = self.E
+        plain = layer.scatter_grads is None
+        want_b = layer.biases is not None and layer.route_bias
+        gw = self._grad_slot("w", layer) if plain else torch.empty(E, layer.cout, layer.cin, dtype=F32, device=self.dev)
+        if (self.mlp_wgrad_fused and layer.ks == 1 and self.dtype == torch.bfloat16 and dy.shape[1] == 1 and dy.shape[2] == 1
+                and x.t.shape[1] == 1 and x.t.shape[2] == 1 and layer.route_bias):
+            # round 4: a Linear layer of the expert MLPs -- weight AND bias gradient in one launch, written in the parameters'
+            # own layout (csrc/gemm_skinny.hip mlp_wgrad_kernel)
+            gb = None
+            if want_b:
+                gb = self._grad_slot("b", layer) if plain else torch.empty(E, layer.cout, dtype=F32, device=self.dev)
+            ops.set_meta(flop=flop, name=layer.name)
+            ops.mlp_wgrad(x.t, dy, gw, gb, cin=layer.cinp, cout=layer.cout_st, cin_real=layer.cin, cout_real=layer.cout,
+                          ipe=self.B, x_shared=in_shared, x_coff=x.coff, dy_coff=o.coff)
         else:
-            full = torch.empty(E, layer.cout, layer.cin, dtype=F32, device=self.dev)
-            ops.unpack_conv_wgrad(ws, full, E, layer.cout, layer.cin, 1, cow, cpw)
-            ra = parts[0][2]
-            self._grad_slot("w_part", (layer, "action_pred")).view(E, ra, layer.cin).copy_(full[:, 0:ra])
-            self._grad_slot("w_part", (layer, "alpha")).view(E, layer.cout - ra, layer.cin).copy_(full[:, ra:])
-        if layer.biases is not None:
-            sums = self._colsum(dy, self.B * dy.shape[1] * dy.shape[2], layer.cout_st, o.coff)[:, :layer.cout]
-            if parts is None:
-                self._grad_slot("b", layer).view(E, layer.cout).copy_(sums)
+            cow, cpw = self._wgrad_tile(layer)
+            ws = self._wgrad_ws(E * layer.taps * cow * cpw)      # overwritten by the launch (no atomics, nothing to zero)
+            ops.set_meta(flop=flop, name=layer.name)
+            # plain layers: the launch's own fold writes the parameter-layout gradient (no separate unpack launch)
+            d = ops.conv2d_wgrad(x.t, dy, ws, cin=layer.cinp, cout=layer.cout_st, cinp=cpw, coutp=cow, ipe=self.B,
+                                 ks=layer.ks, stride=layer.stride, pad=layer.pad, x_shared=in_shared, x_coff=x.coff,
+                                 dy_coff=o.coff, grads=gw if plain else None, grads_cout=layer.cout,
+                                 grads_cin=layer.cin, defer_fold=plain)
+            if plain:
+                ops.conv2d_wgrad_fold(d)
             else:
-                ra = parts[0][2]
-                self._grad_slot("b_part", (layer, "action_pred")).view(E, ra).copy_(sums[:, 0:ra])
-                self._grad_slot("b_part", (layer, "alpha")).view(E, layer.cout - ra).copy_(sums[:, ra:])
+                ops.unpack_conv_wgrad(ws, gw, E, layer.cout, layer.cin, 1, cow, cpw)
+            gb = self._colsum(dy, self.B * dy.shape[1] * dy.shape[2], layer.cout_st, o.coff)[:, :layer.cout] if want_b else None
+            if plain and want_b:
+                self._grad_slot("b", layer).view(E, layer.cout).copy_(gb)
+        if not plain:
+            layer.scatter_grads(self, gw, gb)
 
     def _colsum(self, t, rpe, C, coff=0):
         """per-expert column sums [E,C] (f32) of the channel window [coff, coff+C) of ``t``: partial rows over enough
@@ -700,11 +712,7 @@ class ExpertGroupEngine:
             if part.shape[2] != C_:
                 raise RuntimeError("BatchNorm reductions from the data-gradient epilogue: channel count mismatch")
             part, nparts = self._fold_parts(part.view(E, nparts, 2 * C_), nparts, 2 * C_, cap=2048)
-            c1, c2 = (torch.empty(E, C_, dtype=F32, device=self.dev) for _ in range(2))
-            dgamma, dbeta, store = self._bn_grad_views(layer)
-            ops.bn_bwd_finalize(part, nparts, rpe, dgamma, dbeta, c1, c2, E, C_)
-            if store is not None:
-                store()
+            c1, c2 = self._bn_bwd_finalize(layer, part, nparts, rpe, train)
             if z.needs_grad:
                 if z.grad is not None:
                     raise RuntimeError("BN input consumed twice")
@@ -727,14 +735,7 @@ class ExpertGroupEngine:
         ops.set_meta(name=layer.name, bytes=nb * ((3 if ysrc is not None else 2) + (gm is not None)))
         ops.bn_bwd_reduce(dy, ysrc, z.t, mean, invstd, scale, shift, rpe, E, C_, relu, part, nparts, gmask=gm)
         part, nparts = self._fold_parts(part, nparts, 2 * C_, cap=2048)
-        c1, c2 = (torch.empty(E, C_, dtype=F32, device=self.dev) for _ in range(2))
-        dgamma, dbeta, store = self._bn_grad_views(layer)
-        ops.bn_bwd_finalize(part, nparts, rpe, dgamma, dbeta, c1, c2, E, C_)
-        if store is not None:
-            store()
-        if not train:          # eval-mode BN is an affine map: no batch-statistics terms
-            c1.zero_()
-            c2.zero_()
+        c1, c2 = self._bn_bwd_finalize(layer, part, nparts, rpe, train)
         dz = torch.empty_like(z.t) if z.needs_grad else None
         if gm is not None:
             if dz is not None:
@@ -759,6 +760,20 @@ class ExpertGroupEngine:
             if res.grad is not None:
                 raise RuntimeError("residual gradient slot already filled")
             res.set_grad(gm)
+
+    def _bn_bwd_finalize(self, layer, part, nparts, rpe, train, out=None):
+        """folded reductions of a BatchNorm backward -> d gamma / d beta in their slots and the two per-channel terms (c1, c2)
+        [E,C] of dz, written to ``out`` if the caller has already handed those tensors to a kernel"""
+        E, C_ = self.E, layer.C
+        c1, c2 = out or (torch.empty(E, C_, dtype=F32, device=self.dev) for _ in range(2))
+        dgamma, dbeta, store = self._bn_grad_views(layer)
+        ops.bn_bwd_finalize(part, nparts, rpe, dgamma, dbeta, c1, c2, E, C_)
+        if store is not None:
+            store()
+        if not train:          # eval-mode BN is an affine map: no batch-statistics terms
+            c1.zero_()
+            c2.zero_()
+        return c1, c2
 
     def _bn_grad_views(self, layer):
         """[E,C] views for d gamma / d beta of ``layer`` (+ an optional store step; hook for channel-padded BatchNorms)."""
@@ -808,25 +823,15 @@ class ExpertGroupEngine:
                     p4, np4 = self._fold_parts(p4, np4, 4 * C_)
                     o1, o2 = (torch.empty(E, 1, 2, C_, dtype=F32, device=self.dev) for _ in range(2))
                     ops.stem_tail_combine(p4, np4, part_x, npx, consts, rpe, o1, o2, E, C_)
-                    ops.bn_bwd_finalize(o1, 1, rpe, self._grad_slot("gamma", self.bn1).view(E, C_),
-                                        self._grad_slot("beta", self.bn1).view(E, C_), c11, c21, E, C_)
-                    ops.bn_bwd_finalize(o2, 1, rpe, self._grad_slot("gamma", self.bn_c2).view(E, C_),
-                                        self._grad_slot("beta", self.bn_c2).view(E, C_), c12, c22, E, C_)
+                    self._bn_bwd_finalize(self.bn1, o1, 1, rpe, train, out=(c11, c21))
+                    self._bn_bwd_finalize(self.bn_c2, o2, 1, rpe, train, out=(c12, c22))
                 else:
                     ops.stem_tail_bwd(1, z2.t, dp, am, None, consts, p1, nparts, E, self.B)
                     pf, nf = self._fold_parts(p1, nparts, 2 * C_)
-                    ops.bn_bwd_finalize(pf, nf, rpe, self._grad_slot("gamma", self.bn1).view(E, C_),
-                                        self._grad_slot("beta", self.bn1).view(E, C_), c11, c21, E, C_)
-                    if not train:
-                        c11.zero_()
-                        c21.zero_()
+                    self._bn_bwd_finalize(self.bn1, pf, nf, rpe, train, out=(c11, c21))
                     ops.stem_tail_bwd(2, z2.t, dp, am, None, consts, p1, nparts, E, self.B)
                     pf, nf = self._fold_parts(p1, nparts, 2 * C_)
-                    ops.bn_bwd_finalize(pf, nf, rpe, self._grad_slot("gamma", self.bn_c2).view(E, C_),
-                                        self._grad_slot("beta", self.bn_c2).view(E, C_), c12, c22, E, C_)
-                    if not train:
-                        c12.zero_()
-                        c22.zero_()
+                    self._bn_bwd_finalize(self.bn_c2, pf, nf, rpe, train, out=(c12, c22))
                 if z2.needs_grad:
                     dz = torch.empty_like(z2.t)
                     ops.stem_tail_bwd(3, z2.t, dp, am, dz, consts, p1, nparts, E, self.B)
@@ -900,7 +905,7 @@ class ExpertGroupEngine:
                     -> ECA weight gradient and dgap  ->  dx = conv^T(dy, W_n) + dgap/HW  (the per-image bias of that conv)"""
         nx, h, w, c = x.t.shape
         hw = h * w
-        N, B_, E = self.N, self.B, self.E
+        N, B_ = self.N, self.B
         if getattr(x, "gap_part", None) is not None:          # left by the BatchNorm pass that wrote x (_bn, want_gap)
             part, nparts = x.gap_part
         else:
@@ -914,9 +919,7 @@ class ExpertGroupEngine:
         wd = torch.empty(N, layer.dg_rows, layer.taps, layer.dg_red, dtype=self.dtype, device=self.dev) if x.needs_grad else None
         ops.pack_conv_weights_gated(self._tab("w", layer), gate, wf, wd, N, B_, layer.cout, layer.cin, layer.ks, layer.coutp,
                                     layer.cinp, layer.dg_rows, layer.dg_red, self.dtype)
-        Ho = ops.conv_out_size(h, layer.ks, layer.stride, layer.pad)
-        Wo = ops.conv_out_size(w, layer.ks, layer.stride, layer.pad)
-        o = Var(self._new(N, Ho, Wo, layer.cout_st), layer.cout_st, 0)
+        Ho, Wo, o = self._conv_out(x, layer)
         stats = None
         if self.training and self.fuse_conv_stats and self.dtype == torch.bfloat16:
             rows = ops.conv2d_stat_rows(N, h, w, Ho, Wo, layer.cinp, layer.cout_st, layer.coutp, 1, layer.ks, layer.stride,
@@ -932,23 +935,8 @@ class ExpertGroupEngine:
                 dy = o.grad
                 if dy is None:
                     return
-                ckw = 64 if self.dtype == torch.bfloat16 else 32
-                cpw = (layer.cinp + ckw - 1) // ckw * ckw
-                cow = (layer.cout_st + ckw - 1) // ckw * ckw
-                G = self._wgrad_ws(N * layer.taps * cow * cpw, main=True)
                 ops.set_meta(flop=flop, name=layer.name)
-                ops.conv2d_wgrad(x.t, dy, G, cin=layer.cinp, cout=layer.cout_st, cinp=cpw, coutp=cow, ipe=B_, ks=layer.ks,
-                                 stride=layer.stride, pad=layer.pad, per_image=True)
-                ds = torch.empty(N, c, dtype=F32, device=self.dev)
-                dw = self._grad_slot("w", layer) if layer.trainable else torch.empty(
-                    E * layer.cout * layer.cin * layer.taps, dtype=F32, device=self.dev)
-                ops.eca_stem_fold(G, gate, self._tab("w", layer), dw, ds, N, B_, layer.cout, layer.cin, layer.ks, cow, cpw)
-                dgap = torch.empty(N, c, dtype=F32, device=self.dev) if x.needs_grad else None
-                if ecal.trainable or x.needs_grad:
-                    dwe = self._grad_slot("eca", ecal).view(E, ecal.k) if ecal.trainable else torch.empty(
-                        E, ecal.k, dtype=F32, device=self.dev)
-                    ops.eca_bwd_small(ds, 1, gate, gapmean, self._tab("eca", ecal), ecal.k, dgap, dwe, N, B_, c, ecal.creal,
-                                      dgap_scale=1.0 / hw)
+                dgap = self._filter_grads(x.t, dy, layer, ecal, gate, gapmean, want_dgap=x.needs_grad, dgap_scale=1.0 / hw)
                 if x.needs_grad:
                     if x.grad is not None or x.act != hip.ACT_NONE:
                         raise RuntimeError("gate-folded conv: its input must have this conv as the only consumer")
@@ -1034,7 +1022,8 @@ class ExpertGroupEngine:
 
     @staticmethod
     def _key(kind, layer):
-        return (kind, id(layer) if not isinstance(layer, tuple) else (id(layer[0]), layer[1]))
+        """slot / pointer-table key of one parameter group: ``layer`` is whatever object stands in self.params for it"""
+        return (kind, id(layer))
 
     def _layout_arena(self):
         """Gradient arena in BACKWARD order (heads first, stem last): contiguous all-reduce buckets."""
@@ -1060,7 +1049,7 @@ class ExpertGroupEngine:
         tail = None
         for key in self._order:
             layer = next((l for k, l, _ in self.params if self._key(k, l) == key), None)
-            name = getattr(layer[0] if isinstance(layer, tuple) else layer, "name", "")
+            name = getattr(layer, "name", "")
             if name.startswith("layer1.") or name.startswith("stem.") or name in ("bn1", "eca1", "eca2"):
                 tail = self._slots[key][0]
                 break
@@ -1191,10 +1180,7 @@ class ExpertGroupEngine:
                                          conv.coutp, conv.cinp, self.dtype)
             cache = conv.__dict__["_bn_fold"] = (key, wf, bf)
         _, wf, bf = cache
-        H, W = x.t.shape[1], x.t.shape[2]
-        Ho = ops.conv_out_size(H, conv.ks, conv.stride, conv.pad)
-        Wo = ops.conv_out_size(W, conv.ks, conv.stride, conv.pad)
-        o = Var(self._new(self.N, Ho, Wo, conv.cout_st), conv.cout_st, 0) if out is None else out.window(0, conv.cout_st)
+        Ho, Wo, o = self._conv_out(x, conv, out)
         ops.set_meta(flop=2.0 * self.N * Ho * Wo * conv.cout * conv.cin * conv.taps, name=conv.name + "+bn")
         ops.conv2d(x.t, wf, o.t, cin=conv.cinp, cout=conv.cout_st, coutp=conv.coutp, ipe=self.B, ks=conv.ks,
                    stride=conv.stride, pad=conv.pad, in_shared=(x.t.shape[0] != self.N), in_coff=x.coff, out_coff=o.coff,
@@ -1279,27 +1265,36 @@ class ExpertGroupEngine:
         dy = z1.grad
         if dy is None:
             return
-        E, layer, ecal = self.E, self.conv1, self.eca1
-        ckw = 64 if self.dtype == torch.bfloat16 else 32
-        cpw = (layer.cinp + ckw - 1) // ckw * ckw
-        cow = (layer.cout_st + ckw - 1) // ckw * ckw
-        G = self._wgrad_ws(self.N * layer.taps * cow * cpw, main=True)
+        layer = self.conv1
         ops.set_meta(flop=2.0 * self.N * dy.shape[1] * dy.shape[2] * layer.cout * layer.cin * layer.taps, name=layer.name,
                      bytes=(2 if z1.bn_fused is not None else 1) * dy.numel() * dy.element_size())
         fuse = None
         if z1.bn_fused is not None:                      # dy is g (masked gradient of the BatchNorm output): dz1 on load
             g_, coef, c1, c2 = z1.bn_fused
             fuse = (z1.t, coef, c1, c2)
-        ops.conv2d_wgrad(x0.t, dy, G, cin=layer.cinp, cout=layer.cout_st, cinp=cpw, coutp=cow, ipe=self.B, ks=layer.ks,
-                         stride=1, pad=layer.pad, x_shared=True, per_image=True, bn_fuse=fuse)
-        ds = torch.empty(self.N, gate.shape[-1], dtype=F32, device=self.dev)
-        dw = self._grad_slot("w", layer) if layer.trainable else torch.empty(E * layer.cout * layer.cin * layer.taps,
-                                                                             dtype=F32, device=self.dev)
-        ops.eca_stem_fold(G, gate, self._tab("w", layer), dw, ds, self.N, self.B, layer.cout, layer.cin, layer.ks, cow, cpw)
-        if ecal.trainable:
-            # ds plays the role of the (single) partial row of sum_hw dy*x in the generic ECA backward
-            ops.eca_bwd_small(ds, 1, gate, gapmean, self._tab("eca", ecal), ecal.k, None,
-                              self._grad_slot("eca", ecal).view(E, ecal.k), self.N, self.B, gate.shape[-1], ecal.creal)
+        self._filter_grads(x0.t, dy, layer, self.eca1, gate, gapmean, x_shared=True, bn_fuse=fuse)
+
+    def _filter_grads(self, xt, dy, layer, ecal, gate, gapmean, want_dgap=False, dgap_scale=1.0, **wgrad_kw):
+        """backward of conv(x * gate) through per-image filter gradients G[n] = dy (x) x (no gated activation, no data-gradient
+        conv for the gate): dW = sum_n g[n] G[n] and ds = sum W G[n] (eca_stem_fold), then the ECA weight gradient from ds, which
+        plays the (single) partial row of sum_hw dy*x in the generic ECA backward.  Frozen layers get a scratch gradient.
+        -> dgap [N,C] (``want_dgap``: the gate's pooled input needs its gradient)"""
+        N, B_, E, c = self.N, self.B, self.E, gate.shape[-1]
+        cow, cpw = self._wgrad_tile(layer)
+        G = self._wgrad_ws(N * layer.taps * cow * cpw, main=True)
+        ops.conv2d_wgrad(xt, dy, G, cin=layer.cinp, cout=layer.cout_st, cinp=cpw, coutp=cow, ipe=B_, ks=layer.ks,
+                         stride=layer.stride, pad=layer.pad, per_image=True, **wgrad_kw)
+        ds = torch.empty(N, c, dtype=F32, device=self.dev)
+        dw = self._grad_slot("w", layer) if layer.trainable else torch.empty(
+            E * layer.cout * layer.cin * layer.taps, dtype=F32, device=self.dev)
+        ops.eca_stem_fold(G, gate, self._tab("w", layer), dw, ds, N, B_, layer.cout, layer.cin, layer.ks, cow, cpw)
+        dgap = torch.empty(N, c, dtype=F32, device=self.dev) if want_dgap else None
+        if ecal.trainable or want_dgap:
+            dwe = self._grad_slot("eca", ecal).view(E, ecal.k) if ecal.trainable else torch.empty(
+                E, ecal.k, dtype=F32, device=self.dev)
+            ops.eca_bwd_small(ds, 1, gate, gapmean, self._tab("eca", ecal), ecal.k, dgap, dwe, N, B_, c, ecal.creal,
+                              dgap_scale=dgap_scale)
+        return dgap
 
     def _merge_alt_head(self, head, al):
         """moe_alt: alpha comes from its own MLP; place it in column 4 of the head rows (device copy)."""

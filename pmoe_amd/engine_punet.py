@@ -21,6 +21,7 @@ from .engine import ExpertGroupEngine, GroupedBN, GroupedConv, Var, r16, F32
 
 class _UpConv(GroupedConv):
     """ConvTranspose2d(cin, cout, 2, 2) as a 1x1 layer with 4*cout rows (row (dy*2+dx)*cout + c)."""
+    route_bias = False        # the bias gradient is taken from the un-shuffled output gradient in PUNetEngine._up_bwd
 
     def __init__(self, eng, name, mod):
         super().__init__(eng, name, None, None, mod.in_channels, 4 * mod.out_channels, 1, 1, 0)
@@ -33,13 +34,10 @@ class _UpConv(GroupedConv):
     def trainable(self):
         return self.mod.weight.requires_grad or self.mod.bias.requires_grad
 
-    def store_grads(self, eng, ws, cow, cpw):
-        """weight gradient of the 4*Cout-row 1x1 layer -> ConvTranspose2d layout [cin, cout, 2, 2] (a strided copy);
-        the bias gradient is taken from the un-shuffled output gradient in PUNetEngine._up_bwd."""
-        full = torch.empty(1, self.cout, self.cin, dtype=F32, device=eng.dev)
-        ops.unpack_conv_wgrad(ws, full, 1, self.cout, self.cin, 1, cow, cpw)
+    def scatter_grads(self, eng, full_w, full_b):
+        """weight gradient of the 4*Cout-row 1x1 layer -> ConvTranspose2d layout [cin, cout, 2, 2] (a strided copy)"""
         eng._grad_slot("wT", self).view(self.cin, self.c_up, 2, 2).copy_(
-            full.view(2, 2, self.c_up, self.cin).permute(3, 2, 0, 1))
+            full_w.view(2, 2, self.c_up, self.cin).permute(3, 2, 0, 1))
 
     def pack_derived(self, dev):
         m = self.mod
@@ -179,7 +177,7 @@ class PUNetEngine(ExpertGroupEngine):
         super()._ensure_built(dev, dtype)
 
     def _extra_tables(self):
-        return [((kind, id(l)), [l.shadow[kind]]) for l in self.shadow_bns for kind in ("gamma", "beta", "rm", "rv")]
+        return [(self._key(kind, l), [l.shadow[kind]]) for l in self.shadow_bns for kind in ("gamma", "beta", "rm", "rv")]
 
     def _pack_all(self):
         for up in self.up_layers:
