@@ -477,6 +477,21 @@ int pmoe_seg_loss_fwd(const float* logits, const int64_t* target, int32_t B, int
 int pmoe_seg_loss_bwd(const float* logits, const int64_t* target, const float* coefG, const float* coefT, const float* dloss,
                       float* dlogits, int32_t B, int32_t F, int32_t C, int32_t H, int32_t W, int32_t mode, void* stream);
 
+/* ---- stage-0 U-Net training (reference caller trainer/train_0.py:52,55,68,230; model/blocks/unet.py:50-95).
+ * dice_score (trainer/loss.py:20-31): logits f32 [B][C][HW] (NCHW as UNet.forward returns them), target int64 [B][HW],
+ * C <= 64.  Per-pixel arg-max over the classes (ties: lowest index, as torch.argmax), integer counts [3][C] (arg-max ==
+ * target == c, arg-max == c, target == c; zeroed by the call), dice[c] = 2 (inter + epsilon) / (pred + target + epsilon) in
+ * f32.  Integer reductions only: bit-reproducible, no host synchronisation. */
+int pmoe_dice_score(const float* logits, const int64_t* target, int32_t B, int32_t C, int64_t HW, float epsilon,
+                    uint64_t* counts, float* dice, void* stream);
+/* nn.Dropout2d (unet.py:31,53-65): table f32 [N][C] = 0 with probability p, else 1 / (1 - p), from the counter-based hash
+ * of (seed, n * C + c); p = 0 keeps everything, p = 1 drops everything. */
+int pmoe_dropout2d_table(float* table, int32_t N, int32_t C, float p, uint64_t seed, void* stream);
+/* x[n][pix][coff + c] *= table[n][c] in place over an NHWC channel window (x [N][HW][ld]; C, ld, coff multiples of the
+ * 16-byte vector): Dropout2d forward on the activation, backward on its gradient. */
+int pmoe_channel_scale(void* x, int32_t ld, int32_t coff, const float* table, int32_t N, int64_t HW, int32_t C, int32_t dtype,
+                       void* stream);
+
 /* ---- fused optimizer tail of the stage-2 step (reference caller trainer/train_2.py:157-165,184 + conf
  * stage_2_pmoe.yaml:11,137-144): torch.nn.utils.clip_grad_norm_, torch.optim.Adam(amsgrad=True).step() and
  * torch.optim.swa_utils.AveragedModel.update_parameters, each as ONE launch over a chunk table instead of a few

@@ -268,8 +268,10 @@ class PUNetEngine(ExpertGroupEngine):
             h = self._materialize(h)
         return self._conv(h, layer, bias=True)
 
-    def _maxpool2(self, x, cat=None, fused=None):
-        """``fused``: the pooled tensor was already written by the pass that produced x (_bn, pool_to): only the tape entry is added."""
+    def _maxpool2(self, x, cat=None, fused=None, drop=None):
+        """``fused``: the pooled tensor was already written by the pass that produced x (_bn, pool_to): only the tape entry is added.
+        ``drop``: the Dropout2d scale table [N,C] that _skip_dropout applied to x and the pooled tensor: the gradient of the
+        un-dropped activation is the gradient of x times the same table."""
         n, h, w, _ = x.t.shape
         y = Var(fused if fused is not None else self._new(n, h // 2, w // 2, x.c))
         if fused is None:
@@ -283,6 +285,8 @@ class PUNetEngine(ExpertGroupEngine):
                     return
                 dx = self._new(n, h, w, x.c)
                 ops.maxpool2_bwd(x.t, y.grad, dx, dskip=skip, c=x.c, x_coff=x.coff, dskip_coff=x.coff)
+                if drop is not None:
+                    ops.channel_scale(dx, drop)
                 x.set_grad(dx)
             self.tape.append(bwd)
         return y
@@ -319,7 +323,7 @@ class PUNetEngine(ExpertGroupEngine):
                      else None)
             a = self._conv3(h, U["dwn"][i], out=cat, pool_to=fused)
             cats.append(cat)
-            h = self._maxpool2(a, cat, fused=fused)
+            h = self._maxpool2(a, cat, fused=fused, drop=self._skip_dropout(U, a, fused))
             hh, ww = hh // 2, ww // 2
         # round 4 (late): the last BatchNorm + ReLU of a block whose one consumer is a 1x1 layer (the transposed convolutions, the
         # final classifier) stays pending on its pre-activation and is applied on load by that launch (untaped forward: _last_bn)
@@ -338,6 +342,14 @@ class PUNetEngine(ExpertGroupEngine):
                 self.tape.append(lambda t=t, up=up, cat=cat: self._up_bwd(t, up, cat))
             h = self._conv3(cat, U["up_forw"][j], defer=lazy)
         return self._conv1x1_after_bn(h, U["out"]), (None if x5.pending_bn is not None else x5)
+
+    def _skip_dropout(self, U, a, pooled):
+        """hook: nn.Dropout2d on a skip activation x_1..x_4 (unet.py:53-65) -> its scale table, or None where there is none
+        (the U-Nets inside a PU-Net are built with dropout = 0: no launch; one built with dropout > 0 is refused, not ignored)."""
+        if U["mod"].dropout.p > 0:
+            raise NotImplementedError("a U-Net inside a PU-Net runs without Dropout2d (punet.py:33-39,62-68 never configure it); "
+                                      "UNet(dropout>0) is supported on its own (UNetEngine)")
+        return None
 
     fuse_in_bn_1x1 = os.environ.get("PMOE_PUNET_BN_1X1", "1") != "0"      # round 4 (late): see _unet_fwd (the variable: A/B runs)
     fuse_upconv_shuffle = True     # round 4: ConvTranspose2d = 1x1 GEMM whose store scatters the 2x2 blocks itself (frozen / untaped path)
@@ -614,3 +626,82 @@ class PredictiveUnetEngine(PUNetEngine):
         self._layout_arena()                             # (the accumulator has the arena's padded length)
         self._acc = torch.zeros(self._arena_numel, dtype=F32, device=tape_state["dev"])
         return super().backward(tape_state, *douts)
+
+
+class UNetEngine(PUNetEngine):
+    """The segmentation ``UNet`` on its own (``model/blocks/unet.py:50-95``): stage-0 training (``trainer/train_0.py:130-140``)
+    and plain segmentation inference.  A group of one running the same taped primitives as ``pred_unet`` in stage 1: every layer
+    gets a weight gradient, every layer but the first convolution (its input is the image) a data gradient.
+
+    ``Dropout2d(p)`` on x_1..x_4: one [N,C] scale table per site (0 or 1/(1-p), seeded from the engine's seed counter), applied
+    in place to the skip window of the concatenation buffer and to the pooled tensor the BatchNorm pass wrote next to it -- the
+    scale is non-negative, so max-pooling the dropped activation equals dropping the pooled one, and the fused BatchNorm + pool
+    pass stays.  Nothing in backward reads the un-dropped activation: the BatchNorm backward recomputes the ReLU decision from
+    its pre-activation, the max-pool backward finds the same winners in the scaled window (an all-zero window's gradient is
+    multiplied by zero afterwards), and the convolutions that read the dropped tensors are the ones whose input they are."""
+    _punet_trains = True
+
+    def __init__(self, unet):
+        import types
+        self.return_inter = bool(unet.inter_repr)
+        self.debug_drop_tables = []        # the [N,C] scale table of every Dropout2d site of the LAST forward (tests replay them)
+        ExpertGroupEngine.__init__(self, [types.SimpleNamespace(unet=unet)], alt=False)
+
+    def _collect_network(self, ex):
+        self.pu = None
+        self.up_layers, self.shadow_bns = [], []
+        self.unet = self._collect_unet("unet", ex[0].unet)
+        self.conv1 = self.eca1 = self.head = None
+        self.blocks = []
+        for up in self.unet["up"]:
+            up.need_dgrad = True
+        self.unet["dwn"][0]["c1"].need_dgrad = False          # fed by the image
+
+    def _skip_dropout(self, U, a, pooled):
+        p = float(U["mod"].dropout.p)
+        if p <= 0.0 or not self.training:
+            return None
+        table = torch.empty(a.t.shape[0], a.c, dtype=F32, device=self.dev)
+        seed = (next(self._seed_counter) * 0x9E3779B1 + self.base_seed) & 0xFFFFFFFFFFFF
+        ops.dropout2d_table(table, p, seed)
+        ops.channel_scale(a.t, table, c=a.c, coff=a.coff)
+        if pooled is not None:
+            ops.channel_scale(pooled, table)
+        self.debug_drop_tables.append(table)
+        return table
+
+    def forward(self, image, training, taping, dtype, base_seed=0):
+        """image [B,C,H,W] f32 -> (logits [B,classes,H,W] f32, bottleneck feature [B,512] or None, state)."""
+        mod = self.unet["mod"]
+        if taping and self.return_inter:
+            raise NotImplementedError("UNet(inter_repr=True) is inference-only on the HIP path: the pooled x_5 output takes no "
+                                      "gradient (call it under torch.no_grad(), or build the U-Net with inter_repr=False)")
+        first = self.unet["dwn"][0]["c1"]
+        if image.shape[1] != first.cin:
+            raise ValueError(f"UNet: image carries {image.shape[1]} channels, the first convolution expects {first.cin}")
+        Bsz = self._begin(image.unsqueeze(1), training, taping, dtype, base_seed)
+        H, W = image.shape[-2:]
+        x = Var(self._new(Bsz, H, W, first.cinp))
+        ops.nchw_to_nhwc(image.contiguous().float(), x.t)
+        self.debug_drop_tables = []
+        out, x5 = self._unet_fwd(self.unet, x)
+        self._bump_batch_counters()
+        nc = self.unet["out"].cout
+        logits = torch.empty(Bsz, nc, H, W, dtype=F32, device=self.dev)
+        ops.nhwc_to_nchw(out.t, logits, nc)
+        inter = None
+        if self.return_inter:
+            feat = Var(self._new(Bsz, 1, 1, x5.c))
+            self._gap_to(x5, feat, 0)
+            inter = feat.t.view(Bsz, -1).float()
+        state = dict(tape=self.tape, tail=out, B=self.B, N=self.N, dev=self.dev, dtype=self.dtype)
+        self.tape = None
+        return logits, inter, state
+
+    def _tail_bwd(self, out, dout):
+        """d loss / d logits [B,classes,H,W] f32 -> the gradient of the classifier's NHWC output (zero padded)."""
+        if dout is None:
+            return
+        g = torch.empty_like(out.t)
+        ops.nchw_to_nhwc(dout.contiguous().float(), g)
+        out.set_grad(g)

@@ -133,6 +133,9 @@ SIGNATURES = {
     "pmoe_seg_loss_cp": [_I],
     "pmoe_seg_loss_fwd": [_P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _F, _F, _P, _P, _P, _P, _P, _P],
     "pmoe_seg_loss_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "pmoe_dice_score": [_P, _P, _I, _I, _L, _F, _P, _P, _P],
+    "pmoe_dropout2d_table": [_P, _I, _I, _F, C.c_uint64, _P],
+    "pmoe_channel_scale": [_P, _I, _I, _P, _I, _L, _I, _I, _P],
     "pmoe_resample_u8_horizontal": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P],
     "pmoe_resample_u8_vertical_to_f32": [_P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P],
     "pmoe_resample_u8_vertical_to_i64": [_P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P],

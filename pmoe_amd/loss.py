@@ -1,4 +1,5 @@
-"""Drop-in for ``PMoE/trainer/loss.py:121-132`` (``moe_loss``) backed by the fused HIP loss kernel."""
+"""Drop-ins for ``PMoE/trainer/loss.py`` backed by the fused HIP loss kernels: ``moe_loss``, ``punet_loss``, ``pmoe_loss``,
+``AutoregressiveCriterion`` (stage 1) and the stage-0 pair ``cross_entropy_tversky_weighted_loss`` / ``dice_score``."""
 import torch
 
 from . import ops
@@ -85,10 +86,10 @@ def pmoe_loss(actions, speed_pred, actions_gt, speed_gt, loss_coefs):
 
 class _SegLossFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits, target, mode):
+    def forward(ctx, logits, target, mode, ce_weight, tversky_weight):
         lg = logits.contiguous().float()
         tg = target.contiguous()
-        loss, coefG, coefT = ops.seg_loss_fwd(lg, tg, mode)
+        loss, coefG, coefT = ops.seg_loss_fwd(lg, tg, mode, ce_weight, tversky_weight)
         ctx.mode, ctx.saved = mode, (lg, tg, coefG, coefT)
         ctx.frame_losses = loss[1:]
         return loss[0]
@@ -99,7 +100,29 @@ class _SegLossFn(torch.autograd.Function):
         ctx.saved = None
         dl = torch.empty_like(lg)
         ops.seg_loss_bwd(lg, tg, coefG, coefT, g.contiguous().float().view(1), dl, ctx.mode)
-        return dl, None, None
+        return dl, None, None, None, None
+
+
+def cross_entropy_tversky_weighted_loss(pred, target, cross_entropy_weight=0.5, tversky_weight=0.5):
+    """``trainer/loss.py:47-55`` (the stage-0 criterion, train_0.py:68): ``cross_entropy_weight * cross_entropy(weight = 1 -
+    class dice) + tversky_weight * tversky_loss`` of ``pred`` [B,C,H,W] logits against ``target`` [B,H,W] int64 class indices --
+    the one-frame case of the segmentation-loss kernels behind :class:`AutoregressiveCriterion`."""
+    if cross_entropy_weight + tversky_weight != 1:
+        raise ValueError("Cross Entropy weight and Tversky weight should sum to 1")
+    if pred.dim() != 4 or tuple(target.shape) != (pred.shape[0],) + tuple(pred.shape[2:]):
+        raise ValueError(f"cross_entropy_tversky_weighted_loss: pred [B,C,H,W] and target [B,H,W] expected, got "
+                         f"{tuple(pred.shape)} / {tuple(target.shape)}")
+    if target.dtype != torch.int64:
+        raise ValueError("cross_entropy_tversky_weighted_loss: target must be int64 class indices")
+    return _SegLossFn.apply(pred.unsqueeze(1), target.unsqueeze(1), "tversky", float(cross_entropy_weight),
+                            float(tversky_weight))
+
+
+@torch.no_grad()
+def dice_score(pred, target, epsilon=1e-6):
+    """``trainer/loss.py:20-31`` (train_0.py:230 validation metric): per-class dice of the arg-max prediction, f32 [C] on the
+    device, computed by one counting kernel over the f32 NCHW logits -- no per-class Python loop, no host synchronisation."""
+    return ops.dice_score(pred.contiguous().float(), target.contiguous().long(), epsilon)[0]
 
 
 class AutoregressiveCriterion(torch.nn.Module):
@@ -120,4 +143,4 @@ class AutoregressiveCriterion(torch.nn.Module):
         assert targets.size(1) == self.n_target_frames
         if targets.dtype != torch.int64:
             raise ValueError("AutoregressiveCriterion: targets must be int64 class indices (data_loader.py segmentation masks)")
-        return _SegLossFn.apply(inputs, targets, self.loss_type)
+        return _SegLossFn.apply(inputs, targets, self.loss_type, 0.5, 0.5)

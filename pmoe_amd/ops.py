@@ -678,6 +678,39 @@ def seg_loss_bwd(logits, target, coefG, coefT, dloss, dlogits, mode):
                                    stream_ptr()), "pmoe_seg_loss_bwd")
 
 
+def dice_score(logits, target, epsilon=1e-6):
+    """``trainer/loss.py:20-31`` on the device: logits f32 [B,C,H,W] (NCHW, as ``UNet.forward`` returns them), target int64
+    [B,H,W] -> dice f32 [C] = 2 (inter + eps) / (pred + target + eps) of the arg-max prediction.  Integer counts, no host sync."""
+    if logits.dim() != 4 or tuple(target.shape) != (logits.shape[0],) + tuple(logits.shape[2:]):
+        raise ValueError(f"dice_score: logits [B,C,H,W] and target [B,H,W] expected, got {tuple(logits.shape)} / "
+                         f"{tuple(target.shape)}")
+    b, c, h, w_ = logits.shape
+    if not 1 <= c <= 64:
+        raise ValueError(f"dice_score: C={c} must be 1..64")
+    counts = torch.empty(3, c, dtype=torch.int64, device=logits.device)
+    dice = torch.empty(c, dtype=torch.float32, device=logits.device)
+    check(load().pmoe_dice_score(ptr(logits, "logits", torch.float32), ptr(target, "target", torch.int64), b, c, h * w_,
+                                 float(epsilon), ptr(counts), ptr(dice), stream_ptr()), "pmoe_dice_score")
+    return dice, counts
+
+
+def dropout2d_table(table, p, seed):
+    """table f32 [N,C] <- Dropout2d scales: 0 with probability p, else 1 / (1 - p) (one decision per sample and channel)."""
+    n, c = table.shape
+    check(load().pmoe_dropout2d_table(ptr(table, "table", torch.float32), n, c, float(p), int(seed), stream_ptr()),
+          "pmoe_dropout2d_table")
+
+
+def channel_scale(x, table, c=None, coff=0):
+    """x[n, :, :, coff + k] *= table[n, k] in place over the channel window [coff, coff + c) of NHWC ``x``."""
+    n, h, w_, ld = _nhwc(x, "x")
+    c = ld if c is None else c
+    if tuple(table.shape) != (n, c):
+        raise ValueError(f"channel_scale: table must be {(n, c)}, got {tuple(table.shape)}")
+    check(load().pmoe_channel_scale(ptr(x, "x"), ld, coff, ptr(table, "table", torch.float32), n, h * w_, c, dt(x),
+                                    stream_ptr()), "pmoe_channel_scale")
+
+
 def action_head_fwd(head, spd, actions, speeds, B):
     f32 = torch.float32
     check(load().pmoe_action_head_fwd(ptr(head, "head"), head.shape[-1], ptr(spd, "spd", head.dtype), spd.shape[-1],
@@ -720,5 +753,5 @@ def blend_bwd(moe_act, pu_act, lat_w, long_w, out, dout, dlat_w, dlat_b, dlong_w
 
 for _n in ("maxpool2_fwd", "pixel_shuffle2", "copy_window", "action_head_fwd", "action_head_bwd", "action_loss",
            "blend_fwd", "blend_bwd", "maxpool2_bwd", "pixel_unshuffle2", "add_window", "nhwc_to_nchw", "seg_loss_fwd",
-           "seg_loss_bwd", "cat_windows"):
+           "seg_loss_bwd", "cat_windows", "dice_score", "dropout2d_table", "channel_scale"):
     globals()[_n] = _timed(globals()[_n])

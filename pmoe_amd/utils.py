@@ -20,6 +20,41 @@ def freeze(model: nn.Module, exclude: List = (), verbose: bool = False) -> nn.Mo
     return model
 
 
+def init_weights(method: str = "kaiming_normal", mean: float = 0.0, std: float = 0.5, low: float = 0.0, high: float = 1.0,
+                 mode: str = "fan_in", nonlinearity: str = "leaky_relu", gain: float = 1.0):
+    """``utils/nn.py:61-194``: returns the function for ``model.apply`` that re-initialises the weights of every matched layer
+    with ``method`` and zeroes its bias.  The method names are the reference's (``"kaiming_uniform_"`` carries its trailing
+    underscore there).  Matched layers, as in the reference: convolutions and ``Linear`` for the two Kaiming methods, those plus
+    BatchNorm for ``normal`` / ``uniform`` / ``xavier_*`` (torch's Xavier fills reject a BatchNorm's 1-D weight with a
+    ``ValueError``, in the reference too); ``ConvTranspose2d`` is in neither list.  Both the ``torch.nn`` classes and this
+    package's parameter containers are recognised.  Host code on the parameters, drawing from torch's global generator in
+    ``model.apply`` order: under the same seed a reference model and its container twin get bit-identical values."""
+    from .model import blocks as B
+    plain = (nn.Conv1d, nn.Conv2d, nn.Conv3d, nn.Linear, B.Conv1d, B.Conv2d, B.Linear)
+    with_norm = plain + (nn.BatchNorm1d, nn.BatchNorm2d, nn.BatchNorm3d, B.BatchNorm1d)      # (B.BatchNorm2d derives from it)
+    table = {
+        "kaiming_normal": (plain, lambda w: nn.init.kaiming_normal_(w, mode=mode, nonlinearity=nonlinearity)),
+        "kaiming_uniform_": (plain, lambda w: nn.init.kaiming_uniform_(w, mode=mode, nonlinearity=nonlinearity)),
+        "normal": (with_norm, lambda w: nn.init.normal_(w, mean=mean, std=std)),
+        "uniform": (with_norm, lambda w: nn.init.uniform_(w, a=low, b=high)),
+        "xavier_normal": (with_norm, lambda w: nn.init.xavier_normal_(w, gain=gain)),
+        "xavier_uniform": (with_norm, lambda w: nn.init.xavier_uniform_(w, gain=gain)),
+    }
+    if method not in table:
+        raise ValueError(f"init_weights: unknown method {method!r}; one of {sorted(table)}")
+    print(f"Initializing the model using {method}!")
+    kinds, fill = table[method]
+
+    def init(m):
+        if isinstance(m, kinds):
+            fill(m.weight)
+            bias = getattr(m, "bias", None)
+            if bias is not None:
+                nn.init.constant_(bias, 0)
+
+    return init
+
+
 class AttrDict(dict):
     """Attribute-access mapping accepted wherever the reference takes an OmegaConf node: supports
     ``cfg.key``, ``**cfg.node`` and item assignment (``moe.py:55-66,274``)."""
