@@ -437,6 +437,25 @@ int pmoe_blend_fwd(const float* moe_actions, const float* punet_actions, const f
 int pmoe_blend_bwd(const float* moe_actions, const float* punet_actions, const float* lat_w, const float* long_w,
                    const float* out, const float* dout, float* dlat_w, float* dlat_b, float* dlong_w, float* dlong_b,
                    float* dpunet, int32_t B, void* stream);
+/* ---- closed-loop policy tick (pmoe_amd/infer.py:PolicyTick; the agent's deques, autoagents/image_agent.py:63-64,136,158)
+ * History ring pushed IN PLACE: ring [B][T][L] elements of `dtype`; slot t + 1 moves to slot t (t = 0..T-2) and item [B][L]
+ * becomes slot T-1 (one thread owns one element offset in all T slots and walks them oldest first: no second buffer, and a
+ * recorded launch keeps working on the same pointers).  `item` must not overlap the ring.  nhwc != NULL (dtype must be f32, the
+ * item is C channel planes [B][C][L / C]): the launch also writes the new item as `nhwc_dtype` [B][L / C][Cp], zero padded,
+ * bit for bit what pmoe_nchw_to_nhwc gives (Cp a multiple of the 16-byte vector, >= C); NULL: C / Cp / nhwc_dtype unused. */
+int pmoe_history_push(void* ring, const void* item, int32_t B, int32_t T, int64_t L, int32_t dtype, void* nhwc, int32_t C,
+                      int32_t Cp, int32_t nhwc_dtype, void* stream);
+/* One draw per batch row from the mixture pmoe_gate_mixture_fwd wrote (probs [B][E], mean / std [B][E][2]; either head layout),
+ * on the device: state = two 64-bit words {seed, draws_done} in DEVICE memory (8-byte aligned).  With c = draws_done and
+ * u_i = hash_uniform(seed, (c * B + b) * 4 + i) (csrc/common.h): the component is the first k whose running f32 sum of
+ * probs[b][0..k] (index order) exceeds u0 * sum(probs[b][:]), the last one if none does; r = sqrtf(-2 logf(1 - u1));
+ * raw[b] = mean[b][k] + std[b][k] * (r cosf(2 pi u2), r sinf(2 pi u2)).  After every row has read the state the launch stores
+ * draws_done + 1, so re-issuing it with identical arguments draws fresh numbers.  punet_actions != NULL ([B][2], with the two
+ * nn.Linear(2,1) of pmoe_blend_fwd): out [B][2] = the blend of raw with them, bit-identical to pmoe_blend_fwd(raw, ...);
+ * NULL: lat_w .. out unused.  One workgroup; raw is always written. */
+int pmoe_mixture_draw(const float* probs, const float* mean, const float* std_, void* state, float* raw,
+                      const float* punet_actions, const float* lat_w, const float* lat_b, const float* long_w,
+                      const float* long_b, float* out, int32_t B, int32_t E, void* stream);
 
 /* ---- stage-1 PU-Net training (trainer/train_1.py:129-141) ------------------------------------------
  * Backward of nn.MaxPool2d(2,2) (blocks/unet.py:52-62): dx = scatter of dy to the FIRST maximum of each 2x2 window of x

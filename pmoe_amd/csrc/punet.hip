@@ -148,6 +148,10 @@ __global__ void __launch_bounds__(256) action_loss_kernel(const float* __restric
 }
 
 // PMoE blend (moe.py:353-356): out[b][j] = tanh(w_j[0]*moe[b][j] + w_j[1]*punet[b][j] + bias_j), j=0 lateral, j=1 longitudinal
+// (one expression for blend_fwd_kernel and mixture_draw_kernel: the closed-loop tick's blend equals pmoe_blend_fwd bit for bit)
+__device__ __forceinline__ float blend_value(const float* __restrict__ w, float bias, float moe, float pu) {
+    return tanhf(w[0] * moe + w[1] * pu + bias);
+}
 __global__ void __launch_bounds__(256) blend_fwd_kernel(const float* __restrict__ moe_act, const float* __restrict__ pu_act,
                                                        const float* __restrict__ lat_w, const float* __restrict__ lat_b,
                                                        const float* __restrict__ long_w, const float* __restrict__ long_b,
@@ -157,7 +161,7 @@ __global__ void __launch_bounds__(256) blend_fwd_kernel(const float* __restrict_
     const int j = i & 1;
     const float* w = j ? long_w : lat_w;
     const float bias = j ? long_b[0] : lat_b[0];
-    out[i] = tanhf(w[0] * moe_act[i] + w[1] * pu_act[i] + bias);
+    out[i] = blend_value(w, bias, moe_act[i], pu_act[i]);
 }
 
 // one workgroup: dW_j = sum_b g*[moe, punet], db_j = sum_b g, dpunet = g * w_j[1];  g = dout * (1 - out^2)
@@ -193,6 +197,100 @@ __global__ void __launch_bounds__(256) blend_bwd_kernel(const float* __restrict_
         dlat_w[0] = red[0][0]; dlat_w[1] = red[1][0]; dlat_b[0] = red[2][0];
         dlong_w[0] = red[3][0]; dlong_w[1] = red[4][0]; dlong_b[0] = red[5][0];
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Closed-loop history (pmoe_amd/infer.py:PolicyTick; the agent's deque, autoagents/image_agent.py:63-64,136,158) as a ring that
+// stays in place: ring [B][T][L], slot t + 1 moves to slot t (t = 0..T-2), `item` [B][L] becomes slot T-1.  One thread owns one
+// element offset (a 16-byte vector, or one element where L is not a multiple of it) in ALL T slots of its row and walks them
+// oldest first, so no thread reads what another one writes: in place, no second buffer, no ordering between threads.  The row
+// b is blockIdx.y (wave-uniform geometry, no per-element division).  `nhwc` (f32 rings of C channel planes, L = C * HW): the
+// same launch also writes the new item as ET [B][HW][Cp], zero padded -- the tensor pmoe_nchw_to_nhwc makes of it (a conversion
+// of the same f32 values: bit-identical); that half reads `item` only.
+template <typename RT, typename ET, int VEC>
+__global__ void __launch_bounds__(256) history_push_kernel(RT* ring, const RT* __restrict__ item, int T, long long L,
+                                                          ET* __restrict__ nhwc, int C, long long HW, int Cp) {
+    const int b = blockIdx.y;
+    RT* row = ring + (size_t)b * T * L;
+    const RT* src = item + (size_t)b * L;
+    const long long nv = L / VEC;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nv; i += (long long)gridDim.x * 256) {
+        RT* p = row + (size_t)i * VEC;
+        for (int t = 0; t + 1 < T; ++t, p += L) {
+            if (VEC == 1) *p = p[L];
+            else stg16(p, ldg16(p + L));
+        }
+        if (VEC == 1) *p = src[i];
+        else stg16(p, ldg16(src + (size_t)i * VEC));
+    }
+    if (nhwc == nullptr) return;
+    constexpr int VE = 16 / (int)sizeof(ET);
+    const float* planes = reinterpret_cast<const float*>(src);            // (RT is float on this half: checked by the entry point)
+    ET* dst = nhwc + (size_t)b * HW * Cp;
+    for (long long px = (long long)blockIdx.x * 256 + threadIdx.x; px < HW; px += (long long)gridDim.x * 256)
+        for (int c0 = 0; c0 < Cp; c0 += VE) {
+            float v[VE];
+#pragma unroll
+            for (int k = 0; k < VE; ++k) v[k] = c0 + k < C ? planes[(size_t)(c0 + k) * HW + px] : 0.f;
+            stg16(dst + (size_t)px * Cp + c0, pack16<ET>(v));
+        }
+}
+
+// One draw per batch row from the Gaussian mixture (moe.py:154-156 + dists.sample(), moe.py:337) with the counter-based
+// hash_uniform of common.h, and optionally the PMoE blend of the draw.  `state` = {seed, draws_done} lives in device memory:
+// every row reads it, then -- behind the barrier -- one lane stores draws_done + 1, so a launch re-issued with the same frozen
+// arguments (a recorded plan) draws fresh numbers.  ONE workgroup loops over the rows (B is a handful in the closed loop).
+//   u_i = hash_uniform(seed, (draws_done * B + b) * 4 + i);  component = first k with sum(probs[b, 0..k]) > u0 * sum(probs[b, :])
+//   (f32 running sums in index order; the last component when none does);  r = sqrt(-2 log(1 - u1));
+//   raw[b] = mean[b, k] + std[b, k] * (r cos(2 pi u2), r sin(2 pi u2))
+__global__ void __launch_bounds__(256) mixture_draw_kernel(const float* __restrict__ probs, const float* __restrict__ mean,
+                                                          const float* __restrict__ sd, unsigned long long* state,
+                                                          float* __restrict__ raw, const float* __restrict__ pu_act,
+                                                          const float* __restrict__ lat_w, const float* __restrict__ lat_b,
+                                                          const float* __restrict__ long_w, const float* __restrict__ long_b,
+                                                          float* __restrict__ out, int B, int E) {
+    const unsigned long long seed = state[0], done = state[1];
+    for (int b = threadIdx.x; b < B; b += 256) {
+        const unsigned long long ctr = (done * (unsigned long long)B + (unsigned long long)b) * 4ull;
+        const float u0 = hash_uniform(seed, ctr), u1 = hash_uniform(seed, ctr + 1), u2 = hash_uniform(seed, ctr + 2);
+        const float* p = probs + (size_t)b * E;
+        float total = 0.f;
+        for (int e = 0; e < E; ++e) total += p[e];
+        const float thr = u0 * total;
+        int k = E - 1;
+        float run = 0.f;
+        for (int e = 0; e < E; ++e) {
+            run += p[e];
+            if (run > thr) { k = e; break; }
+        }
+        const float r = sqrtf(-2.f * logf(1.f - u1)), ang = 6.28318530717958647692f * u2;
+        const size_t o = ((size_t)b * E + k) * 2;
+        const float a0 = mean[o] + sd[o] * (r * cosf(ang)), a1 = mean[o + 1] + sd[o + 1] * (r * sinf(ang));
+        raw[b * 2 + 0] = a0;
+        raw[b * 2 + 1] = a1;
+        if (pu_act) {
+            out[b * 2 + 0] = blend_value(lat_w, lat_b[0], a0, pu_act[b * 2 + 0]);
+            out[b * 2 + 1] = blend_value(long_w, long_b[0], a1, pu_act[b * 2 + 1]);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) state[1] = done + 1ull;
+}
+
+template <typename RT, typename ET>
+static int history_push_launch(void* ring, const void* item, int B, int T, long long L, void* nhwc, int C, long long HW, int Cp,
+                               hipStream_t stream) {
+    constexpr int VR = 16 / (int)sizeof(RT);
+    const bool vec = !(L % VR) && !((uintptr_t)ring % 16) && !((uintptr_t)item % 16);
+    const long long work = vec ? L / VR : L;
+    const dim3 grid(grid_for(work > HW ? work : HW), B);
+    if (vec)
+        hipLaunchKernelGGL((history_push_kernel<RT, ET, VR>), grid, dim3(256), 0, stream, (RT*)ring, (const RT*)item, T, L,
+                           (ET*)nhwc, C, HW, Cp);
+    else
+        hipLaunchKernelGGL((history_push_kernel<RT, ET, 1>), grid, dim3(256), 0, stream, (RT*)ring, (const RT*)item, T, L,
+                           (ET*)nhwc, C, HW, Cp);
+    return (int)hipGetLastError();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -282,6 +380,35 @@ int pmoe_blend_bwd(const float* moe_actions, const float* punet_actions, const f
     if (B < 1) return PMOE_ERR_ARG;
     hipLaunchKernelGGL(blend_bwd_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, moe_actions, punet_actions, lat_w,
                        long_w, out, dout, dlat_w, dlat_b, dlong_w, dlong_b, dpunet, B);
+    return (int)hipGetLastError();
+}
+
+int pmoe_history_push(void* ring, const void* item, int32_t B, int32_t T, int64_t L, int32_t dtype, void* nhwc, int32_t C,
+                      int32_t Cp, int32_t nhwc_dtype, void* stream) {
+    if (!ring || !item || B < 1 || B > 65535 || T < 1 || L < 1) return PMOE_ERR_ARG;
+    if (dtype != PMOE_DT_BF16 && dtype != PMOE_DT_F32) return PMOE_ERR_ARG;
+    if (!nhwc) {
+        if (dtype == PMOE_DT_F32) return history_push_launch<float, float>(ring, item, B, T, L, nullptr, 0, 0, 0, (hipStream_t)stream);
+        return history_push_launch<bf16, bf16>(ring, item, B, T, L, nullptr, 0, 0, 0, (hipStream_t)stream);
+    }
+    // the NHWC copy of the new item: f32 channel planes in, whole 16-byte vectors out
+    if (dtype != PMOE_DT_F32 || C < 1 || Cp < C || L % C || (uintptr_t)nhwc % 16) return PMOE_ERR_ARG;
+    const long long HW = L / C;
+    if (nhwc_dtype == PMOE_DT_F32) {
+        if (Cp % 4) return PMOE_ERR_ARG;
+        return history_push_launch<float, float>(ring, item, B, T, L, nhwc, C, HW, Cp, (hipStream_t)stream);
+    }
+    if (nhwc_dtype != PMOE_DT_BF16 || Cp % 8) return PMOE_ERR_ARG;
+    return history_push_launch<float, bf16>(ring, item, B, T, L, nhwc, C, HW, Cp, (hipStream_t)stream);
+}
+
+int pmoe_mixture_draw(const float* probs, const float* mean, const float* std_, void* state, float* raw,
+                      const float* punet_actions, const float* lat_w, const float* lat_b, const float* long_w,
+                      const float* long_b, float* out, int32_t B, int32_t E, void* stream) {
+    if (!probs || !mean || !std_ || !state || !raw || B < 1 || E < 1 || (uintptr_t)state % 8) return PMOE_ERR_ARG;
+    if (punet_actions && (!lat_w || !lat_b || !long_w || !long_b || !out)) return PMOE_ERR_ARG;
+    hipLaunchKernelGGL(mixture_draw_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, probs, mean, std_,
+                       (unsigned long long*)state, raw, punet_actions, lat_w, lat_b, long_w, long_b, out, B, E);
     return (int)hipGetLastError();
 }
 

@@ -388,6 +388,7 @@ class ExpertGroupEngine:
         self._ptr_key = None
         self._packed_version = None
         self._built_for = key
+        self._build_gen = self.__dict__.get("_build_gen", 0) + 1      # (pmoe_amd/infer.py: recorded pointers into the old banks are stale)
 
     def _refresh_tables(self, dev):
         """One int64 device table of all parameter/buffer pointers (rebuilt only when storage moved)."""
@@ -1297,9 +1298,11 @@ class ExpertGroupEngine:
         return dgap
 
     def _merge_alt_head(self, head, al):
-        """moe_alt: alpha comes from its own MLP; place it in column 4 of the head rows (device copy)."""
-        merged = Var(head.t.clone())
-        merged.t.view(self.N, 16)[:, 4] = al.t.view(self.N, 16)[:, 0]
+        """moe_alt: alpha comes from its own MLP; place it in column 4 of the head rows (two window copies: library launches,
+        so that a recorded plan -- pmoe_amd/infer.py -- holds them; the mixture inside PMoE is of this kind, moe.py:330-332)."""
+        merged = Var(torch.empty_like(head.t))
+        ops.copy_window(head.t, 0, merged.t, 0, 16)
+        ops.copy_window(al.t, 0, merged.t, 4, 1)
         merged.needs_grad = head.needs_grad or al.needs_grad
         if self.taping and merged.needs_grad:
             def bwd():

@@ -174,6 +174,7 @@ class PUNetEngine(ExpertGroupEngine):
             for l in self.shadow_bns:
                 l.shadow = {k: torch.zeros(l.C, dtype=F32, device=dev) for k in ("gamma", "beta", "rm", "rv")}
             self._punet_built_for = key
+            self._punet_build_gen = self.__dict__.get("_punet_build_gen", 0) + 1
         super()._ensure_built(dev, dtype)
 
     def _extra_tables(self):
@@ -496,6 +497,17 @@ class PUNetEngine(ExpertGroupEngine):
             self.debug_x0_kept = x0.t if x0 is not None else None
         self.taping = taping_saved
         self.training = top_training
+        actions, speeds = self._expert_tail(x0, inter, spd, cmd, Bsz)
+        self._shadows_out()
+        self._bump_batch_counters()
+        state = dict(tape=self.tape, tail=self._tail, B=self.B, N=self.N, dev=self.dev, dtype=self.dtype)
+        self.tape = self._tail = None
+        return actions, speeds, state
+
+    def _expert_tail(self, x0, inter, spd, cmd, Bsz):
+        """backbone (or the PU-Net bottleneck), measurement encoders, heads and the tanh action head behind the PU-Net: the half
+        that the full forward and the closed-loop tick (forward_cached) share, launch for launch."""
+        e = self.experts[0]
         feat = Var(self._new(self.N, 1, 1, 1536))
         if self.return_inter:
             self._gap_to(inter, feat, 0)
@@ -511,11 +523,79 @@ class PUNetEngine(ExpertGroupEngine):
         actions = torch.empty(Bsz, 2, dtype=F32, device=self.dev)
         speeds = torch.empty(Bsz, 1, dtype=F32, device=self.dev)
         ops.action_head_fwd(head.t.view(Bsz, -1), sp.t.view(Bsz, -1), actions, speeds, Bsz)
-        self._shadows_out()
-        self._bump_batch_counters()
-        state = dict(tape=self.tape, tail=(head, sp, actions), B=self.B, N=self.N, dev=self.dev, dtype=self.dtype)
+        self._tail = (head, sp, actions)
+        return actions, speeds
+
+    # ------------------------------------------------------------------ closed loop: the masks of the older frames are given
+    def _cached_begin(self, images, dtype, training=False, taping=False):
+        if training or taping or any(getattr(m, "training", False) for m in (self.experts[0], self.pu)):
+            raise RuntimeError("PUNetEngine: the cached-mask forward is the eval-mode, untaped chain: call model.eval() first")
+        if getattr(self, "debug_forced_masks", None) is not None or getattr(self, "debug_x0", None) is not None:
+            raise RuntimeError("PUNetEngine: debug_forced_masks / debug_x0 replace U-Net passes of the FULL forward and do not "
+                               "combine with cached masks")
+        if images.shape[1] != self.pu.n_past_frames:
+            raise AssertionError("Number of images should match number of past frames")      # punet.py:84-86
+        if self.pu.n_future_frames == 0:
+            raise NotImplementedError("PUNetExpert needs future_frames > 0 (moe.py:286-289 sizes its stem from it)")
+        Bsz = self._begin(images, False, False, dtype, 0)
         self.tape = None
-        return actions, speeds, state
+        return Bsz
+
+    def prepare_cached(self, images, dtype):
+        """What the cached route keeps OUT of the tick: packs, pointer tables and the padded-BatchNorm shadows (torch copies;
+        constant in eval mode).  Called when a PolicyTick is built or refreshed; ``images`` is its frame ring [B,T,C,H,W]."""
+        self._cached_begin(images, dtype)
+        self._shadows_in()
+
+    def mask_of(self, images, frame, dtype):
+        """``unet`` over ONE frame given as NHWC [B,H,W,16] in the compute dtype -> its mask tensor [B,H,W,r16(classes)]: the pass
+        the full forward runs per frame (eval mode: it depends on that frame alone)."""
+        self._cached_begin(images, dtype)
+        out = self._unet_fwd(self.unet, Var(frame))[0]
+        kept = getattr(self, "debug_pass_out", None)
+        if kept is not None:
+            kept.append(out.t)
+        return out.t
+
+    def forward_cached(self, images, newest, mask_ring, speed, command, dtype, training=False, taping=False):
+        """The eval-mode, untaped forward with the masks of the T - 1 older frames GIVEN: only ``newest`` (the last frame, NHWC
+        [B,H,W,16] in the compute dtype) goes through ``unet``; its mask is pushed into ``mask_ring`` [1,T,B,H,W,r16(classes)]
+        (slots 1..T-1 hold the older frames' masks on entry, oldest first), and the F roll-out steps, the backbone or bottleneck
+        and the heads run as in :meth:`forward`, on the same shapes.  ``images`` is the caller's frame ring [B,T,C,H,W]: geometry
+        only, no pixel of it is read.  Nothing but library launches on buffers the caller or this call owns: no strided slice, no
+        torch kernel (``prepare_cached`` filled the shadows), so a ``hip.LaunchRecorder`` sees all of it.
+        -> actions [B,2] (tanh), pred_speed [B,1]."""
+        Bsz = self._cached_begin(images, dtype, training, taping)
+        pu = self.pu
+        T, F_, nc = pu.n_past_frames, pu.n_future_frames, pu.num_classes
+        H, W = images.shape[-2:]
+        if tuple(newest.shape) != (Bsz, H, W, r16(pu.in_features)) or newest.dtype != dtype:
+            raise ValueError(f"forward_cached: newest must be {(Bsz, H, W, r16(pu.in_features))} {dtype}, got {tuple(newest.shape)}")
+        if tuple(mask_ring.shape) != (1, T, Bsz, H, W, r16(nc)) or mask_ring.dtype != dtype:
+            raise ValueError(f"forward_cached: mask_ring must be {(1, T, Bsz, H, W, r16(nc))} {dtype}, got {tuple(mask_ring.shape)}")
+        spd, cmd = self._measurement_inputs(speed, command)
+        kept = getattr(self, "debug_pass_out", None)
+        out = self._unet_fwd(self.unet, Var(newest))[0]
+        if kept is not None:
+            kept.append(out.t)
+        ops.history_push(mask_ring, out.t.unsqueeze(0))
+        masks = [Var(mask_ring[0, t]) for t in range(T)]
+        inter = None
+        for f in range(F_):
+            cat = Var(self._new(Bsz, H, W, r16(T * nc)))
+            self._cat_masks([m.t for m in masks[-T:]], cat.t, nc)
+            m, inter = self._unet_fwd(self.pred_unet, self._entry_fwd(cat))
+            if kept is not None:
+                kept.append(m.t)
+            masks.append(m)
+        x0 = None
+        if not self.return_inter:
+            x0 = Var(self._new(Bsz, H, W, self._x0_width(F_ * nc)))
+            self._cat_masks([m.t for m in masks[T:]], x0.t, nc)
+        self.training = False
+        actions, speeds = self._expert_tail(x0, inter, spd, cmd, Bsz)
+        self._tail = None
+        return actions, speeds
 
     def _tail_bwd(self, tail, dactions, dspeeds):
         head, sp, actions = tail

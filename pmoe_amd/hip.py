@@ -124,6 +124,8 @@ SIGNATURES = {
     "pmoe_action_loss": [_P, _P, _P, _P, _F, _F, _P, _P, _P, _I, _P],
     "pmoe_blend_fwd": [_P, _P, _P, _P, _P, _P, _P, _I, _P],
     "pmoe_blend_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P],
+    "pmoe_history_push": [_P, _P, _I, _I, _L, _I, _P, _I, _I, _I, _P],
+    "pmoe_mixture_draw": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P],
     "pmoe_maxpool2s2_bwd": [_P, _I, _I, _P, _P, _I, _I, _P, _I, _I, _I, _I, _I, _P],
     "pmoe_pixel_unshuffle2": [_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P],
     "pmoe_add_window": [_P, _I, _I, _P, _I, _I, _L, _I, _I, _P],

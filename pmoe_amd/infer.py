@@ -7,9 +7,13 @@ new inputs copied into the captured input buffers.  Parameters are read through 
 replay first compares the engine's build / pointer-table / version keys with those taken at capture and re-captures
 (:meth:`GraphedMixture.refresh`) when a weight, a BatchNorm buffer, the compute dtype or the device has changed since.
 """
+import types
+
 import torch
 
-from . import hip
+from . import hip, ops
+from .engine import r16
+from .model import moe as _moe
 from .model.moe import MixtureDistribution
 
 
@@ -19,9 +23,15 @@ def _plan_key(model):
     parameter's storage moves), their contents (parameter versions) and the eval-mode BatchNorm folds (buffer versions).
     A replay whose key differs from the one taken at capture would read freed or stale memory."""
     eng = model._engine()
-    bufs = [b for l in eng.all_bns for m in l.mods for b in (m.running_mean, m.running_var)]
-    return (eng._built_for, eng._ptr_key, eng._packed_version, sum(p._version for p in eng.flat_params),
-            sum(b._version for b in bufs), tuple(b.data_ptr() for b in bufs[:4]))
+    # (the PU-Net engines' padded BatchNorms keep their statistics outside all_bns, behind zero-padded shadows; their
+    #  ConvTranspose2d layers pack from a derived tensor with a version key of its own)
+    bns = list(eng.all_bns) + list(getattr(eng, "shadow_bns", ()))
+    bufs = [b for l in bns for m in l.mods for b in (m.running_mean, m.running_var)]
+    ups = tuple((up._derived_version, up.w_fwd.data_ptr() if up.w_fwd is not None else 0) for up in getattr(eng, "up_layers", ()))
+    shadows = tuple(t.data_ptr() for l in getattr(eng, "shadow_bns", ()) if l.shadow for t in l.shadow.values())
+    return (eng._built_for, eng.__dict__.get("_build_gen"), eng.__dict__.get("_ptr_key"), eng.__dict__.get("_packed_version"),
+            sum(p._version for p in eng.flat_params), sum(b._version for b in bufs), tuple(b.data_ptr() for b in bufs[:4]),
+            eng.__dict__.get("_punet_built_for"), eng.__dict__.get("_punet_build_gen"), ups, shadows)
 
 
 class GraphedMixture:
@@ -108,3 +118,190 @@ class PlannedMixture:
     def sample(self, images, speed, command):
         probs, mean, std, _ = self(images, speed, command)
         return MixtureDistribution(probs, mean, std).sample()
+
+
+class PolicyTick:
+    """The agent's loop (``autoagents/image_agent.py:127-177``) for EVERY model type ``get_model`` returns: the object keeps what
+    the agent keeps -- the last T frames, and for PU-Net models the masks ``unet`` made of them -- on the device, and
+    ``tick(frame, speed, command)`` -> actions ``[B,2]`` means ``model.sample(stack of the last T frames, speed, command)`` in
+    eval mode.  Per tick:
+
+    * one ``pmoe_history_push`` moves the frame ring ``[B,T,3,H,W]`` (what the mixture's stem reads) and writes the new frame
+      as the NHWC tensor ``unet`` takes;
+    * PU-Net models run ``PUNetEngine.forward_cached``: ONE ``unet`` pass (the newest frame; the other T - 1 masks are last
+      ticks' outputs, bit for bit, because eval-mode BatchNorm makes a mask a function of its frame alone), a second push for
+      the mask ring, then the F roll-out steps, backbone and heads;
+    * mixtures run ``mixture_params`` and ``pmoe_mixture_draw`` (device-side draw from a counter kept in device memory; for
+      ``PMoE`` the same launch blends the draw with the PU-Net expert's actions).
+
+    ``mode="eager"`` runs the engine's Python every tick; ``mode="plan"`` records these launches once (``hip.LaunchRecorder``,
+    private ``torch.cuda.MemPool``) and re-issues them through ctypes, all on one stream.  ``tick`` returns the object's own
+    output buffer (copy it to keep it across ticks); ``tick.last`` holds the deterministic tensors of the most recent tick:
+    ``probs, mean, std, speeds`` (mixtures), ``punet_actions, pred_speed`` (PU-Net models), ``raw`` (the draw), else None.
+    A weight / BatchNorm-buffer / compute-dtype / device change is noticed on the next tick (``_plan_key``): the plan is
+    re-recorded and all T masks are recomputed from the frame history."""
+
+    def __init__(self, model, batch=1, height=224, width=224, mode="plan", seed=0):
+        if mode not in ("eager", "plan"):
+            raise ValueError(f"PolicyTick: mode must be 'eager' or 'plan', got {mode!r}")
+        if model.training:
+            raise RuntimeError("PolicyTick runs the eval-mode chain: call model.eval() first")
+        if isinstance(model, _moe.PMoE):
+            self.moe, self.pun = model.moe, model.punet
+        elif isinstance(model, _moe.PUNetExpert):
+            self.moe, self.pun = None, model
+        elif hasattr(model, "mixture_params"):
+            self.moe, self.pun = model, None
+        else:
+            raise TypeError(f"PolicyTick: {type(model).__name__} is not a model type of get_model")
+        if batch < 1 or height < 1 or width < 1:
+            raise ValueError("PolicyTick: batch, height and width must be positive")
+        if self.pun is not None and (height % 16 or width % 16):
+            raise ValueError("PolicyTick: the U-Nets need a height and width divisible by 16")
+        self.model, self.mode = model, mode
+        self.B, self.H, self.W = int(batch), int(height), int(width)
+        main = self.moe if self.moe is not None else self.pun
+        eng = main._engine()
+        self.T = self.pun.punet.n_past_frames if self.pun is not None else eng.conv1.cin // 3
+        if self.moe is not None and self.moe._engine().conv1.cin != 3 * self.T:
+            raise ValueError("PolicyTick: the mixture and the PU-Net expert look at different numbers of past frames")
+        n_speed, n_cmd = eng.speed_enc["layers"][0].cin, eng.cmd_enc["layers"][0].cin
+        # ---- everything below touches the device
+        dev = next(model.parameters()).device
+        if dev.type != "cuda":
+            raise RuntimeError(f"PolicyTick: the model is on {dev}; pmoe_amd has no CPU path")
+        hip.load()
+        f32 = torch.float32
+        with torch.cuda.device(dev):
+            self.frames = torch.zeros(self.B, self.T, 3, self.H, self.W, dtype=f32, device=dev)
+            self.static_in = [torch.zeros(self.B, 3, self.H, self.W, dtype=f32, device=dev),
+                              torch.zeros(self.B, n_speed, dtype=f32, device=dev), torch.zeros(self.B, n_cmd, dtype=f32, device=dev)]
+            self.state = torch.zeros(2, dtype=torch.int64, device=dev)
+            self.raw = torch.zeros(self.B, 2, dtype=f32, device=dev)
+            self.out = torch.zeros(self.B, 2, dtype=f32, device=dev)
+        self.masks = self.newest = None
+        self.plan = self.pool = self.key = None
+        self.last = types.SimpleNamespace(probs=None, mean=None, std=None, speeds=None, punet_actions=None, pred_speed=None,
+                                          raw=None)
+        self.reseed(seed)
+        self.reset()
+
+    # ------------------------------------------------------------------ state
+    def _dtype(self, m):
+        return m.compute_dtype or _moe._DEFAULT_DTYPE
+
+    def _key(self):
+        """what a recorded tick (and, in either mode, the cached masks) depend on beyond this object's own buffers"""
+        key = []
+        for m in (self.pun, self.moe):
+            if m is not None:
+                key.append((self._dtype(m), bool(m.fp8_weights), _plan_key(m)))
+        if self.moe is not None and self.pun is not None:
+            key.append(tuple(p.data_ptr() for l in (self.model.lat_weights, self.model.long_weights) for p in (l.weight, l.bias)))
+        return tuple(key)
+
+    def reseed(self, seed):
+        """rewrite the device-resident draw state {seed, draws_done = 0}"""
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.state.copy_(torch.tensor([seed - (1 << 64) if seed >> 63 else seed, 0], dtype=torch.int64))
+
+    @property
+    def draws_done(self):
+        """the draw counter, read back from the device (synchronises)"""
+        return int(self.state[1].item())
+
+    def reset(self):
+        """start of an episode: T zero frames (image_agent.py:63-64); PU-Net models: ``unet(0)`` once, in every mask slot"""
+        self.frames.zero_()
+        if self.key is None or self._key() != self.key:
+            self.refresh()
+        elif self.pun is not None:
+            with torch.no_grad():
+                self.newest.zero_()
+                m = self.pun._engine().mask_of(self.frames, self.newest, self._dtype(self.pun))
+                for t in range(self.T):
+                    self.masks[0, t].copy_(m)
+
+    def refresh(self):
+        """(re)build: packs and shadows, ALL T masks from the frame history (masks of other weights are stale), and in plan mode
+        the recording.  Runs by itself when the engines' plan key has changed."""
+        dev = next(self.model.parameters()).device
+        if dev != self.frames.device:            # the model moved: this object's buffers follow it
+            self.frames, self.state, self.raw, self.out = (t.to(dev) for t in (self.frames, self.state, self.raw, self.out))
+            self.static_in = [t.to(dev) for t in self.static_in]
+            self.masks = self.newest = None
+        with torch.no_grad(), torch.cuda.device(dev):
+            if self.pun is not None:
+                eng, dtype = self.pun._engine(), self._dtype(self.pun)
+                eng.fp8 = bool(self.pun.fp8_weights) and dtype == torch.bfloat16
+                pu = self.pun.punet
+                if self.masks is None or self.masks.dtype != dtype:
+                    self.masks = torch.zeros(1, self.T, self.B, self.H, self.W, r16(pu.num_classes), dtype=dtype, device=dev)
+                    self.newest = torch.zeros(self.B, self.H, self.W, r16(pu.in_features), dtype=dtype, device=dev)
+                eng.prepare_cached(self.frames, dtype)
+                for t in range(self.T):
+                    ops.nchw_to_nhwc(self.frames[:, t].contiguous(), self.newest)
+                    self.masks[0, t].copy_(eng.mask_of(self.frames, self.newest, dtype))
+            if self.moe is not None:             # banks, pointer tables and packs of the mixture: what its half of the key reads
+                eng, dtype = self.moe._engine(), self._dtype(self.moe)
+                eng.fp8 = bool(self.moe.fp8_weights) and dtype == torch.bfloat16
+                eng._begin(self.frames, False, False, dtype, 0)
+                eng.tape = None
+            self.plan = self.pool = None
+            if self.mode == "plan":
+                # the recorded run (and its warm-up, which packs weights and folds BatchNorms: cached on the parameters' versions)
+                # moves the rings and the draw counter like any tick: put them back afterwards
+                saved = [t.clone() for t in (self.frames, self.state) + ((self.masks,) if self.masks is not None else ())]
+                for _ in range(2):
+                    self._body()
+                self.pool = torch.cuda.MemPool()
+                with torch.cuda.use_mem_pool(self.pool), hip.LaunchRecorder() as plan:
+                    self._result = self._body()
+                self.plan = plan
+                for dst, src in zip((self.frames, self.state, self.masks), saved):
+                    dst.copy_(src)
+            self.key = self._key()
+
+    # ------------------------------------------------------------------ one tick
+    def _body(self):
+        """the launches of one tick, in order: frame push, PU-Net expert (its mask push inside), mixture, draw (+ blend)"""
+        frame, speed, command = self.static_in
+        res = dict(probs=None, mean=None, std=None, speeds=None, punet_actions=None, pred_speed=None, raw=None)
+        ops.history_push(self.frames, frame, nhwc=self.newest)
+        if self.pun is not None:
+            eng, dtype = self.pun._engine(), self._dtype(self.pun)
+            eng.fp8 = bool(self.pun.fp8_weights) and dtype == torch.bfloat16
+            res["punet_actions"], res["pred_speed"] = eng.forward_cached(self.frames, self.newest, self.masks, speed, command, dtype)
+            actions = res["punet_actions"]
+        if self.moe is not None:
+            res["probs"], res["mean"], res["std"], res["speeds"] = self.moe.mixture_params(self.frames, speed, command)
+            blend = None
+            if self.pun is not None:
+                m = self.model
+                blend = (m.lat_weights.weight, m.lat_weights.bias, m.long_weights.weight, m.long_weights.bias)
+            ops.mixture_draw(res["probs"], res["mean"], res["std"], self.state, self.raw, res["punet_actions"], blend,
+                             self.out if blend is not None else None)
+            res["raw"] = self.raw
+            actions = self.out if blend is not None else self.raw
+        return actions, res
+
+    def tick(self, frame, speed, command):
+        """frame f32 [B,3,H,W] (contiguous, on the device), speed [B,1], command [B,n_commands] -> actions [B,2] f32"""
+        if self.model.training:
+            raise RuntimeError("PolicyTick runs the eval-mode chain: call model.eval() first")
+        for dst, src, name in zip(self.static_in, (frame, speed, command), ("frame", "speed", "command")):
+            if tuple(dst.shape) != tuple(src.shape):
+                raise ValueError(f"PolicyTick: {name} must be {tuple(dst.shape)}, got {tuple(src.shape)}")
+            dst.copy_(src)
+        if self._key() != self.key:              # weights / buffers / dtype / device changed: cached masks and the plan are stale
+            self.refresh()
+        with torch.no_grad():
+            if self.plan is not None:
+                self.plan.replay()
+                actions, res = self._result
+            else:
+                actions, res = self._body()
+        self.last = types.SimpleNamespace(**res)
+        return actions
+
+    __call__ = tick

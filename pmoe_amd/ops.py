@@ -751,7 +751,52 @@ def blend_bwd(moe_act, pu_act, lat_w, long_w, out, dout, dlat_w, dlat_b, dlong_w
                                 stream_ptr()), "pmoe_blend_bwd")
 
 
+def history_push(ring, item, nhwc=None):
+    """In-place history ring (pmoe_amd/infer.py:PolicyTick): ``ring`` [B,T,...] loses slot 0, slots 1..T-1 move down and
+    ``item`` [B,...] becomes slot T-1.  ``nhwc`` [B,H,W,Cp] (bf16 / f32; the ring is then f32 [B,T,C,H,W]): the launch also
+    writes the new item in that layout, zero padded -- what ``nchw_to_nhwc(item, nhwc)`` gives, bit for bit."""
+    if ring.dim() < 3 or tuple(item.shape) != (ring.shape[0],) + tuple(ring.shape[2:]) or item.dtype != ring.dtype:
+        raise ValueError(f"history_push: ring [B,T,...] {tuple(ring.shape)} / {ring.dtype} takes items [B,...] of its dtype, got "
+                         f"{tuple(item.shape)} / {item.dtype}")
+    b, t = ring.shape[0], ring.shape[1]
+    length = item.numel() // b
+    c = cp = nd = 0
+    if nhwc is not None:
+        if ring.dim() != 5 or ring.dtype != torch.float32:
+            raise ValueError("history_push: the NHWC copy needs an f32 ring [B,T,C,H,W]")
+        c, cp, nd = ring.shape[2], nhwc.shape[-1], dt(nhwc)
+        if tuple(nhwc.shape) != (b,) + tuple(ring.shape[3:]) + (cp,) or cp < c or (cp * nhwc.element_size()) % 16:
+            raise ValueError(f"history_push: nhwc must be [{b},{ring.shape[3]},{ring.shape[4]},Cp >= {c}] in whole 16-byte "
+                             f"vectors, got {tuple(nhwc.shape)}")
+    check(load().pmoe_history_push(ptr(ring, "ring"), ptr(item, "item"), b, t, length, dt(ring), ptr(nhwc, "nhwc"), c, cp, nd,
+                                   stream_ptr()), "pmoe_history_push")
+
+
+def mixture_draw(probs, mean, std, state, raw, punet_actions=None, blend=None, out=None):
+    """One draw per row of the mixture (probs [B,E], mean / std [B,E,2], f32) into ``raw`` [B,2]; ``state`` is the int64 [2]
+    device tensor {seed, draws_done}, whose counter the launch advances.  ``punet_actions`` [B,2] with ``blend`` = (lat_w, lat_b,
+    long_w, long_b): ``out`` [B,2] also receives the PMoE blend of the draw (bit-identical to ``blend_fwd`` on ``raw``)."""
+    f32 = torch.float32
+    b, e = probs.shape
+    if tuple(mean.shape) != (b, e, 2) or tuple(std.shape) != (b, e, 2) or tuple(raw.shape) != (b, 2):
+        raise ValueError(f"mixture_draw: probs [B,E] = {tuple(probs.shape)} needs mean / std [B,E,2] and raw [B,2]")
+    if state.dtype != torch.int64 or state.numel() != 2:
+        raise ValueError("mixture_draw: state is an int64 tensor of two words {seed, draws_done}")
+    extra = [None] * 6
+    if punet_actions is not None:
+        if blend is None or out is None or tuple(punet_actions.shape) != (b, 2) or tuple(out.shape) != (b, 2):
+            raise ValueError("mixture_draw: the blend needs punet_actions [B,2], the four Linear(2,1) tensors and out [B,2]")
+        lat_w, lat_b, long_w, long_b = blend
+        if lat_w.numel() != 2 or long_w.numel() != 2 or lat_b.numel() != 1 or long_b.numel() != 1:
+            raise ValueError("mixture_draw: blend = (lat_w [1,2], lat_b [1], long_w [1,2], long_b [1])")
+        extra = [ptr(punet_actions, "punet_actions", f32), ptr(lat_w, "lat_w", f32), ptr(lat_b, "lat_b", f32),
+                 ptr(long_w, "long_w", f32), ptr(long_b, "long_b", f32), ptr(out, "out", f32)]
+    check(load().pmoe_mixture_draw(ptr(probs, "probs", f32), ptr(mean, "mean", f32), ptr(std, "std", f32),
+                                   ptr(state, "state", torch.int64), ptr(raw, "raw", f32), *extra, b, e, stream_ptr()),
+          "pmoe_mixture_draw")
+
+
 for _n in ("maxpool2_fwd", "pixel_shuffle2", "copy_window", "action_head_fwd", "action_head_bwd", "action_loss",
            "blend_fwd", "blend_bwd", "maxpool2_bwd", "pixel_unshuffle2", "add_window", "nhwc_to_nchw", "seg_loss_fwd",
-           "seg_loss_bwd", "cat_windows", "dice_score", "dropout2d_table", "channel_scale"):
+           "seg_loss_bwd", "cat_windows", "dice_score", "dropout2d_table", "channel_scale", "history_push", "mixture_draw"):
     globals()[_n] = _timed(globals()[_n])
