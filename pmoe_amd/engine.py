@@ -225,7 +225,8 @@ class ExpertGroupEngine:
         self.dp_enabled = False       # set by pmoe_amd.parallel-aware callers (bench.py, enable_data_parallel)
         self.dp_buckets = 6
         self.dp_always = False        # issue the collectives even in a one-rank group (RCCL path on a single GPU)
-        self._built_for = None
+        self._built_for = self._ptr_key = self._packed_version = None
+        self._build_gen = 0           # counts re-allocations of the packed banks: recorded pointers into the old ones are stale
         self._seed_counter = itertools.count(1)
         self.fuse_conv_stats = True
         self.fuse_stem_tail = True
@@ -388,7 +389,7 @@ class ExpertGroupEngine:
         self._ptr_key = None
         self._packed_version = None
         self._built_for = key
-        self._build_gen = self.__dict__.get("_build_gen", 0) + 1      # (pmoe_amd/infer.py: recorded pointers into the old banks are stale)
+        self._build_gen += 1
 
     def _refresh_tables(self, dev):
         """One int64 device table of all parameter/buffer pointers (rebuilt only when storage moved)."""
@@ -432,6 +433,15 @@ class ExpertGroupEngine:
         for layer in self.all_convs:
             layer.pack()
         self._packed_version = ver
+
+    def replay_key(self, extra_bns=()):
+        """Everything a captured / recorded chain (pmoe_amd/infer.py) holds raw pointers into, beyond its private activation pool:
+        the packed weight banks and pointer tables (rebuilt when the compute dtype, the fp8 switch or the device changes, or when a
+        parameter's storage moves), their contents (parameter versions) and the eval-mode BatchNorm folds (buffer versions).
+        A replay whose key differs from the one taken at capture would read freed or stale memory."""
+        bufs = [b for l in list(self.all_bns) + list(extra_bns) for m in l.mods for b in (m.running_mean, m.running_var)]
+        return (self._built_for, self._build_gen, self._ptr_key, self._packed_version, sum(p._version for p in self.flat_params),
+                sum(b._version for b in bufs), tuple(b.data_ptr() for b in bufs[:4]))
 
     # ------------------------------------------------------------------ primitive ops (forward + tape)
     def _new(self, n, h, w, c, dtype=None):
@@ -1099,7 +1109,13 @@ class ExpertGroupEngine:
         self._pack_all()
         self.tape, self._bn_touched = [], []
         self._seed_counter = itertools.count(1)       # dropout masks are a function of (base_seed, layer order)
+        return Bsz
 
+    def prepare(self, images, dtype):
+        """What an eval-mode, untaped call on inputs shaped like ``images`` sets up before its first launch: banks, pointer tables
+        and packs (what ``replay_key`` reads).  -> batch size"""
+        Bsz = self._begin(images, False, False, dtype, 0)
+        self.tape = None
         return Bsz
 
     def forward(self, images, speed, command, training, taping, dtype, base_seed=0):

@@ -12,6 +12,7 @@ Built from the same primitive launches as :class:`pmoe_amd.engine.ExpertGroupEng
   the skip-concatenation buffer; ``torch.cat`` / ``view`` of 23-class masks are ``pmoe_copy_window`` launches.
 """
 import os
+import types
 
 import torch
 
@@ -56,8 +57,18 @@ class _UpConv(GroupedConv):
 class PUNetEngine(ExpertGroupEngine):
     _punet_trains = False
 
-    def __init__(self, expert):
-        self.return_inter = expert.return_inter
+    def __init__(self, expert, return_inter=None):
+        self.return_inter = expert.return_inter if return_inter is None else return_inter
+        self._punet_built_for, self._punet_build_gen = None, 0
+        # tests/punet_parity.py (per-pass teacher forcing): ``debug_pass_out`` (a list) collects the mask tensor every U-Net
+        # pass wrote; ``debug_forced_masks`` (T + F tensors [B,classes,H,W]) REPLACES each pass's output by the given mask
+        # before the later passes read it, so that every pass runs on the checker's inputs and errors do not compound
+        self.debug_pass_out = self.debug_forced_masks = None
+        # (teacher forcing): ``debug_x0``, the predicted masks [B,F,classes,H,W], GIVEN: the frozen PU-Net is skipped -- the
+        # trainable half (138-channel stem, ResNet, heads) is then compared on identical inputs, without the chained train-mode
+        # U-Nets' sensitivity in the loop.  ``debug_keep_x0``: forward leaves the backbone's input tensor in ``debug_x0_kept``
+        self.debug_x0 = self.debug_x0_kept = None
+        self.debug_keep_x0 = False
         super().__init__([expert], alt=False)
 
     # ------------------------------------------------------------------ structure
@@ -167,18 +178,25 @@ class PUNetEngine(ExpertGroupEngine):
         #  call, the fresh shadow tensors changed the pointer table, and all 79 weight packs of a PUNetExpert were redone every step:
         #  1.2 ms of pack launches + the derived ConvTranspose2d packs per step until round 4)
         key = (str(dev), dtype)
-        if self.__dict__.get("_punet_built_for") != key:
+        if self._punet_built_for != key:
             for up in self.up_layers:
                 up.alloc(dtype, dev)
                 up._derived_version = None
             for l in self.shadow_bns:
                 l.shadow = {k: torch.zeros(l.C, dtype=F32, device=dev) for k in ("gamma", "beta", "rm", "rv")}
             self._punet_built_for = key
-            self._punet_build_gen = self.__dict__.get("_punet_build_gen", 0) + 1
+            self._punet_build_gen += 1
         super()._ensure_built(dev, dtype)
 
     def _extra_tables(self):
         return [(self._key(kind, l), [l.shadow[kind]]) for l in self.shadow_bns for kind in ("gamma", "beta", "rm", "rv")]
+
+    def replay_key(self):
+        """+ what the base engine does not own: the padded BatchNorms keep their statistics outside all_bns, behind zero-padded
+        shadows; the ConvTranspose2d layers pack from a derived tensor with a version key of its own."""
+        ups = tuple((up._derived_version, up.w_fwd.data_ptr() if up.w_fwd is not None else 0) for up in self.up_layers)
+        shadows = tuple(t.data_ptr() for l in self.shadow_bns if l.shadow for t in l.shadow.values())
+        return super().replay_key(self.shadow_bns) + (self._punet_built_for, self._punet_build_gen, ups, shadows)
 
     def _pack_all(self):
         for up in self.up_layers:
@@ -328,7 +346,7 @@ class PUNetEngine(ExpertGroupEngine):
             hh, ww = hh // 2, ww // 2
         # round 4 (late): the last BatchNorm + ReLU of a block whose one consumer is a 1x1 layer (the transposed convolutions, the
         # final classifier) stays pending on its pre-activation and is applied on load by that launch (untaped forward: _last_bn)
-        lazy = self.fuse_in_bn_1x1 and not self.taping and not getattr(self, "return_inter", False)
+        lazy = self.fuse_in_bn_1x1 and not self.taping and not self.return_inter
         x5 = h = self._conv3(h, U["dwn"][4], defer=lazy)
         for j in range(4):
             cat, up = cats[3 - j], U["up"][j]
@@ -412,30 +430,34 @@ class PUNetEngine(ExpertGroupEngine):
         if pu.n_future_frames == 0 and not self._punet_trains:
             raise NotImplementedError("PUNetExpert needs future_frames > 0 (moe.py:286-289 sizes its stem from it)")
         H, W = images.shape[-2:]
-        nc, cpad = pu.num_classes, r16(pu.in_features)
+        cpad = r16(pu.in_features)
         masks = []
-        # tests/punet_parity.py (per-pass teacher forcing): ``debug_pass_out`` (a list) collects the mask tensor every U-Net
-        # pass wrote; ``debug_forced_masks`` (T + F tensors [B,classes,H,W]) REPLACES each pass's output by the given mask
-        # before the later passes read it, so that every pass runs on the checker's inputs and errors do not compound
-        kept, forced = getattr(self, "debug_pass_out", None), getattr(self, "debug_forced_masks", None)
-
-        def _pass_done(out):
-            if kept is not None:
-                kept.append(out.t)
-            if forced is None:
-                return out
-            given = Var(torch.empty_like(out.t))
-            ops.nchw_to_nhwc(forced[len(masks)].to(self.dev).contiguous().float(), given.t)
-            return given
         for i in range(T):
             xi = Var(self._new(Bsz, H, W, cpad))
             ops.nchw_to_nhwc(images[:, i].contiguous().float(), xi.t)
-            out = self._unet_fwd(self.unet, xi)[0]
-            masks.append(_pass_done(out))
-        F_ = pu.n_future_frames
-        if F_ == 0:                                    # punet.py:91-96: segmentation of the current frame
+            masks.append(self._pass_done(self._unet_fwd(self.unet, xi)[0], i))
+        if pu.n_future_frames == 0:                    # punet.py:91-96: segmentation of the current frame
             self._pred_masks = None
             return masks[-1], None
+        return self._rollout(masks)
+
+    def _pass_done(self, out, index):
+        """a U-Net pass (number ``index`` of the T + F of a forward) has written ``out``: the debug hooks see it, and may replace it"""
+        if self.debug_pass_out is not None:
+            self.debug_pass_out.append(out.t)
+        if self.debug_forced_masks is None:
+            return out
+        given = Var(torch.empty_like(out.t))
+        ops.nchw_to_nhwc(self.debug_forced_masks[index].to(self.dev).contiguous().float(), given.t)
+        return given
+
+    def _rollout(self, masks):
+        """punet.py:98-120: the F autoregressive steps cat(last T masks) -> entry_block -> pred_unet on top of the T ``masks`` of the
+        past frames (Vars [B,H,W,r16(classes)]; the list grows by the predicted ones), then the backbone's input x0
+        [B,H,W,width(F*classes)].  -> x0 (None with ``return_inter``), the last step's bottleneck"""
+        pu = self.pu
+        T, F_, nc = pu.n_past_frames, pu.n_future_frames, pu.num_classes
+        Bsz, H, W, _ = masks[0].t.shape
         inter = None
         for f in range(F_):
             if self.taping:
@@ -454,10 +476,9 @@ class PUNetEngine(ExpertGroupEngine):
                         if m.needs_grad:
                             ops.add_window(cat.grad, k * nc, m.grad, 0, nc)
                 self.tape.append(cat_bwd)
-            e = self._entry_fwd(cat)
-            m, inter = self._unet_fwd(self.pred_unet, e)
+            m, inter = self._unet_fwd(self.pred_unet, self._entry_fwd(cat))
             if not self.taping:
-                m = _pass_done(m)
+                m = self._pass_done(m, len(masks))
             masks.append(m)
         x0 = None
         if not self.return_inter:                  # torch.stack(outs,1).view(B,-1,H,W)  (punet.py:120, moe.py:311)
@@ -482,10 +503,7 @@ class PUNetEngine(ExpertGroupEngine):
         top_training = training
         spd, cmd = self._measurement_inputs(speed, command)
         taping_saved, self.taping = self.taping, False          # nothing inside the frozen PU-Net is taped
-        if getattr(self, "debug_x0", None) is not None and not self.return_inter:
-            # tests/punet_parity.py (teacher forcing): the predicted masks [B,F,classes,H,W] are GIVEN, the frozen PU-Net is
-            # skipped -- the trainable half (138-channel stem, ResNet, heads) is then compared on identical inputs, without
-            # the chained train-mode U-Nets' sensitivity in the loop
+        if self.debug_x0 is not None and not self.return_inter:
             mk = self.debug_x0
             Hm, Wm = mk.shape[-2:]
             x0 = Var(self._new(Bsz, Hm, Wm, self._x0_width(mk.shape[1] * mk.shape[2])))
@@ -493,7 +511,7 @@ class PUNetEngine(ExpertGroupEngine):
             inter = None
         else:
             x0, inter = self._punet_fwd(images)
-        if getattr(self, "debug_keep_x0", False):
+        if self.debug_keep_x0:
             self.debug_x0_kept = x0.t if x0 is not None else None
         self.taping = taping_saved
         self.training = top_training
@@ -530,32 +548,28 @@ class PUNetEngine(ExpertGroupEngine):
     def _cached_begin(self, images, dtype, training=False, taping=False):
         if training or taping or any(getattr(m, "training", False) for m in (self.experts[0], self.pu)):
             raise RuntimeError("PUNetEngine: the cached-mask forward is the eval-mode, untaped chain: call model.eval() first")
-        if getattr(self, "debug_forced_masks", None) is not None or getattr(self, "debug_x0", None) is not None:
+        if self.debug_forced_masks is not None or self.debug_x0 is not None:
             raise RuntimeError("PUNetEngine: debug_forced_masks / debug_x0 replace U-Net passes of the FULL forward and do not "
                                "combine with cached masks")
         if images.shape[1] != self.pu.n_past_frames:
             raise AssertionError("Number of images should match number of past frames")      # punet.py:84-86
         if self.pu.n_future_frames == 0:
             raise NotImplementedError("PUNetExpert needs future_frames > 0 (moe.py:286-289 sizes its stem from it)")
-        Bsz = self._begin(images, False, False, dtype, 0)
-        self.tape = None
-        return Bsz
+        return super().prepare(images, dtype)
 
-    def prepare_cached(self, images, dtype):
+    def prepare(self, images, dtype):
         """What the cached route keeps OUT of the tick: packs, pointer tables and the padded-BatchNorm shadows (torch copies;
         constant in eval mode).  Called when a PolicyTick is built or refreshed; ``images`` is its frame ring [B,T,C,H,W]."""
         self._cached_begin(images, dtype)
         self._shadows_in()
 
+    prepare_cached = prepare
+
     def mask_of(self, images, frame, dtype):
         """``unet`` over ONE frame given as NHWC [B,H,W,16] in the compute dtype -> its mask tensor [B,H,W,r16(classes)]: the pass
         the full forward runs per frame (eval mode: it depends on that frame alone)."""
         self._cached_begin(images, dtype)
-        out = self._unet_fwd(self.unet, Var(frame))[0]
-        kept = getattr(self, "debug_pass_out", None)
-        if kept is not None:
-            kept.append(out.t)
-        return out.t
+        return self._pass_done(self._unet_fwd(self.unet, Var(frame))[0], 0).t
 
     def forward_cached(self, images, newest, mask_ring, speed, command, dtype, training=False, taping=False):
         """The eval-mode, untaped forward with the masks of the T - 1 older frames GIVEN: only ``newest`` (the last frame, NHWC
@@ -567,31 +581,16 @@ class PUNetEngine(ExpertGroupEngine):
         -> actions [B,2] (tanh), pred_speed [B,1]."""
         Bsz = self._cached_begin(images, dtype, training, taping)
         pu = self.pu
-        T, F_, nc = pu.n_past_frames, pu.n_future_frames, pu.num_classes
+        T, nc = pu.n_past_frames, pu.num_classes
         H, W = images.shape[-2:]
         if tuple(newest.shape) != (Bsz, H, W, r16(pu.in_features)) or newest.dtype != dtype:
             raise ValueError(f"forward_cached: newest must be {(Bsz, H, W, r16(pu.in_features))} {dtype}, got {tuple(newest.shape)}")
         if tuple(mask_ring.shape) != (1, T, Bsz, H, W, r16(nc)) or mask_ring.dtype != dtype:
             raise ValueError(f"forward_cached: mask_ring must be {(1, T, Bsz, H, W, r16(nc))} {dtype}, got {tuple(mask_ring.shape)}")
         spd, cmd = self._measurement_inputs(speed, command)
-        kept = getattr(self, "debug_pass_out", None)
-        out = self._unet_fwd(self.unet, Var(newest))[0]
-        if kept is not None:
-            kept.append(out.t)
+        out = self._pass_done(self._unet_fwd(self.unet, Var(newest))[0], T - 1)
         ops.history_push(mask_ring, out.t.unsqueeze(0))
-        masks = [Var(mask_ring[0, t]) for t in range(T)]
-        inter = None
-        for f in range(F_):
-            cat = Var(self._new(Bsz, H, W, r16(T * nc)))
-            self._cat_masks([m.t for m in masks[-T:]], cat.t, nc)
-            m, inter = self._unet_fwd(self.pred_unet, self._entry_fwd(cat))
-            if kept is not None:
-                kept.append(m.t)
-            masks.append(m)
-        x0 = None
-        if not self.return_inter:
-            x0 = Var(self._new(Bsz, H, W, self._x0_width(F_ * nc)))
-            self._cat_masks([m.t for m in masks[T:]], x0.t, nc)
+        x0, inter = self._rollout([Var(mask_ring[0, t]) for t in range(T)])
         self.training = False
         actions, speeds = self._expert_tail(x0, inter, spd, cmd, Bsz)
         self._tail = None
@@ -624,9 +623,7 @@ class PredictiveUnetEngine(PUNetEngine):
     _punet_trains = True
 
     def __init__(self, punet):
-        import types
-        self.return_inter = bool(punet.inter_repr)
-        ExpertGroupEngine.__init__(self, [types.SimpleNamespace(punet=punet)], alt=False)
+        super().__init__(types.SimpleNamespace(punet=punet), bool(punet.inter_repr))
 
     def _collect_network(self, ex):
         self._collect_pre_backbone(ex)
@@ -722,10 +719,8 @@ class UNetEngine(PUNetEngine):
     _punet_trains = True
 
     def __init__(self, unet):
-        import types
-        self.return_inter = bool(unet.inter_repr)
         self.debug_drop_tables = []        # the [N,C] scale table of every Dropout2d site of the LAST forward (tests replay them)
-        ExpertGroupEngine.__init__(self, [types.SimpleNamespace(unet=unet)], alt=False)
+        super().__init__(types.SimpleNamespace(unet=unet), bool(unet.inter_repr))
 
     def _collect_network(self, ex):
         self.pu = None
@@ -778,8 +773,9 @@ class UNetEngine(PUNetEngine):
         self.tape = None
         return logits, inter, state
 
-    def _tail_bwd(self, out, dout):
-        """d loss / d logits [B,classes,H,W] f32 -> the gradient of the classifier's NHWC output (zero padded)."""
+    def _tail_bwd(self, out, dout, dinter=None):
+        """d loss / d logits [B,classes,H,W] f32 -> the gradient of the classifier's NHWC output (zero padded).  (``dinter``: the
+        bottleneck output is inference-only and takes none.)"""
         if dout is None:
             return
         g = torch.empty_like(out.t)

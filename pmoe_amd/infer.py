@@ -17,107 +17,97 @@ from .model import moe as _moe
 from .model.moe import MixtureDistribution
 
 
-def _plan_key(model):
-    """Everything a captured / recorded chain holds raw pointers into, beyond its private activation pool: the engine's
-    packed weight banks and pointer tables (rebuilt when the compute dtype, the fp8 switch or the device changes, or when a
-    parameter's storage moves), their contents (parameter versions) and the eval-mode BatchNorm folds (buffer versions).
-    A replay whose key differs from the one taken at capture would read freed or stale memory."""
-    eng = model._engine()
-    # (the PU-Net engines' padded BatchNorms keep their statistics outside all_bns, behind zero-padded shadows; their
-    #  ConvTranspose2d layers pack from a derived tensor with a version key of its own)
-    bns = list(eng.all_bns) + list(getattr(eng, "shadow_bns", ()))
-    bufs = [b for l in bns for m in l.mods for b in (m.running_mean, m.running_var)]
-    ups = tuple((up._derived_version, up.w_fwd.data_ptr() if up.w_fwd is not None else 0) for up in getattr(eng, "up_layers", ()))
-    shadows = tuple(t.data_ptr() for l in getattr(eng, "shadow_bns", ()) if l.shadow for t in l.shadow.values())
-    return (eng._built_for, eng.__dict__.get("_build_gen"), eng.__dict__.get("_ptr_key"), eng.__dict__.get("_packed_version"),
-            sum(p._version for p in eng.flat_params), sum(b._version for b in bufs), tuple(b.data_ptr() for b in bufs[:4]),
-            eng.__dict__.get("_punet_built_for"), eng.__dict__.get("_punet_build_gen"), ups, shadows)
+class _RecordedChain:
+    """``fn()`` -- an eval-mode launch chain on fixed buffers -- warmed up twice (packs weights, builds pointer tables: cached on the
+    parameters' versions), then run once more and kept: captured into a HIP graph (``graph=True``; warm-up on a side stream, as
+    capture asks), or recorded launch by launch (``hip.LaunchRecorder``) while allocating from a private ``torch.cuda.MemPool``
+    that lives as long as this object, so every recorded pointer stays valid and nothing else is handed that memory.
+    ``replay()`` issues the chain again (a plan: on the stream it was recorded on) and returns what ``fn`` returned."""
+
+    def __init__(self, fn, graph=False):
+        self.pool = None
+        with torch.no_grad():
+            if graph:
+                side = torch.cuda.Stream()
+                side.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(side):
+                    for _ in range(2):
+                        fn()
+                torch.cuda.current_stream().wait_stream(side)
+                self.runner = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(self.runner):
+                    self.result = fn()
+            else:
+                for _ in range(2):
+                    fn()
+                self.pool = torch.cuda.MemPool()
+                with torch.cuda.use_mem_pool(self.pool), hip.LaunchRecorder() as self.runner:
+                    self.result = fn()
+
+    def replay(self):
+        self.runner.replay()
+        return self.result
 
 
-class GraphedMixture:
-    """``gm = GraphedMixture(model, images, speed, command)`` captures ``model.mixture_params`` for inputs of that shape;
-    ``gm(images, speed, command)`` -> (probs, mean, std, speeds) and ``gm.sample(...)`` -> actions ``[B,2]`` replay it."""
+class _StaticMixture:
+    """``model.mixture_params`` for inputs of one shape, kept as a :class:`_RecordedChain` and replayed per tick with the new inputs
+    copied into the chain's input buffers.  Every call first compares the engine's ``replay_key()`` with the one taken when the
+    chain was made and makes it again (:meth:`refresh`) when a weight, a BatchNorm buffer, the compute dtype or the device has
+    changed since, or an eager call in between re-packed or re-allocated what the chain points to."""
+    _graph, _verb, _done = False, "records", "recorded"
 
     def __init__(self, model, images, speed, command):
         if model.training:
-            raise RuntimeError("GraphedMixture captures the eval-mode chain: call model.eval() first")
+            raise RuntimeError(f"{type(self).__name__} {self._verb} the eval-mode chain: call model.eval() first")
+        self._check_inputs(images, speed, command)
         self.model = model
         self.static_in = [images.clone(), speed.clone(), command.clone()]
         self.refresh()
 
+    def _check_inputs(self, *inputs):
+        pass
+
     def refresh(self):
-        """(re)capture -- after load_state_dict / parameter updates."""
-        model = self.model
-        with torch.no_grad():
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(2):                       # warm-up on the capture stream: packs weights, builds pointer tables
-                    model.mixture_params(*self.static_in)
-            torch.cuda.current_stream().wait_stream(side)
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
-                self.static_out = model.mixture_params(*self.static_in)
-        self.key = _plan_key(model)
+        """(re)capture / (re)record -- after load_state_dict / parameter updates."""
+        self.chain = _RecordedChain(lambda: self.model.mixture_params(*self.static_in), self._graph)
+        self.static_out = self.chain.result
+        self.key = self.model._engine().replay_key()
 
     def __call__(self, images, speed, command):
         for dst, src in zip(self.static_in, (images, speed, command)):
             if dst.shape != src.shape:
-                raise ValueError(f"GraphedMixture was captured for input shape {tuple(dst.shape)}, got {tuple(src.shape)}")
+                raise ValueError(f"{type(self).__name__} was {self._done} for input shape {tuple(dst.shape)}, got {tuple(src.shape)}")
             dst.copy_(src)
-        if _plan_key(self.model) != self.key:            # weights / buffers / dtype / device changed since the capture
+        if self.model._engine().replay_key() != self.key:
             self.refresh()
-        self.graph.replay()
-        return self.static_out
+        return self.chain.replay()
 
     def sample(self, images, speed, command):
         probs, mean, std, _ = self(images, speed, command)
         return MixtureDistribution(probs, mean, std).sample()
 
 
-class PlannedMixture:
+class GraphedMixture(_StaticMixture):
+    """``gm = GraphedMixture(model, images, speed, command)`` captures ``model.mixture_params`` for inputs of that shape;
+    ``gm(images, speed, command)`` -> (probs, mean, std, speeds) and ``gm.sample(...)`` -> actions ``[B,2]`` replay it."""
+    _graph, _verb, _done = True, "captures", "captured"
+    graph = property(lambda self: self.chain.runner)
+
+
+class PlannedMixture(_StaticMixture):
     """The same tick WITHOUT graph capture: the launches of one eval-mode ``model.mixture_params`` call are recorded once
     (``hip.LaunchRecorder``: C-ABI function + its converted arguments, descriptors included) and re-issued per tick straight
     through ctypes -- none of the engine's Python (shape logic, descriptor filling, allocation, pointer validation) runs
-    again.  The recorded run allocates from a private ``torch.cuda.MemPool`` that lives as long as the plan, so every
-    recorded pointer stays valid and nothing else is handed that memory.  Same contract as :class:`GraphedMixture`: fixed
-    input shapes, ``refresh()`` after a weight change, replay on the stream the plan was recorded on.  Inputs must already be
-    float32 and contiguous (then the chain contains no torch kernel, only library launches)."""
+    again.  Same contract as :class:`GraphedMixture`: fixed input shapes, ``refresh()`` after a weight change, replay on the
+    stream the plan was recorded on.  Inputs must already be float32 and contiguous (then the chain contains no torch kernel,
+    only library launches)."""
+    plan = property(lambda self: self.chain.runner)
+    pool = property(lambda self: self.chain.pool)
 
-    def __init__(self, model, images, speed, command):
-        if model.training:
-            raise RuntimeError("PlannedMixture records the eval-mode chain: call model.eval() first")
-        for t in (images, speed, command):
+    def _check_inputs(self, *inputs):
+        for t in inputs:
             if t.dtype != torch.float32 or not t.is_contiguous():
                 raise ValueError("PlannedMixture: inputs must be contiguous float32 tensors")
-        self.model = model
-        self.static_in = [images.clone(), speed.clone(), command.clone()]
-        self.refresh()
-
-    def refresh(self):
-        model = self.model
-        with torch.no_grad():
-            for _ in range(2):                           # packs weights, builds pointer tables (cached on the parameters' versions)
-                model.mixture_params(*self.static_in)
-            self.pool = torch.cuda.MemPool()
-            with torch.cuda.use_mem_pool(self.pool), hip.LaunchRecorder() as plan:
-                self.static_out = model.mixture_params(*self.static_in)
-        self.plan = plan
-        self.key = _plan_key(model)
-
-    def __call__(self, images, speed, command):
-        for dst, src in zip(self.static_in, (images, speed, command)):
-            if dst.shape != src.shape:
-                raise ValueError(f"PlannedMixture was recorded for input shape {tuple(dst.shape)}, got {tuple(src.shape)}")
-            dst.copy_(src)
-        if _plan_key(self.model) != self.key:            # an eager call in between re-packed or re-allocated what the plan points to
-            self.refresh()
-        self.plan.replay()
-        return self.static_out
-
-    def sample(self, images, speed, command):
-        probs, mean, std, _ = self(images, speed, command)
-        return MixtureDistribution(probs, mean, std).sample()
 
 
 class PolicyTick:
@@ -138,7 +128,7 @@ class PolicyTick:
     private ``torch.cuda.MemPool``) and re-issues them through ctypes, all on one stream.  ``tick`` returns the object's own
     output buffer (copy it to keep it across ticks); ``tick.last`` holds the deterministic tensors of the most recent tick:
     ``probs, mean, std, speeds`` (mixtures), ``punet_actions, pred_speed`` (PU-Net models), ``raw`` (the draw), else None.
-    A weight / BatchNorm-buffer / compute-dtype / device change is noticed on the next tick (``_plan_key``): the plan is
+    A weight / BatchNorm-buffer / compute-dtype / device change is noticed on the next tick (``replay_key``): the plan is
     re-recorded and all T masks are recomputed from the frame history."""
 
     def __init__(self, model, batch=1, height=224, width=224, mode="plan", seed=0):
@@ -187,15 +177,12 @@ class PolicyTick:
         self.reset()
 
     # ------------------------------------------------------------------ state
-    def _dtype(self, m):
-        return m.compute_dtype or _moe._DEFAULT_DTYPE
-
     def _key(self):
         """what a recorded tick (and, in either mode, the cached masks) depend on beyond this object's own buffers"""
         key = []
         for m in (self.pun, self.moe):
             if m is not None:
-                key.append((self._dtype(m), bool(m.fp8_weights), _plan_key(m)))
+                key.append((m.dtype_in_use(), bool(m.fp8_weights), m._engine().replay_key()))
         if self.moe is not None and self.pun is not None:
             key.append(tuple(p.data_ptr() for l in (self.model.lat_weights, self.model.long_weights) for p in (l.weight, l.bias)))
         return tuple(key)
@@ -218,7 +205,7 @@ class PolicyTick:
         elif self.pun is not None:
             with torch.no_grad():
                 self.newest.zero_()
-                m = self.pun._engine().mask_of(self.frames, self.newest, self._dtype(self.pun))
+                m = self.pun._engine().mask_of(self.frames, self.newest, self.pun.dtype_in_use())
                 for t in range(self.T):
                     self.masks[0, t].copy_(m)
 
@@ -232,32 +219,25 @@ class PolicyTick:
             self.masks = self.newest = None
         with torch.no_grad(), torch.cuda.device(dev):
             if self.pun is not None:
-                eng, dtype = self.pun._engine(), self._dtype(self.pun)
-                eng.fp8 = bool(self.pun.fp8_weights) and dtype == torch.bfloat16
+                eng, dtype, _ = self.pun.resolve_engine()
                 pu = self.pun.punet
                 if self.masks is None or self.masks.dtype != dtype:
                     self.masks = torch.zeros(1, self.T, self.B, self.H, self.W, r16(pu.num_classes), dtype=dtype, device=dev)
                     self.newest = torch.zeros(self.B, self.H, self.W, r16(pu.in_features), dtype=dtype, device=dev)
-                eng.prepare_cached(self.frames, dtype)
+                eng.prepare(self.frames, dtype)
                 for t in range(self.T):
                     ops.nchw_to_nhwc(self.frames[:, t].contiguous(), self.newest)
                     self.masks[0, t].copy_(eng.mask_of(self.frames, self.newest, dtype))
             if self.moe is not None:             # banks, pointer tables and packs of the mixture: what its half of the key reads
-                eng, dtype = self.moe._engine(), self._dtype(self.moe)
-                eng.fp8 = bool(self.moe.fp8_weights) and dtype == torch.bfloat16
-                eng._begin(self.frames, False, False, dtype, 0)
-                eng.tape = None
+                eng, dtype, _ = self.moe.resolve_engine()
+                eng.prepare(self.frames, dtype)
             self.plan = self.pool = None
             if self.mode == "plan":
                 # the recorded run (and its warm-up, which packs weights and folds BatchNorms: cached on the parameters' versions)
                 # moves the rings and the draw counter like any tick: put them back afterwards
                 saved = [t.clone() for t in (self.frames, self.state) + ((self.masks,) if self.masks is not None else ())]
-                for _ in range(2):
-                    self._body()
-                self.pool = torch.cuda.MemPool()
-                with torch.cuda.use_mem_pool(self.pool), hip.LaunchRecorder() as plan:
-                    self._result = self._body()
-                self.plan = plan
+                chain = _RecordedChain(self._body)
+                self.plan, self.pool, self._result = chain.runner, chain.pool, chain.result
                 for dst, src in zip((self.frames, self.state, self.masks), saved):
                     dst.copy_(src)
             self.key = self._key()
@@ -269,8 +249,7 @@ class PolicyTick:
         res = dict(probs=None, mean=None, std=None, speeds=None, punet_actions=None, pred_speed=None, raw=None)
         ops.history_push(self.frames, frame, nhwc=self.newest)
         if self.pun is not None:
-            eng, dtype = self.pun._engine(), self._dtype(self.pun)
-            eng.fp8 = bool(self.pun.fp8_weights) and dtype == torch.bfloat16
+            eng, dtype, _ = self.pun.resolve_engine()
             res["punet_actions"], res["pred_speed"] = eng.forward_cached(self.frames, self.newest, self.masks, speed, command, dtype)
             actions = res["punet_actions"]
         if self.moe is not None:

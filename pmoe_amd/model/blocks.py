@@ -7,13 +7,14 @@ launches by ``pmoe_amd.engine`` -- one launch covers the same layer of every exp
 container directly raises, there is no per-module PyTorch path.  The one exception is ``UNet``: the
 stage-0 trainer calls it on its own, and its ``forward`` runs the whole U-Net on its HIP engine.
 """
-import copy
 import math
 from collections import OrderedDict
 from math import log2
 
 import torch
 import torch.nn as nn
+
+from .host import EngineFn, EngineHost
 
 
 class _Held(nn.Module):
@@ -186,28 +187,7 @@ def conv3(in_ch, out_ch):
                 Conv2d(out_ch, out_ch, 3, 1, 1), BatchNorm2d(out_ch), Activation("relu"))
 
 
-class _UNetFn(torch.autograd.Function):
-    """``UNet.forward`` as one autograd node (pmoe_amd.engine_punet.UNetEngine runs forward and the taped backward)."""
-
-    @staticmethod
-    def forward(ctx, engine, image, training, dtype, taping, seed, *params):
-        out, inter, state = engine.forward(image, training, taping, dtype, seed)
-        ctx.engine, ctx.state = engine, state
-        ctx.param_ids = [id(p) for p in params]
-        if inter is not None:
-            ctx.mark_non_differentiable(inter)
-            return inter, out
-        return out
-
-    @staticmethod
-    def backward(ctx, *douts):
-        grads = ctx.engine.backward(ctx.state, douts[-1])
-        ctx.state = None
-        out = [grads.get(i) if need else None for i, need in zip(ctx.param_ids, ctx.needs_input_grad[6:])]
-        return (None,) * 6 + tuple(out)
-
-
-class UNet(_Held):
+class UNet(EngineHost, _Held):
     """blocks/unet.py:8-95.  Inside ``PredictiveUnet`` / ``PUNetExpert`` / ``PMoE`` it is a parameter container that their
     engines execute.  Called on its own -- the stage-0 trainer's ``self.model(img)`` (trainer/train_0.py:130-140) -- it runs
     on ``pmoe_amd.engine_punet.UNetEngine``: forward, and the backward of every layer, as one autograd node."""
@@ -235,49 +215,23 @@ class UNet(_Held):
         self.up_forw_4 = conv3(128, 64)
         self.out = Conv2d(64, out_features, 1, 1, 0, bias=True)
 
-    compute_dtype = None      # None -> pmoe_amd.model.moe's module-level default (bf16)
-
-    def _engine(self):
-        eng = self.__dict__.get("_eng")
-        if eng is None:
-            from ..engine_punet import UNetEngine
-            eng = self.__dict__["_eng"] = UNetEngine(self)     # not a submodule / not in state_dict
-        return eng
-
-    def __deepcopy__(self, memo):
-        # AveragedModel(model) deep-copies (train_0.py:106): drop the engine (raw device buffers), copy the rest
-        eng = self.__dict__.pop("_eng", None)
-        try:
-            new = self.__class__.__new__(self.__class__)
-            memo[id(self)] = new
-            for k, v in self.__dict__.items():
-                new.__dict__[k] = copy.deepcopy(v, memo)
-        finally:
-            if eng is not None:
-                self.__dict__["_eng"] = eng
-        return new
-
-    def enable_data_parallel(self, group=None, n_buckets=6):
-        """Average parameter gradients over ``group`` (default WORLD) inside backward (pmoe_amd.parallel)."""
-        eng = self._engine()
-        eng.dp_group, eng.dp_enabled, eng.dp_buckets = group, True, n_buckets
-        return self
+    def _make_engine(self):
+        from ..engine_punet import UNetEngine
+        return UNetEngine(self)
 
     def forward(self, image):
         """``unet.py:50-95``: image [B,C,H,W] f32 -> class logits [B,out_features,H,W] f32; with ``inter_repr`` (inference
         only) ``(x_5 pooled [B,512], logits)``."""
         if image.dim() != 4:
             raise ValueError(f"UNet: expected image [B,C,H,W], got {tuple(image.shape)}")
-        from . import moe as _moe
-        eng = self._engine()
-        dtype = self.compute_dtype or _moe._DEFAULT_DTYPE
-        taping = torch.is_grad_enabled() and any(p.requires_grad for p in eng.flat_params)
+        eng, dtype, taping = self.resolve_engine()
         if image.requires_grad and torch.is_grad_enabled():
             raise NotImplementedError("UNet on the HIP path computes no gradient for its input image (the first convolution has "
                                       "no data gradient: train_0.py feeds data, not a trainable tensor); pass image.detach()")
         # Dropout2d masks follow torch's CPU generator like the reference's: same manual_seed + same step order -> same masks
         seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if self.training and self.dropout.p > 0 else 0
-        return _UNetFn.apply(eng, image, self.training, dtype, taping, seed, *eng.flat_params)
+        out, inter = EngineFn.apply(eng, (image, self.training, taping, dtype, seed), *eng.flat_params)
+        return out if inter is None else (inter, out)
 
 
 class BasicBlock(_Held):

@@ -13,17 +13,16 @@ from .. import ops
 from ..engine import ExpertGroupEngine
 from ..utils import freeze  # noqa: F401  (re-exported: the reference imports it from utils.nn)
 from . import blocks as B
+from . import host as _host
+from .host import EngineFn, EngineHost, set_default_compute_dtype  # noqa: F401  (re-exported: callers import it from here)
 from .punet import PredictiveUnet
 
-_DEFAULT_DTYPE = torch.bfloat16
 
-
-def set_default_compute_dtype(dtype):
-    """bf16 (default; BASELINE config) or float32 (exact-f32 MFMA path, used for 1e-4 parity)."""
-    global _DEFAULT_DTYPE
-    if dtype not in (torch.bfloat16, torch.float32):
-        raise ValueError("compute dtype must be torch.bfloat16 or torch.float32")
-    _DEFAULT_DTYPE = dtype
+def __getattr__(name):
+    # ``moe._DEFAULT_DTYPE`` reads the one default that host.set_default_compute_dtype writes (module-attribute semantics kept)
+    if name == "_DEFAULT_DTYPE":
+        return _host._DEFAULT_DTYPE
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def get_model(cfg):
@@ -47,38 +46,8 @@ def get_model(cfg):
             f"'punet_inter', 'pmoe', 'pmoe+pretrained', 'moe_alt'")
 
 
-class _GroupFn(torch.autograd.Function):
-    """The whole grouped network as one autograd node (inputs: the flat parameter list)."""
-
-    @staticmethod
-    def forward(ctx, engine, images, speed, command, training, dtype, seed, taping, *params):
-        *outs, state = engine.forward(images, speed, command, training, taping, dtype, seed)
-        ctx.engine, ctx.state = engine, state
-        ctx.set_materialize_grads(False)      # an unused output (e.g. pred_speed under pmoe_loss) leaves its head's .grad None
-        ctx.param_ids = [id(p) for p in params]
-        return tuple(outs)       # (probs, mean, std, speeds) for the mixtures; (actions, pred_speed) for PUNetExpert
-
-    @staticmethod
-    def backward(ctx, *douts):
-        grads = ctx.engine.backward(ctx.state, *douts)
-        ctx.state = None
-        out = [grads.get(i) if need else None for i, need in zip(ctx.param_ids, ctx.needs_input_grad[8:])]
-        return (None,) * 8 + tuple(out)
-
-
-class _Grouped(nn.Module):
+class _Grouped(EngineHost, nn.Module):
     """Shared forward plumbing of modules that own a list of experts."""
-
-    compute_dtype = None      # None -> module-level default (bf16)
-    fp8_weights = False       # True (with bf16 compute): BASELINE config 5 -- the ResNet layer1-4 forward convolutions run on
-                              # e4m3 weights / e4m3 activations and the fp8 matrix cores (pmoe_conv_desc.w_fp8)
-
-    def _engine(self):
-        eng = self.__dict__.get("_eng")
-        if eng is None:
-            eng = self._make_engine()
-            self.__dict__["_eng"] = eng          # not a submodule / not in state_dict / rebuilt after deepcopy
-        return eng
 
     def _shared_k(self):
         return 0
@@ -86,37 +55,11 @@ class _Grouped(nn.Module):
     def _make_engine(self):
         return ExpertGroupEngine(self._expert_list(), alt=self._alt(), shared_k=self._shared_k())
 
-    def __deepcopy__(self, memo):
-        # AveragedModel(model) deep-copies (train_2.py:120): drop the engine (raw device buffers), copy the rest
-        eng = self.__dict__.pop("_eng", None)
-        try:
-            cls = self.__class__
-            new = cls.__new__(cls)
-            memo[id(self)] = new
-            import copy
-            for k, v in self.__dict__.items():
-                new.__dict__[k] = copy.deepcopy(v, memo)
-        finally:
-            if eng is not None:
-                self.__dict__["_eng"] = eng
-        return new
-
     def _run(self, images, speed, command):
-        eng = self._engine()
-        dtype = self.compute_dtype or _DEFAULT_DTYPE
-        eng.fp8 = bool(self.fp8_weights) and dtype == torch.bfloat16
+        eng, dtype, taping = self.resolve_engine()
         seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if self.training else 0
-        # grad mode is off inside Function.forward, so decide here whether a backward tape is needed
-        taping = torch.is_grad_enabled() and any(p.requires_grad for p in eng.flat_params)
-        return _GroupFn.apply(eng, images, speed, command, self.training, dtype, seed, taping, *eng.flat_params)
-
-    def enable_data_parallel(self, group=None, n_buckets=6, always=False):
-        """Average parameter gradients over ``group`` (default WORLD) inside backward, bucketed and
-        overlapped (pmoe_amd.parallel.BucketedAllReduce).  ``always``: issue the collectives even in a one-rank group
-        (exercises the RCCL path on a single GPU)."""
-        eng = self._engine()
-        eng.dp_group, eng.dp_enabled, eng.dp_buckets, eng.dp_always = group, True, n_buckets, always
-        return self
+        # -> (probs, mean, std, speeds) for the mixtures; (actions, pred_speed) for PUNetExpert
+        return EngineFn.apply(eng, (images, speed, command, self.training, taping, dtype, seed), *eng.flat_params)
 
 
 class BaseExpert(_Grouped):

@@ -165,3 +165,56 @@ def test_bench_self_launch_refuses_missing_devices():
     if torch.cuda.device_count() >= 2:
         pytest.skip("node has the devices")
     assert r.returncode == 2 and "needs 2 devices" in r.stderr, (r.returncode, r.stderr[-500:])
+
+
+@pytest.fixture
+def engine_hosts(tmp_path):
+    """one module of every kind that runs on an engine of its own: a mixture, the stage-1 PU-Net, the stage-0 U-Net"""
+    from pmoe_amd.model.punet import PredictiveUnet
+    torch.save({"unet": B.UNet().state_dict()}, tmp_path / "unet.pth")
+    return [get_model(stage2_model_cfg("moe", 2, dropout=0.0)),
+            PredictiveUnet(4, 2, model_name="unet", model_path=str(tmp_path / "unet.pth")), B.UNet()]
+
+
+def test_engine_hosts_share_cache_deepcopy_and_data_parallel_switch(engine_hosts):
+    from pmoe_amd.model.host import EngineHost
+    for m in engine_hosts:
+        assert isinstance(m, EngineHost) and "__deepcopy__" not in type(m).__dict__
+        eng = m._engine()
+        m2 = copy.deepcopy(m)
+        assert "_eng" not in m2.__dict__ and m._engine() is eng
+        assert m2._engine() is not eng and m2._engine() is m2._engine()
+        assert list(m2.state_dict().keys()) == list(m.state_dict().keys())
+        assert (eng.dp_group, eng.dp_enabled, eng.dp_buckets, eng.dp_always) == (None, False, 6, False)
+        group = object()
+        assert m.enable_data_parallel(group, n_buckets=3, always=True) is m
+        assert (eng.dp_group, eng.dp_enabled, eng.dp_buckets, eng.dp_always) == (group, True, 3, True)
+        m2.enable_data_parallel()
+        e2 = m2._engine()
+        assert (e2.dp_group, e2.dp_enabled, e2.dp_buckets, e2.dp_always) == (None, True, 6, False)
+
+
+def test_engine_hosts_honour_the_default_compute_dtype(engine_hosts):
+    from pmoe_amd.model import host, moe
+    assert moe.set_default_compute_dtype is host.set_default_compute_dtype
+    try:
+        for default in (torch.float32, torch.bfloat16):
+            moe.set_default_compute_dtype(default)
+            assert moe._DEFAULT_DTYPE is default and host._DEFAULT_DTYPE is default
+            for m in engine_hosts:
+                eng, dtype, taping = m.resolve_engine()
+                assert eng is m._engine() and dtype is default and taping and eng.fp8 is False
+                with torch.no_grad():
+                    assert m.resolve_engine()[2] is False
+                m.compute_dtype = torch.float32 if default is torch.bfloat16 else torch.bfloat16
+                assert m.resolve_engine()[1] is m.compute_dtype
+                m.compute_dtype = None
+        mix = engine_hosts[0]
+        mix.fp8_weights = True                           # the fp8 switch follows fp8_weights under bf16 compute only
+        assert mix.resolve_engine()[0].fp8 is True
+        mix.compute_dtype = torch.float32
+        assert mix.resolve_engine()[0].fp8 is False
+        with pytest.raises(ValueError, match="compute dtype"):
+            moe.set_default_compute_dtype(torch.float16)
+    finally:
+        host.set_default_compute_dtype(torch.bfloat16)

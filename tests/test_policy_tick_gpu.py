@@ -142,6 +142,29 @@ def test_tick_equals_stack_deterministic_models(tmp_path, name, dtype):
         with torch.no_grad():
             ref = model.sample(stack, dev["speed"], dev["command"])
         assert torch.equal(tick(frame, dev["speed"], dev["command"]), ref)
+    # the engine's own calls, without PolicyTick: the masks mask_of makes frame by frame, then forward_cached, against forward on
+    # the stacked frames
+    from pmoe_amd import ops
+    from pmoe_amd.engine import r16
+    pu = model.punet
+    hist = _History(T, B, S, S, seed=13)
+    for _ in range(T):
+        frame, stack = hist.step()
+    with torch.no_grad():
+        eng, dt, _ = model.resolve_engine()
+        assert dt == dtype
+        eng.prepare_cached(stack, dt)
+        ring = torch.zeros(1, T, B, S, S, r16(pu.num_classes), dtype=dt, device="cuda")
+        newest = torch.zeros(B, S, S, r16(pu.in_features), dtype=dt, device="cuda")
+        for t in range(T):                               # on entry slots 1..T-1 hold the older frames' masks, oldest first
+            ops.nchw_to_nhwc(stack[:, t].contiguous(), newest)
+            mask = eng.mask_of(stack, newest, dt).clone()
+            if t < T - 1:
+                ring[0, t + 1].copy_(mask)
+        got, got_speed = eng.forward_cached(stack, newest, ring, dev["speed"], dev["command"], dt)
+        assert torch.equal(ring[0, T - 1], mask)         # the newest frame's mask: the one pass forward_cached runs itself
+        ref, ref_speed = model(stack, dev["speed"], dev["command"])
+    assert torch.equal(got, ref) and torch.equal(got_speed, ref_speed)
 
 
 def _check_mixture_tick(model, moe, dev, B, S, with_punet):
@@ -230,6 +253,79 @@ def test_plan_survives_allocations_and_notices_weight_and_dtype_changes(tmp_path
     model.train()
     with pytest.raises(RuntimeError, match="eval"):
         tick(torch.zeros(B, 3, S, S, device="cuda"), dev["speed"], dev["command"])
+
+
+# ------------------------------------------------------------------------------------------------ replay key
+def _check_replay_key(host, dev, changes):
+    """host.eval() forward -> replay_key() is stable over a second forward; after each of ``changes`` (name, callable) and one
+    forward it is another key, and stable again"""
+    def run():
+        with torch.no_grad():
+            host(dev["images"], dev["speed"], dev["command"])
+        return host._engine().replay_key()
+    key = run()
+    assert run() == key
+    for name, change in changes:
+        with torch.no_grad():
+            change()
+        new = run()
+        assert new != key, name
+        assert run() == new, name
+        key = new
+
+
+def _dtype_switch(model):
+    def change():
+        model.compute_dtype = torch.float32 if model.compute_dtype == torch.bfloat16 else torch.bfloat16
+    return change
+
+
+def _fp8_toggle(host):
+    def change():
+        host.fp8_weights = not host.fp8_weights
+    return change
+
+
+def _punet_changes(model, host):
+    pu = host.punet
+    up = pu.pred_unet.up_2
+
+    def new_storage():
+        up.weight.data = up.weight.data.clone()
+    return [("parameter", lambda: host.action_pred[1].weight.mul_(1.01)),
+            ("frozen parameter", lambda: pu.unet.dwn_1[0].weight.mul_(1.01)),
+            ("running buffer", lambda: pu.unet.dwn_3[1].running_mean.add_(0.01)),
+            ("running buffer behind a shadow", lambda: pu.entry_block.layer2.conv2[1].running_var.mul_(1.01)),
+            ("compute dtype", _dtype_switch(model)), ("compute dtype back", _dtype_switch(model)),
+            ("ConvTranspose2d weight storage", new_storage)]
+
+
+def _mixture_changes(model, host):
+    bb = host.moe[0].backbone
+    return [("parameter", lambda: host.moe[1].action_pred.weight.mul_(1.01)),
+            ("running buffer", lambda: bb.layer2[0].bn1.running_var.mul_(1.01)),
+            ("compute dtype", _dtype_switch(model)), ("compute dtype back", _dtype_switch(model)),
+            ("fp8_weights on", _fp8_toggle(host)), ("fp8_weights off", _fp8_toggle(host))]
+
+
+@pytest.mark.gpu
+def test_replay_key_punet(tmp_path):
+    model, meta, dev = _punet_model(tmp_path, "p2_punet_b1_64_f6_eval", torch.bfloat16)
+    _check_replay_key(model, dev, _punet_changes(model, model))
+
+
+@pytest.mark.gpu
+def test_replay_key_mixture():
+    model, meta, dev = _moe_model("g4_moealt_e4_b2_64", torch.bfloat16)
+    _check_replay_key(model, dev, _mixture_changes(model, model))
+
+
+@pytest.mark.gpu
+def test_replay_key_pmoe(tmp_path):
+    """both engines of a PMoE, each under the switches of the whole model (``PMoE.compute_dtype`` sets both halves)"""
+    model, meta, dev = _punet_model(tmp_path, "p5_pmoe_e2_b2_64_f2", torch.bfloat16, exclude_freeze=["lat_weights", "long_weights"])
+    _check_replay_key(model.punet, dev, _punet_changes(model, model.punet))
+    _check_replay_key(model.moe, dev, _mixture_changes(model, model.moe))
 
 
 # ------------------------------------------------------------------------------------------------ draws
