@@ -1008,32 +1008,6 @@ __global__ void __launch_bounds__(512) conv_wgrad_bnbwd_kernel(const WgradArgs a
     }
 }
 
-// per-image filter gradient of a <= 16-input-channel 3x3 stride-1 convolution whose output gradient is given as (g, z) of the
-// BatchNorm + ReLU behind it (see the kernel).  plan == true: 0 if the descriptor fits the kernel, else an error code.
-int conv_wgrad_bnbwd_launch(WgradArgs a, const void* z, int z_ld, const float* coef, const float* c1, const float* c2,
-                            int dtype, hipStream_t st, bool plan) {
-    if (dtype != PMOE_DT_BF16 || !a.per_image || a.ks != 3 || a.stride != 1 || a.pad != 1) return PMOE_ERR_UNSUPPORTED;
-    if (a.Cin > 16 || a.Cin % 8 || a.Cout > 64 || a.Cout % 8 || a.CoutP != 64 || a.CinP != 64) return PMOE_ERR_UNSUPPORTED;
-    if (a.Ho != a.H || a.Wo != a.W || a.N % a.ipe || (long long)a.H * a.W < 256) return PMOE_ERR_UNSUPPORTED;
-    if (z_ld % 8 || z_ld < a.Cout || a.x_ld % 8 || a.dy_ld % 8) return PMOE_ERR_ARG;
-    auto p2 = [](int v) { int l = 0; while ((1 << l) < v) ++l; return l; };
-    int lTW = p2(a.W); if (lTW > 5) lTW = 5;
-    const int lTH = 8 - lTW;
-    a.lTW = lTW; a.lTH = lTH; a.TN = 1; a.n_groups = a.ipe;
-    a.tiles_y = (a.H + (1 << lTH) - 1) >> lTH;
-    a.tiles_x = (a.W + (1 << lTW) - 1) >> lTW;
-    const int NPIX = ((1 << lTW) + 2) * ((1 << lTH) + 2);
-    if (NPIX * 2 > 1024) return PMOE_ERR_UNSUPPORTED;                 // two 16-byte patch items per thread
-    if (plan) return 0;
-    if (!z || !coef || !c1 || !c2 || !a.x || !a.dy || !a.dw) return PMOE_ERR_ARG;
-    size_t smem = (size_t)256 * 192 + (size_t)NPIX * 32;
-    if (smem < (size_t)3 * 2 * 4096) smem = (size_t)3 * 2 * 4096;     // fold room: (WK - 1) x 2 tile waves x 4 KiB
-    HIP_RET((ensure_dyn_lds<conv_wgrad_bnbwd_kernel>(160 * 1024)));
-    BnBwdFuse f{z, coef, c1, c2, z_ld, a.Cout};
-    hipLaunchKernelGGL(conv_wgrad_bnbwd_kernel, dim3(a.ipe, 1, a.N / a.ipe), dim3(512), smem, st, a, f);
-    return (int)hipGetLastError();
-}
-
 // dw[i] = sum over the K-split slabs, fixed order (slab s at part + s * total)
 __global__ void __launch_bounds__(256) wgrad_reduce_kernel(const float* __restrict__ part, float* __restrict__ dw,
                                                            const int nsplit, const long long total4) {
@@ -1086,218 +1060,235 @@ __global__ void __launch_bounds__(256) wgrad_fold_unpack_kernel(const float* __r
     }
 }
 
+// ---- host side: ONE selection (wgrad_select -> WgradPlan, kernels.h) behind the launch, the deferred fold, the plan code and the
+// workspace size; one launcher per kernel family, which only picks the instantiation the plan names.
+
 // the tail of a weight-gradient launch: slabs -> a.dw (wgrad_reduce_kernel) or, with a.grads, straight into the parameter layout
-static int wgrad_finish(const WgradArgs& a, int E, int taps, int nsplit, hipStream_t st, bool force = false) {
+static int wgrad_finish(const WgradPlan& p, hipStream_t st, bool force = false) {
+    const WgradArgs& a = p.a;
     if (a.per_image || (a.defer_fold && !force)) return 0;
-    const long long total = (long long)E * taps * a.CoutP * a.CinP;
+    const long long total = (long long)p.E * p.taps * a.CoutP * a.CinP;
     if (a.grads) {
-        const float* src = nsplit > 1 ? a.part : a.dw;
+        const float* src = p.nsplit > 1 ? a.part : a.dw;
         long long blocks = ((long long)a.cout_real * a.cin_real + 63) / 64;
         if (blocks > 4096) blocks = 4096;
-        dim3 grid((unsigned)blocks, E);
-        if (taps == 9)
-            hipLaunchKernelGGL(wgrad_fold_unpack_kernel<9>, grid, dim3(256), 0, st, src, a.grads, nsplit, total, a.cout_real,
+        dim3 grid((unsigned)blocks, p.E);
+        if (p.taps == 9)
+            hipLaunchKernelGGL(wgrad_fold_unpack_kernel<9>, grid, dim3(256), 0, st, src, a.grads, p.nsplit, total, a.cout_real,
                                a.cin_real, a.CoutP, a.CinP);
         else
-            hipLaunchKernelGGL(wgrad_fold_unpack_kernel<1>, grid, dim3(256), 0, st, src, a.grads, nsplit, total, a.cout_real,
+            hipLaunchKernelGGL(wgrad_fold_unpack_kernel<1>, grid, dim3(256), 0, st, src, a.grads, p.nsplit, total, a.cout_real,
                                a.cin_real, a.CoutP, a.CinP);
         return (int)hipGetLastError();
     }
-    if (nsplit > 1) {
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, st, a.part, a.dw, nsplit,
+    if (p.nsplit > 1) {
+        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, st, a.part, a.dw, p.nsplit,
                            total / 4);
         return (int)hipGetLastError();
     }
     return 0;
 }
 
-template <typename T, int TAPS, int MAXV> static int launch_wg(const WgradArgs& a, int E, size_t smem, hipStream_t st) {
-    HIP_RET((ensure_dyn_lds<conv_wgrad_kernel<T, TAPS, MAXV>>(160 * 1024)));
-    constexpr int CKW = 128 / (int)sizeof(T);
-    const int mbpe = a.n_groups * a.tiles_y * a.tiles_x;
-    const int nsplit = (mbpe + a.mb_per_wg - 1) / a.mb_per_wg;
-    dim3 grid(nsplit * ((a.Cout + CKW - 1) / CKW) * ((a.Cin + CKW - 1) / CKW), 1, E), block(WgradCfg<T>::NW * 64, 1, 1);
-    // room for the in-workgroup fold of the pixel-split waves: (WK-1) x TPR taps x tile waves x 4 KiB
-    constexpr size_t fold = (size_t)(WgradCfg<T>::WK - 1) * (TAPS == 9 ? 3 : 1) * WgradCfg<T>::WCO * WgradCfg<T>::WCI * 4096;
-    if (smem < fold) smem = fold;
-    hipLaunchKernelGGL((conv_wgrad_kernel<T, TAPS, MAXV>), grid, block, smem, st, a);
-    HIP_RET(hipGetLastError());
-    return wgrad_finish(a, E, TAPS, nsplit, st);
+static int wgrad_p2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
+
+// per-image filter gradient of a <= 16-input-channel 3x3 stride-1 convolution whose output gradient is given as (g, z) of the
+// BatchNorm + ReLU behind it (conv_wgrad_bnbwd_kernel): the plan, or the reason why the kernel does not serve the descriptor
+static int wgrad_bnbwd_plan(int dtype, int z_ld, WgradPlan* p) {
+    WgradArgs& a = p->a;
+    if (dtype != PMOE_DT_BF16 || !a.per_image || a.ks != 3 || a.stride != 1 || a.pad != 1) return PMOE_ERR_UNSUPPORTED;
+    if (a.Cin > 16 || a.Cin % 8 || a.Cout > 64 || a.Cout % 8 || a.CoutP != 64 || a.CinP != 64) return PMOE_ERR_UNSUPPORTED;
+    if (a.Ho != a.H || a.Wo != a.W || a.N % a.ipe || (long long)a.H * a.W < 256) return PMOE_ERR_UNSUPPORTED;
+    if (z_ld % 8 || z_ld < a.Cout || a.x_ld % 8 || a.dy_ld % 8) return PMOE_ERR_ARG;
+    a.lTW = wgrad_p2(a.W) > 5 ? 5 : wgrad_p2(a.W);
+    a.lTH = 8 - a.lTW; a.TN = 1; a.n_groups = a.ipe;
+    a.tiles_y = (a.H + (1 << a.lTH) - 1) >> a.lTH;
+    a.tiles_x = (a.W + (1 << a.lTW) - 1) >> a.lTW;
+    const int NPIX = ((1 << a.lTW) + 2) * ((1 << a.lTH) + 2);
+    if (NPIX * 2 > 1024) return PMOE_ERR_UNSUPPORTED;                 // two 16-byte patch items per thread
+    p->kind = WGRAD_BNBWD;
+    p->E = a.N / a.ipe; p->taps = 9; p->nsplit = 1; p->ws_floats = 0;   // per image: no K-split scratch
+    p->grid = dim3(a.ipe, 1, p->E); p->block = dim3(512);
+    p->smem = (size_t)256 * 192 + (size_t)NPIX * 32;
+    if (p->smem < (size_t)3 * 2 * 4096) p->smem = (size_t)3 * 2 * 4096;     // fold room: (WK - 1) x 2 tile waves x 4 KiB
+    return 7209;
 }
 
-// the separated-roles kernel serves the wide layout (>= 64 input channels) on 16- or 32-pixel-wide tiles
-static bool wgrad_v2_ok(const WgradArgs& a, int lTW) {
-    const char* ev = getenv("PMOE_WGRAD_V2");
-    if (ev && !atoi(ev)) return false;
-    const char* evx = getenv("PMOE_WGRAD_PIPE");
-    if (evx) return false;                              // (the PIN / timing modes belong to the 8-wave kernel)
-    return (lTW == 4 || lTW == 5) && a.ipe <= 511;
-}
-
-// plan == true: nothing is launched, *ws_floats receives the size of the K-split workspace the launch needs (0: none)
-template <typename T> static int wgrad_dtype(WgradArgs a, hipStream_t st, bool plan, long long* ws_floats, int* code = nullptr) {
-    constexpr int CKW = 128 / (int)sizeof(T);
-    constexpr int VEh = 16 / (int)sizeof(T);
-    if (a.Cin % VEh || a.Cout % VEh || a.CinP < a.Cin || a.CoutP < a.Cout) return PMOE_ERR_ARG;
-    // the workgroup tiles must cover dw exactly (every element is WRITTEN, nothing is accumulated onto old contents)
-    if (a.CinP != (a.Cin + CKW - 1) / CKW * CKW || a.CoutP != (a.Cout + CKW - 1) / CKW * CKW) return PMOE_ERR_ARG;
-    if ((a.ks != 1 && a.ks != 3) || (a.stride != 1 && a.stride != 2) || a.N % a.ipe) return PMOE_ERR_ARG;
-    const int E = a.N / a.ipe;
-    auto p2 = [](int v) { int l = 0; while ((1 << l) < v) ++l; return l; };
-    for (int lBM = 8; lBM >= 6; --lBM) {
-        int lTW = p2(a.Wo); if (lTW > 5) lTW = 5;
-        int lTH = p2(a.Ho); if (lTH > lBM - lTW) lTH = lBM - lTW;
-        if (lTW > lBM) { lTW = lBM; lTH = 0; }
-        const int BMP = 1 << lBM;
-        const int TN = BMP >> (lTW + lTH);
-        const int TW = 1 << lTW, TH = 1 << lTH;
-        const int lstride = a.ks == 1 ? 1 : a.stride;
-        const int PW = (TW - 1) * lstride + a.ks, PH = (TH - 1) * lstride + a.ks;
-        const int NPIX = TN * PH * PW;
-        constexpr int NTHR = WgradCfg<T>::NW * 64;
-        const int need = (NPIX * 8 + NTHR - 1) / NTHR;  // 16-byte patch loads per thread
-        constexpr int M1 = 48 / WgradCfg<T>::NW, M2 = 80 / WgradCfg<T>::NW;   // patch loads per thread: 6|10 (8 waves), 12|20 (4 waves)
-        if (need > M2) continue;
-        const size_t smem = (size_t)BMP * 192 + (size_t)NPIX * 192;
-        if (smem > 150 * 1024) continue;
-        a.lTW = lTW; a.lTH = lTH; a.TN = TN;
-        a.n_groups = (a.ipe + TN - 1) / TN;
-        a.tiles_y = (a.Ho + TH - 1) / TH;
-        a.tiles_x = (a.Wo + TW - 1) / TW;
-        const int mbpe = a.n_groups * a.tiles_y * a.tiles_x;
-        // K-split: one workgroup per CU is resident; ONE round of 256 workgroups measured best (each walks more m-blocks,
-        // flushes its 9 x 64 x 64 accumulators once, no second-round tail): 2 rounds -10 %, 1.25-1.5 rounds -25..30 %.
-        // PMOE_WGRAD_WGS overrides the target for A/B runs.
-        const int pairs = ((a.Cout + CKW - 1) / CKW) * ((a.Cin + CKW - 1) / CKW) * E;
-        static int target = 0;
-        if (!target) { const char* ev = getenv("PMOE_WGRAD_WGS"); target = ev ? atoi(ev) : 256; }
-        int want = (target + pairs - 1) / pairs;
-        if (want < 1) want = 1;
-        if (want > mbpe) want = mbpe;
-        a.mb_per_wg = (mbpe + want - 1) / want;
-        if (a.per_image) {                              // one workgroup walks exactly one image
-            if (TN != 1) return PMOE_ERR_UNSUPPORTED;
-            a.mb_per_wg = a.tiles_y * a.tiles_x;
-        }
-        { const char* ev = getenv("PMOE_WGRAD_SLICE_FASTEST"); a.slice_fastest = ev ? atoi(ev) : 0; }
-        const int nsplit = (mbpe + a.mb_per_wg - 1) / a.mb_per_wg;
-        const long long ws = (a.per_image || nsplit == 1) ? 0 : (long long)nsplit * E * a.ks * a.ks * a.CoutP * a.CinP;
-        if (plan && !code) { *ws_floats = ws; return 0; }
-        if (!plan && ws > 0 && (!a.part || a.part_floats < ws)) return PMOE_ERR_ARG;
-        if constexpr (sizeof(T) == 2) {
-            // dense 3x3 stride 1 in bf16: the LDS-DMA variant (PMOE_WGRAD_DMA=0: A/B switch back to register staging)
-            const char* evd = getenv("PMOE_WGRAD_DMA");      // (read per launch: tools/ab_conv.py flips it inside one process)
-            const int dma_on = evd ? atoi(evd) : 1;
-            const long long xbytes = (long long)a.ipe * a.H * a.W * a.x_ld * 2, dybytes = (long long)a.ipe * a.Ho * a.Wo * a.dy_ld * 2;
-            const int npiece = (NPIX + 7) / 8;
-            int mpw, mph;
-            const bool exact = magic_div_exact(npiece * 8, PW, PH, &mpw, &mph);
-            if (dma_on && a.ks == 3 && a.stride == 1 && BMP == 256 && lTW >= 2 && npiece <= 48 && exact &&
-                xbytes < 0x7ff00000ll && dybytes < 0x7ff00000ll && 2 * ((size_t)BMP * 128 + (size_t)npiece * 1024) <= 160 * 1024) {
-                const char* evn = getenv("PMOE_WGRAD_NARROW");           // A/B: 0 = the 2 x 2 x 2 wave layout for every layer
-                const bool narrow = a.Cin <= 32 && !(evn && !atoi(evn));
-                if (plan) { *code = narrow ? 7109 : wgrad_v2_ok(a, lTW) ? 7309 : 7009; return 0; }   // conv_wgrad_dma_kernel<1, 1> / dma2 / <1, 2>
-                size_t sm = 2 * ((size_t)BMP * 128 + (size_t)npiece * 1024);
-                if (sm < 49152) sm = 49152;               // room for the flush's fold
-                const int nsp = (mbpe + a.mb_per_wg - 1) / a.mb_per_wg;
-                dim3 grid(nsp * pairs / E, 1, E), block(512, 1, 1);
-                const char* evx = getenv("PMOE_WGRAD_PIPE");
-                const char* evp = getenv("PMOE_WGRAD_PAIRS");            // A/B: 0 = one tap per MFMA column block
+// The LDS-DMA kernels: dense 3x3 stride 1 in bf16 on 256-pixel blocks (NPIX patch pixels, PW x PH per image; `tiles` channel tiles
+// per expert; the tile and the K-split are already in *p).  conv_wgrad_dma_kernel<PIN, WCI, PAIRS, REQ> with its 2 x 4 wave layout (WCI = 1) for <= 32 input channels,
+// conv_wgrad_dma2_kernel<lTW, AHEAD> (separated roles) for the wide layout on 16- or 32-pixel-wide tiles.  false: the
+// register-staged kernel serves the descriptor.  Every switch is read per call (tools/ab_conv.py flips them inside one process).
+static bool wgrad_dma_plan(int NPIX, int PW, int PH, int tiles, WgradPlan* p) {
+    const WgradArgs& a = p->a;
+    const char* evd = getenv("PMOE_WGRAD_DMA");          // A/B: 0 = back to register staging
+    const long long xbytes = (long long)a.ipe * a.H * a.W * a.x_ld * 2, dybytes = (long long)a.ipe * a.Ho * a.Wo * a.dy_ld * 2;
+    const int npiece = (NPIX + 7) / 8;
+    const size_t sm = 2 * ((size_t)256 * 128 + (size_t)npiece * 1024);
+    if ((evd && !atoi(evd)) || a.ks != 3 || a.stride != 1 || a.lTW < 2 || npiece > 48 || sm > 160 * 1024 ||
+        xbytes >= 0x7ff00000ll || dybytes >= 0x7ff00000ll || !magic_div_exact(npiece * 8, PW, PH, &p->mpw, &p->mph))
+        return false;
+    const char* evn = getenv("PMOE_WGRAD_NARROW");       // A/B: 0 = the 2 x 2 x 2 wave layout for every layer
+    const char* ev2 = getenv("PMOE_WGRAD_V2");           // A/B: 0 = the 8-wave kernel for the wide layout too
+    const char* evx = getenv("PMOE_WGRAD_PIPE");         // set: the PIN / timing modes, which belong to the 8-wave kernel
+    const bool narrow = a.Cin <= 32 && !(evn && !atoi(evn));
+    const bool v2 = !narrow && !(ev2 && !atoi(ev2)) && !evx && (a.lTW == 4 || a.lTW == 5) && a.ipe <= 511;
+    p->kind = v2 ? WGRAD_DMA2 : WGRAD_DMA;
+    p->code = narrow ? 7109 : v2 ? 7309 : 7009;
+    p->grid = dim3(p->nsplit * tiles, 1, p->E); p->block = dim3(512);
+    p->smem = sm < 49152 ? 49152 : sm;                   // room for the flush's fold
+    const int pipe = evx ? atoi(evx) : 1;
+    p->pin = 1; p->wci = narrow ? 1 : 2;
+    if (v2) {
+        const char* eva = getenv("PMOE_WGRAD_AHEAD");    // A/B: fragment read-ahead in taps (5 | 6)
+        p->ahead = eva && atoi(eva) == 6 ? 6 : 5;
 #ifdef PMOE_STAMP          // tools build only (tools/stamp_conv.py --build): timing modes with WRONG results, see the kernel's main loop
-                if (evx && atoi(evx) == 2) {
-                    HIP_RET((ensure_dyn_lds<conv_wgrad_dma_kernel<2>>(160 * 1024)));
-                    hipLaunchKernelGGL(conv_wgrad_dma_kernel<2>, grid, block, sm, st, a, mpw, mph);
-                } else if (evx && atoi(evx) == 3) {
-                    HIP_RET((ensure_dyn_lds<conv_wgrad_dma_kernel<3>>(160 * 1024)));
-                    hipLaunchKernelGGL(conv_wgrad_dma_kernel<3>, grid, block, sm, st, a, mpw, mph);
-                } else
+    } else if (pipe == 2 || pipe == 3) {
+        p->pin = pipe; p->wci = 2;
 #endif
-                if (narrow && a.Cin <= 16 && !(evp && !atoi(evp))) {
-                    if (sm < (size_t)3 * 3 * 2 * 4096) sm = (size_t)3 * 3 * 2 * 4096;
-                    HIP_RET((ensure_dyn_lds<conv_wgrad_dma_kernel<1, 1, true>>(160 * 1024)));
-                    hipLaunchKernelGGL((conv_wgrad_dma_kernel<1, 1, true>), grid, block, sm, st, a, mpw, mph);
-                } else if (narrow) {
-                    if (sm < (size_t)3 * 3 * 2 * 4096) sm = (size_t)3 * 3 * 2 * 4096;      // fold room: (WK - 1) x 3 taps x 2 tile waves
-                    HIP_RET((ensure_dyn_lds<conv_wgrad_dma_kernel<1, 1>>(160 * 1024)));
-                    hipLaunchKernelGGL((conv_wgrad_dma_kernel<1, 1>), grid, block, sm, st, a, mpw, mph);
-                } else if (evx && !atoi(evx)) {
-                    HIP_RET((ensure_dyn_lds<conv_wgrad_dma_kernel<0>>(160 * 1024)));
-                    hipLaunchKernelGGL(conv_wgrad_dma_kernel<0>, grid, block, sm, st, a, mpw, mph);
-                } else if (wgrad_v2_ok(a, lTW)) {
-                    // round 4: four accumulating waves (one per SIMD, k-block-deep fragment read-ahead) + one request-only wave
-                    const char* eva = getenv("PMOE_WGRAD_AHEAD");            // A/B: fragment read-ahead in taps (5 | 6)
-                    const int ahead = eva ? atoi(eva) : 5;
-                    if (lTW == 5 && ahead == 6) {
-                        HIP_RET((ensure_dyn_lds<conv_wgrad_dma2_kernel<5, 6>>(160 * 1024)));
-                        hipLaunchKernelGGL((conv_wgrad_dma2_kernel<5, 6>), grid, dim3(512, 1, 1), sm, st, a, mpw, mph);
-                    } else if (lTW == 5) {
-                        HIP_RET((ensure_dyn_lds<conv_wgrad_dma2_kernel<5>>(160 * 1024)));
-                        hipLaunchKernelGGL(conv_wgrad_dma2_kernel<5>, grid, dim3(512, 1, 1), sm, st, a, mpw, mph);
-                    } else if (ahead == 6) {
-                        HIP_RET((ensure_dyn_lds<conv_wgrad_dma2_kernel<4, 6>>(160 * 1024)));
-                        hipLaunchKernelGGL((conv_wgrad_dma2_kernel<4, 6>), grid, dim3(512, 1, 1), sm, st, a, mpw, mph);
-                    } else {
-                        HIP_RET((ensure_dyn_lds<conv_wgrad_dma2_kernel<4>>(160 * 1024)));
-                        hipLaunchKernelGGL(conv_wgrad_dma2_kernel<4>, grid, dim3(512, 1, 1), sm, st, a, mpw, mph);
-                    }
-                } else {
-                    const char* evr = getenv("PMOE_WGRAD_REQ");             // A/B: 0 = round-2 request code, 1 = precomputed, at the top
-                    const int req = a.ipe > 511 ? 0 : evr ? atoi(evr) : 1;
-                    if (req == 2) {
-                        HIP_RET((ensure_dyn_lds<conv_wgrad_dma_kernel<1, 2, false, 2>>(160 * 1024)));
-                        hipLaunchKernelGGL((conv_wgrad_dma_kernel<1, 2, false, 2>), grid, block, sm, st, a, mpw, mph);
-                    } else if (req == 1) {
-                        HIP_RET((ensure_dyn_lds<conv_wgrad_dma_kernel<1, 2, false, 1>>(160 * 1024)));
-                        hipLaunchKernelGGL((conv_wgrad_dma_kernel<1, 2, false, 1>), grid, block, sm, st, a, mpw, mph);
-                    } else {
-                        HIP_RET((ensure_dyn_lds<conv_wgrad_dma_kernel<1>>(160 * 1024)));
-                        hipLaunchKernelGGL(conv_wgrad_dma_kernel<1>, grid, block, sm, st, a, mpw, mph);
-                    }
-                }
-                HIP_RET(hipGetLastError());
-                return wgrad_finish(a, E, 9, nsp, st);
-            }
-        }
-        if (plan) { *code = 6000 + a.ks * a.ks * 100 + (need <= M1 ? M1 : M2); return 0; }      // conv_wgrad_kernel<T, taps, MAXV>
-        if (need <= M1) return a.ks == 3 ? launch_wg<T, 9, M1>(a, E, smem, st) : launch_wg<T, 1, M1>(a, E, smem, st);
-        return a.ks == 3 ? launch_wg<T, 9, M2>(a, E, smem, st) : launch_wg<T, 1, M2>(a, E, smem, st);
+    } else if (narrow) {
+        const char* evp = getenv("PMOE_WGRAD_PAIRS");    // A/B: 0 = one tap per MFMA column block
+        p->pairs = a.Cin <= 16 && !(evp && !atoi(evp));
+        if (p->smem < (size_t)3 * 3 * 2 * 4096) p->smem = (size_t)3 * 3 * 2 * 4096;      // fold room: (WK - 1) x 3 taps x 2 tile waves
+    } else if (pipe == 0) {
+        p->pin = 0;
+    } else {
+        const char* evr = getenv("PMOE_WGRAD_REQ");      // A/B: 0 = round-2 request code, 1 = precomputed, at the top
+        const int req = a.ipe > 511 ? 0 : evr ? atoi(evr) : 1;
+        p->req = req == 1 || req == 2 ? req : 0;
     }
-    return PMOE_ERR_UNSUPPORTED;
+    return true;
 }
 
-// the deferred tail (WgradArgs.defer_fold): the K-split count is the one the launch used (same planning code)
-int conv_wgrad_fold(const WgradArgs& a, int dtype, hipStream_t st) {
-    if (a.per_image) return 0;
-    long long ws = 0;
-    const int rc = dtype == PMOE_DT_BF16 ? wgrad_dtype<bf16>(a, nullptr, true, &ws)
-                 : dtype == PMOE_DT_F32 ? wgrad_dtype<float>(a, nullptr, true, &ws) : PMOE_ERR_ARG;
-    if (rc) return rc;
-    const int E = a.N / a.ipe, taps = a.ks * a.ks;
-    const long long total = (long long)E * taps * a.CoutP * a.CinP;
-    const int nsplit = ws > 0 ? (int)(ws / total) : 1;
-    if (nsplit > 1 && (!a.part || a.part_floats < ws)) return PMOE_ERR_ARG;
-    return wgrad_finish(a, E, taps, nsplit, st, true);
+// the dtype-dependent constants of conv_wgrad_kernel<T, ...> (WgradCfg<T>) as values: waves, and the waves whose partial tiles the
+// in-workgroup fold parks in LDS
+template <typename T> constexpr int wgrad_fold_waves = (WgradCfg<T>::WK - 1) * WgradCfg<T>::WCO * WgradCfg<T>::WCI;
+
+int wgrad_select(const WgradArgs& a0, int dtype, const WgradBn& bn, WgradPlan* p) {
+    *p = WgradPlan{};
+    p->a = a0;
+    WgradArgs& a = p->a;
+    auto done = [p](int code) { return p->code = code; };
+    if (bn.fused) return done(wgrad_bnbwd_plan(dtype, bn.z_ld, p));
+    if (dtype != PMOE_DT_BF16 && dtype != PMOE_DT_F32) return done(PMOE_ERR_ARG);
+    const int esz = p->esz = dtype == PMOE_DT_BF16 ? 2 : 4;
+    const int CKW = 128 / esz, VEh = 16 / esz, NW = esz == 2 ? WgradCfg<bf16>::NW : WgradCfg<float>::NW;
+    const int M1 = 48 / NW, M2 = 80 / NW;               // patch loads per thread: 6|10 (8 waves), 12|20 (4 waves)
+    if (a.Cin % VEh || a.Cout % VEh || a.CinP < a.Cin || a.CoutP < a.Cout) return done(PMOE_ERR_ARG);
+    // the workgroup tiles must cover dw exactly (every element is WRITTEN, nothing is accumulated onto old contents)
+    if (a.CinP != (a.Cin + CKW - 1) / CKW * CKW || a.CoutP != (a.Cout + CKW - 1) / CKW * CKW) return done(PMOE_ERR_ARG);
+    if ((a.ks != 1 && a.ks != 3) || (a.stride != 1 && a.stride != 2) || a.N % a.ipe) return done(PMOE_ERR_ARG);
+    p->E = a.N / a.ipe; p->taps = a.ks * a.ks;
+    // the largest pixel block (256, 128, 64) whose halo patch fits the per-thread load budget and LDS; rows of up to 32 pixels
+    const int lstride = a.ks == 1 ? 1 : a.stride;
+    a.lTW = wgrad_p2(a.Wo) > 5 ? 5 : wgrad_p2(a.Wo);
+    int lBM = 8, PW, PH, NPIX, need;
+    size_t smem;
+    for (;; --lBM) {
+        if (lBM < 6) return done(PMOE_ERR_UNSUPPORTED);
+        a.lTH = wgrad_p2(a.Ho) > lBM - a.lTW ? lBM - a.lTW : wgrad_p2(a.Ho);
+        a.TN = (1 << lBM) >> (a.lTW + a.lTH);
+        PW = ((1 << a.lTW) - 1) * lstride + a.ks; PH = ((1 << a.lTH) - 1) * lstride + a.ks;
+        NPIX = a.TN * PH * PW;
+        need = (NPIX * 8 + NW * 64 - 1) / (NW * 64);   // 16-byte patch loads per thread
+        smem = ((size_t)(1 << lBM) + NPIX) * 192;
+        if (need <= M2 && smem <= 150 * 1024) break;
+    }
+    a.n_groups = (a.ipe + a.TN - 1) / a.TN;
+    a.tiles_y = (a.Ho + (1 << a.lTH) - 1) >> a.lTH;
+    a.tiles_x = (a.Wo + (1 << a.lTW) - 1) >> a.lTW;
+    const int mbpe = a.n_groups * a.tiles_y * a.tiles_x;
+    // K-split: one workgroup per CU is resident; ONE round of 256 workgroups measured best (each walks more m-blocks,
+    // flushes its 9 x 64 x 64 accumulators once, no second-round tail): 2 rounds -10 %, 1.25-1.5 rounds -25..30 %.
+    // PMOE_WGRAD_WGS overrides the target for A/B runs (latched on first use).
+    const int tiles = ((a.Cout + CKW - 1) / CKW) * ((a.Cin + CKW - 1) / CKW);     // channel tiles per expert
+    static int target = 0;
+    if (!target) { const char* ev = getenv("PMOE_WGRAD_WGS"); target = ev ? atoi(ev) : 256; }
+    int want = (target + tiles * p->E - 1) / (tiles * p->E);
+    if (want < 1) want = 1;
+    if (want > mbpe) want = mbpe;
+    a.mb_per_wg = (mbpe + want - 1) / want;
+    if (a.per_image) {                                  // one workgroup walks exactly one image
+        if (a.TN != 1) return done(PMOE_ERR_UNSUPPORTED);
+        a.mb_per_wg = a.tiles_y * a.tiles_x;
+    }
+    { const char* ev = getenv("PMOE_WGRAD_SLICE_FASTEST"); a.slice_fastest = ev ? atoi(ev) : 0; }
+    p->nsplit = (mbpe + a.mb_per_wg - 1) / a.mb_per_wg;
+    p->ws_floats = (a.per_image || p->nsplit == 1) ? 0 : (long long)p->nsplit * p->E * p->taps * a.CoutP * a.CinP;
+    if (esz == 2 && lBM == 8 && wgrad_dma_plan(NPIX, PW, PH, tiles, p)) return p->code;
+    p->kind = WGRAD_TILE;
+    p->maxv = need <= M1 ? M1 : M2;
+    p->grid = dim3(p->nsplit * tiles, 1, p->E); p->block = dim3(NW * 64);
+    // room for the in-workgroup fold of the pixel-split waves: (WK-1) x TPR taps x tile waves x 4 KiB
+    const size_t fold = (size_t)(esz == 2 ? wgrad_fold_waves<bf16> : wgrad_fold_waves<float>) * (p->taps == 9 ? 3 : 1) * 4096;
+    p->smem = smem < fold ? fold : smem;
+    return p->code = 6000 + p->taps * 100 + p->maxv;
 }
 
-int conv_wgrad_launch(const WgradArgs& a, int dtype, hipStream_t st) {
-    long long ws = 0;
-    if (dtype == PMOE_DT_BF16) return wgrad_dtype<bf16>(a, st, false, &ws);
-    if (dtype == PMOE_DT_F32) return wgrad_dtype<float>(a, st, false, &ws);
-    return PMOE_ERR_ARG;
+template <auto KERNEL, typename... Args> static int wgrad_go(const WgradPlan& p, hipStream_t st, Args... args) {
+    HIP_RET((ensure_dyn_lds<KERNEL>(160 * 1024)));
+    hipLaunchKernelGGL(KERNEL, p.grid, p.block, p.smem, st, p.a, args...);
+    return (int)hipGetLastError();
 }
 
-// which kernel a descriptor runs on: 7009 = conv_wgrad_dma_kernel (7109: its <= 32-input-channel wave layout); 6000 + taps * 100 + MAXV = conv_wgrad_kernel<T, taps, MAXV>
-int conv_wgrad_plan(const WgradArgs& a, int dtype) {
-    long long ws = 0;
-    int code = 0;
-    const int rc = dtype == PMOE_DT_BF16 ? wgrad_dtype<bf16>(a, nullptr, true, &ws, &code)
-                 : dtype == PMOE_DT_F32 ? wgrad_dtype<float>(a, nullptr, true, &ws, &code) : PMOE_ERR_ARG;
-    return rc ? rc : code;
+template <typename T> static int wgrad_tile_launch(const WgradPlan& p, hipStream_t st) {
+    constexpr int M1 = 48 / WgradCfg<T>::NW, M2 = 80 / WgradCfg<T>::NW;
+    if (p.maxv == M1) return p.taps == 9 ? wgrad_go<conv_wgrad_kernel<T, 9, M1>>(p, st) : wgrad_go<conv_wgrad_kernel<T, 1, M1>>(p, st);
+    return p.taps == 9 ? wgrad_go<conv_wgrad_kernel<T, 9, M2>>(p, st) : wgrad_go<conv_wgrad_kernel<T, 1, M2>>(p, st);
 }
 
-long long conv_wgrad_ws_floats(const WgradArgs& a, int dtype) {
-    long long ws = 0;
-    const int rc = dtype == PMOE_DT_BF16 ? wgrad_dtype<bf16>(a, nullptr, true, &ws)
-                 : dtype == PMOE_DT_F32 ? wgrad_dtype<float>(a, nullptr, true, &ws) : PMOE_ERR_ARG;
-    return rc ? rc : ws;
+static int wgrad_dma_launch(const WgradPlan& p, hipStream_t st) {
+    switch (p.pin) {
+    case 0: return wgrad_go<conv_wgrad_dma_kernel<0>>(p, st, p.mpw, p.mph);
+#ifdef PMOE_STAMP
+    case 2: return wgrad_go<conv_wgrad_dma_kernel<2>>(p, st, p.mpw, p.mph);
+    case 3: return wgrad_go<conv_wgrad_dma_kernel<3>>(p, st, p.mpw, p.mph);
+#endif
+    }
+    if (p.wci == 1 && p.pairs) return wgrad_go<conv_wgrad_dma_kernel<1, 1, true>>(p, st, p.mpw, p.mph);
+    if (p.wci == 1) return wgrad_go<conv_wgrad_dma_kernel<1, 1>>(p, st, p.mpw, p.mph);
+    if (p.req == 2) return wgrad_go<conv_wgrad_dma_kernel<1, 2, false, 2>>(p, st, p.mpw, p.mph);
+    if (p.req == 1) return wgrad_go<conv_wgrad_dma_kernel<1, 2, false, 1>>(p, st, p.mpw, p.mph);
+    return wgrad_go<conv_wgrad_dma_kernel<1>>(p, st, p.mpw, p.mph);
+}
+
+// round 4: four accumulating waves (one per SIMD, k-block-deep fragment read-ahead) + one request-only wave
+static int wgrad_dma2_launch(const WgradPlan& p, hipStream_t st) {
+    if (p.a.lTW == 5) return p.ahead == 6 ? wgrad_go<conv_wgrad_dma2_kernel<5, 6>>(p, st, p.mpw, p.mph) : wgrad_go<conv_wgrad_dma2_kernel<5>>(p, st, p.mpw, p.mph);
+    return p.ahead == 6 ? wgrad_go<conv_wgrad_dma2_kernel<4, 6>>(p, st, p.mpw, p.mph) : wgrad_go<conv_wgrad_dma2_kernel<4>>(p, st, p.mpw, p.mph);
+}
+
+static int conv_wgrad_bnbwd_launch(const WgradPlan& p, const WgradBn& bn, hipStream_t st) {
+    if (!bn.z || !bn.coef || !bn.c1 || !bn.c2 || !p.a.x || !p.a.dy || !p.a.dw) return PMOE_ERR_ARG;
+    return wgrad_go<conv_wgrad_bnbwd_kernel>(p, st, BnBwdFuse{bn.z, bn.coef, bn.c1, bn.c2, bn.z_ld, p.a.Cout});
+}
+
+int conv_wgrad_launch(const WgradArgs& a, int dtype, const WgradBn& bn, hipStream_t st) {
+    WgradPlan p;
+    if (wgrad_select(a, dtype, bn, &p) < 0) return p.code;
+    if (p.ws_floats > 0 && (!a.part || a.part_floats < p.ws_floats)) return PMOE_ERR_ARG;
+    const int rc = p.kind == WGRAD_BNBWD ? conv_wgrad_bnbwd_launch(p, bn, st)
+                 : p.kind == WGRAD_DMA2 ? wgrad_dma2_launch(p, st)
+                 : p.kind == WGRAD_DMA ? wgrad_dma_launch(p, st)
+                 : p.esz == 2 ? wgrad_tile_launch<bf16>(p, st) : wgrad_tile_launch<float>(p, st);
+    return rc ? rc : wgrad_finish(p, st);
+}
+
+// the deferred tail (WgradArgs.defer_fold): the K-split count is the one the launch used (the same selection)
+int conv_wgrad_fold(const WgradArgs& a, int dtype, const WgradBn& bn, hipStream_t st) {
+    WgradPlan p;
+    if (wgrad_select(a, dtype, bn, &p) < 0) return p.code;
+    if (p.ws_floats > 0 && (!a.part || a.part_floats < p.ws_floats)) return PMOE_ERR_ARG;
+    return wgrad_finish(p, st, true);
+}
+
+// which kernel a descriptor runs on: 7009 = conv_wgrad_dma_kernel (7109: its <= 32-input-channel wave layout), 7309 =
+// conv_wgrad_dma2_kernel, 7209 = conv_wgrad_bnbwd_kernel; 6000 + taps * 100 + MAXV = conv_wgrad_kernel<T, taps, MAXV>
+int conv_wgrad_plan(const WgradArgs& a, int dtype, const WgradBn& bn) {
+    WgradPlan p;
+    return wgrad_select(a, dtype, bn, &p);
+}
+
+// the size of the K-split workspace the launch needs (0: none)
+long long conv_wgrad_ws_floats(const WgradArgs& a, int dtype, const WgradBn& bn) {
+    WgradPlan p;
+    return wgrad_select(a, dtype, bn, &p) < 0 ? p.code : p.ws_floats;
 }

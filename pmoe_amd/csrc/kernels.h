@@ -123,10 +123,37 @@ int conv_dma_launch(const ConvLaunch& l, hipStream_t st);
 int conv_igemm_launch(const ConvArgs& a, int dtype, hipStream_t st);
 int conv_igemm_mblocks(const ConvArgs& a, int dtype);
 int conv_igemm_plan(const ConvArgs& a, int dtype);
-int conv_wgrad_launch(const WgradArgs& a, int dtype, hipStream_t st);
-int conv_wgrad_fold(const WgradArgs& a, int dtype, hipStream_t st);
-long long conv_wgrad_ws_floats(const WgradArgs& a, int dtype);
-int conv_wgrad_plan(const WgradArgs& a, int dtype);
-// per-image filter gradient with the BatchNorm backward applied on load (conv_wgrad.hip, round 4)
-int conv_wgrad_bnbwd_launch(WgradArgs a, const void* z, int z_ld, const float* coef, const float* c1, const float* c2,
-                            int dtype, hipStream_t st, bool plan);
+
+// the kernel families a weight-gradient launch can run on
+enum WgradKind { WGRAD_TILE = 1, WGRAD_DMA, WGRAD_DMA2, WGRAD_BNBWD };
+
+// pmoe_wgrad_desc.bn_fused: the per-image filter gradient with the BatchNorm backward applied on load (conv_wgrad_bnbwd_kernel,
+// round 4).  `fused` and `z_ld` take part in the selection; the pointers are read by the launch only.
+struct WgradBn {
+    int fused, z_ld;
+    const void* z;
+    const float *coef, *c1, *c2;
+};
+
+// What wgrad_select decided for a descriptor: the family, the descriptor the kernel receives (tile fields, mb_per_wg and
+// slice_fastest filled in) and what that family's launcher needs to pick the instantiation.  The launch, the deferred fold, the plan
+// code and the workspace size all read this one plan.
+struct WgradPlan {
+    int kind;              // WgradKind
+    int code;              // pmoe_conv2d_wgrad_plan code, or a PMOE_ERR_* (< 0): nothing runs
+    WgradArgs a;
+    int esz, maxv;         // TILE: conv_wgrad_kernel<T, taps, MAXV> (esz = sizeof(T))
+    int pin, wci, pairs, req;      // DMA: conv_wgrad_dma_kernel<PIN, WCI, PAIRS, REQ>
+    int ahead;             // DMA2: conv_wgrad_dma2_kernel<a.lTW, AHEAD>
+    dim3 grid, block;
+    size_t smem;           // dynamic LDS bytes of the launch
+    int mpw, mph;          // DMA / DMA2: magic numbers of the piece decode
+    int E, taps, nsplit;   // experts, filter taps, K-split slabs the launch writes (the fold sums them)
+    long long ws_floats;   // pmoe_conv2d_wgrad_ws_floats: nsplit slabs, 0 if the launch writes dw itself
+};
+int wgrad_select(const WgradArgs& a, int dtype, const WgradBn& bn, WgradPlan* p);      // -> p->code
+
+int conv_wgrad_launch(const WgradArgs& a, int dtype, const WgradBn& bn, hipStream_t st);
+int conv_wgrad_fold(const WgradArgs& a, int dtype, const WgradBn& bn, hipStream_t st);
+long long conv_wgrad_ws_floats(const WgradArgs& a, int dtype, const WgradBn& bn);
+int conv_wgrad_plan(const WgradArgs& a, int dtype, const WgradBn& bn);

@@ -199,13 +199,14 @@ def conv2d_wgrad(x, dy, dw_ws, *, cin, cout, cinp, coutp, ipe, ks, stride, pad, 
         d.grads, d.cout_real, d.cin_real = ptr(grads, "grads", torch.float32), int(grads_cout), int(grads_cin)
     if bn_fuse is not None and plan_only:       # -> 7209 if the fused kernel serves this shape, else a negative error code
         return load().pmoe_conv2d_wgrad_plan(C.byref(d))
-    if dw_ws.numel() < (n if per_image else n // ipe) * ks * ks * coutp * cinp:
+    slab = (n // ipe) * ks * ks * coutp * cinp          # one [E][taps][coutp][cinp] gradient: dw_ws, and each K-split slab
+    if dw_ws.numel() < (n * ks * ks * coutp * cinp if per_image else slab):
         raise ValueError("conv2d_wgrad: workspace too small")
     need = load().pmoe_conv2d_wgrad_ws_floats(C.byref(d))
     if need < 0:
         check(int(need), "pmoe_conv2d_wgrad_ws_floats")
-    if plan_only:                    # number of K-split slices (workgroups along the pixel axis) the launch would use
-        return max(1, need // ((n // ipe) * ks * ks * coutp * cinp))
+    if plan_only:                    # number of K-split slices (workgroups along the pixel axis) the launch would use: the
+        return max(1, need // slab)  # selection reports it as the size of its `nsplit` slabs (0: the launch writes dw_ws itself)
     if need > 0:
         part = _wgrad_part_ws(x.device, need)
         d.part_ws, d.part_ws_floats = ptr(part, "part_ws"), part.numel()
@@ -381,9 +382,8 @@ def stem_tail_pool(z2, y, argmax, sc2, sh2, sc1, sh1, mu2, mu1, ipe):
 def stem_tail_bwd(phase, z2, dpool, argmax, dz2, consts, part, nparts, E, ipe):
     """consts: list of 12 f32 [E,C] tensors (or None): sc2 sh2 sc1 sh1 mu1 is1 mu2 is2 c11 c21 c12 c22."""
     n, h, w_, c = _nhwc(z2, "z2")
-    arr = (C.c_void_p * 12)(*[t.data_ptr() if t is not None else None for t in consts])
     check(load().pmoe_stem_tail_bwd(phase, ptr(z2, "z2"), ptr(dpool, "dpool", z2.dtype),
-                                    ptr(argmax, "argmax", torch.uint8), ptr(dz2, "dz2", z2.dtype), arr,
+                                    ptr(argmax, "argmax", torch.uint8), ptr(dz2, "dz2", z2.dtype), _consts12(consts),
                                     ptr(part, "part", torch.float32), nparts, E, ipe, h, w_, c, dt(z2), stream_ptr()),
           "pmoe_stem_tail_bwd")
 

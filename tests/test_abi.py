@@ -217,6 +217,126 @@ def test_wgrad_plan_reports_the_kernel_instantiation():
     assert 6000 <= plan(64, 64, 128, 128, 3, 2) < 7000
 
 
+WGRAD_SWEEP = REPO / "tests" / "golden" / "wgrad_select.json"
+WGRAD_SWEEP_ENVS = ("", "PMOE_WGRAD_DMA=0", "PMOE_WGRAD_V2=0", "PMOE_WGRAD_NARROW=0", "PMOE_WGRAD_PIPE=0")
+_WGRAD_MAPS = ((4, 4), (8, 8), (16, 16), (32, 32), (64, 64), (128, 128), (256, 256), (40, 24), (71, 55), (13, 9), (7, 10),
+               (256, 8), (200, 6), (32, 8))             # (the last three: output rows of <= 8 pixels, many of them)
+WGRAD_SWEEP_EXEMPT_ROWS = 949                           # of the fixture's 1915 (test_wgrad_selection_table_is_the_recorded_one)
+
+
+def _wgrad_sweep_descriptors():
+    """(dtype, ks, stride, H, W, cin, ipe, E, per_image, bn_fused): every 14th row, by a multiplicative hash of its index, of
+    the full cross (26880 rows; the fixture has to stay small)."""
+    import itertools
+    cross = itertools.product((0, 1), ((1, 1), (1, 2), (3, 1), (3, 2)), _WGRAD_MAPS, (16, 32, 64, 128, 256, 512),
+                              (1, 2, 5, 64, 512), (1, 4), (0, 1), (0, 1))
+    for i, (dtype, (ks, stride), (H, W), cin, ipe, E, per_image, bn_fused) in enumerate(cross):
+        if (((i * 2654435761) & 0xFFFFFFFF) >> 16) % 14 == 0:
+            yield (dtype, ks, stride, H, W, cin, ipe, E, per_image, bn_fused)
+
+
+def _wgrad_desc(dtype, ks, stride, H, W, cin, ipe, E, per_image, bn_fused, cout=None):
+    from pmoe_amd.hip import WgradDesc
+    d = WgradDesc()
+    cout = cout or max(cin, 64)
+    ckw, pad = (64 if dtype == 0 else 32), ks // 2
+    d.n, d.h, d.w_, d.cin, d.cinp = E * ipe, H, W, cin, (cin + ckw - 1) // ckw * ckw
+    d.ho, d.wo = (H + 2 * pad - ks) // stride + 1, (W + 2 * pad - ks) // stride + 1
+    d.cout, d.coutp = cout, (cout + ckw - 1) // ckw * ckw
+    d.x_ld, d.dy_ld, d.ipe, d.ks, d.stride, d.pad, d.dtype = cin, cout, ipe, ks, stride, pad, dtype
+    d.per_image, d.bn_fused, d.bn_z_ld = per_image, bn_fused, cout
+    return d
+
+
+def _wgrad_plan_and_size(row):
+    import ctypes as C
+    from pmoe_amd.hip import load
+    d = _wgrad_desc(*row)
+    return [load().pmoe_conv2d_wgrad_plan(C.byref(d)), load().pmoe_conv2d_wgrad_ws_floats(C.byref(d))]
+
+
+def _wgrad_record_sweep(monkeypatch_setenv):
+    """-> the fixture's content: the default answers per row, and per switch only the rows it changes"""
+    rows = list(_wgrad_sweep_descriptors())
+    base = [_wgrad_plan_and_size(r) for r in rows]
+    diffs = {}
+    for env in WGRAD_SWEEP_ENVS[1:]:
+        monkeypatch_setenv(*env.split("="))
+        got = [_wgrad_plan_and_size(r) for r in rows]
+        monkeypatch_setenv(env.split("=")[0], None)
+        diffs[env] = {str(i): g for i, (g, b) in enumerate(zip(got, base)) if g != b}
+    return {"fields": "dtype ks stride H W cin ipe E per_image bn_fused plan ws_floats",
+            "rows": [list(r) + b for r, b in zip(rows, base)], "switch_changes": diffs}
+
+
+def test_wgrad_selection_table_is_the_recorded_one(lib, monkeypatch):
+    """pmoe_conv2d_wgrad_plan / pmoe_conv2d_wgrad_ws_floats over a sweep of descriptors (bf16 and f32, 1x1 and 3x3, both strides,
+    4 x 4 to 256 x 256 and ragged maps, 16..512 channels, 1..512 images per expert, per-image and BatchNorm-fused forms), with the
+    switches at their defaults and with PMOE_WGRAD_DMA / _V2 / _NARROW / _PIPE = 0: row by row the answers recorded in
+    tests/golden/wgrad_select.json.
+
+    The fixture was recorded from the library of commit 22a9f0b (the last one with the selection inside wgrad_dtype<T>), with
+    this module's _wgrad_record_sweep: ``json.dump(_wgrad_record_sweep(setenv), open(WGRAD_SWEEP, "w"))`` where setenv(name, value)
+    sets os.environ[name] (value None: removes it).
+
+    One class of rows differs on purpose: a bn_fused descriptor that conv_wgrad_bnbwd_kernel does not serve (its plan is a
+    PMOE_ERR_*).  The launch refuses it with that code; the size query used to answer 0 for every bn_fused descriptor and now
+    answers the launch's code.  The exempt rows are exactly the fixture's rows with bn_fused = 1, plan < 0 and size 0, and their
+    number is pinned."""
+    import json
+    fx = json.loads(WGRAD_SWEEP.read_text())
+    rows = [tuple(r[:10]) for r in fx["rows"]]
+    assert rows == list(_wgrad_sweep_descriptors())
+    exempt = 0
+    for env in WGRAD_SWEEP_ENVS:
+        if env:
+            monkeypatch.setenv(*env.split("="))
+        changed = fx["switch_changes"].get(env, {})
+        for i, r in enumerate(fx["rows"]):
+            plan, ws = changed.get(str(i), r[10:])
+            if r[9] and plan < 0:
+                assert ws == 0
+                ws = plan
+                exempt += not env
+            assert _wgrad_plan_and_size(rows[i]) == [plan, ws], (env, rows[i], plan, ws)
+        if env:
+            monkeypatch.delenv(env.split("=")[0])
+    assert exempt == WGRAD_SWEEP_EXEMPT_ROWS
+    # the sweep reaches every kernel family and both failure codes
+    codes = {r[10] for r in fx["rows"]} | {v[0] for c in fx["switch_changes"].values() for v in c.values()}
+    assert {7009, 7109, 7209, 7309, 6106, 6906, 6910, 6112, 6912, 6920, hip.ERR_UNSUPPORTED} <= codes, sorted(codes)
+
+
+def test_wgrad_queries_answer_what_the_launch_does(lib):
+    """Plan, size and fold go through the launch's own selection.  Three places where they once answered differently:"""
+    import ctypes as C
+    fused_ok = _wgrad_desc(0, 3, 1, 32, 32, 16, 2, 2, 1, 1)
+    assert (lib.pmoe_conv2d_wgrad_plan(C.byref(fused_ok)), lib.pmoe_conv2d_wgrad_ws_floats(C.byref(fused_ok))) == (7209, 0)
+    # 1. the size of a bn_fused descriptor that the fused kernel refuses is that refusal, not "no scratch needed"
+    for bad in (_wgrad_desc(0, 3, 1, 32, 32, 64, 2, 2, 1, 1), _wgrad_desc(0, 3, 1, 32, 32, 16, 2, 2, 0, 1),
+                _wgrad_desc(1, 3, 1, 32, 32, 16, 2, 2, 1, 1), _wgrad_desc(0, 3, 1, 8, 8, 16, 2, 2, 1, 1)):
+        assert lib.pmoe_conv2d_wgrad_plan(C.byref(bad)) == lib.pmoe_conv2d_wgrad_ws_floats(C.byref(bad)) == hip.ERR_UNSUPPORTED
+    bad = _wgrad_desc(0, 3, 1, 32, 32, 16, 2, 2, 1, 1)
+    bad.bn_z_ld = 60                                            # (rows of z not 16-byte aligned)
+    assert lib.pmoe_conv2d_wgrad_plan(C.byref(bad)) == lib.pmoe_conv2d_wgrad_ws_floats(C.byref(bad)) == hip.ERR_ARG
+    # 2. the fold of a per_image descriptor has nothing to do (no launch: runs without a GPU), but only for a descriptor that the
+    #    launch accepts -- it used to answer 0 before looking at it
+    per_image = _wgrad_desc(0, 3, 1, 32, 32, 64, 2, 2, 1, 0)
+    per_image.dw_ws = 0x1000
+    assert lib.pmoe_conv2d_wgrad_fold(C.byref(per_image), None) == 0
+    fused_ok.dw_ws = 0x1000
+    assert lib.pmoe_conv2d_wgrad_fold(C.byref(fused_ok), None) == 0
+    per_image.cinp = 128                                        # (the tiles would not cover dw exactly)
+    assert lib.pmoe_conv2d_wgrad_fold(C.byref(per_image), None) == lib.pmoe_conv2d_wgrad_plan(C.byref(per_image)) == hip.ERR_ARG
+    two_per_tile = _wgrad_desc(0, 3, 1, 8, 8, 64, 2, 2, 1, 0)   # (8 x 8 maps: four images per pixel block, not one workgroup per image)
+    two_per_tile.dw_ws = 0x1000
+    assert lib.pmoe_conv2d_wgrad_fold(C.byref(two_per_tile), None) == hip.ERR_UNSUPPORTED
+    # 3. a bn_fused descriptor is the fused kernel's or nobody's in EVERY call: the fold once planned it as a plain one
+    not_fused = _wgrad_desc(0, 3, 1, 32, 32, 64, 2, 2, 0, 1)
+    not_fused.dw_ws = 0x1000
+    assert lib.pmoe_conv2d_wgrad_fold(C.byref(not_fused), None) == hip.ERR_UNSUPPORTED
+
+
 def test_launch_recorder_is_transparent_for_planning_calls():
     """hip.LaunchRecorder (pmoe_amd/infer.py:PlannedMixture): planning / query entry points pass through unrecorded, and the
     proxy is only in place while a recorder is active."""

@@ -4,6 +4,7 @@ the same op, called through the same ctypes binding the model uses.
 Tolerances: f32 kernels 1e-4 (exact-f32 MFMA chains vs CPU summation order); bf16 kernels 1e-2
 relative to the tensor's scale with the inputs pre-rounded to bf16 (north_star: 1e-4 fp32 / 1e-2 bf16).
 """
+import ctypes
 import math
 
 import pytest
@@ -98,8 +99,8 @@ CONV_CASES = [
 
 def _conv_case(case, dtype, plan=None):
     """forward (+ fused BatchNorm partial sums), data gradient, weight gradient of one grouped conv against CPU fp32 autograd.
-    ``plan`` = (forward code, data-gradient code, weight-gradient K-split x channel-tile pairs): asserted BEFORE running, so
-    a routing change cannot silently move a shape off the kernel this case exists to cover."""
+    ``plan`` = (forward code, data-gradient code, weight-gradient K-split x channel-tile pairs[, weight-gradient code]): asserted
+    BEFORE running (None: not pinned), so a routing change cannot silently move a shape off the kernel this case exists to cover."""
     E, ipe, cin, cout, H, W, ks, stride = case
     g = torch.Generator().manual_seed(hash(case) & 0xFFFF)
     pad = ks // 2
@@ -123,7 +124,7 @@ def _conv_case(case, dtype, plan=None):
     stats = torch.zeros(rows, 2, coutp, device=DEV)
     if plan is not None:
         got = ops.conv2d(xd, wf, out, cin=cinp, cout=cout, coutp=coutp, ipe=ipe, ks=ks, stride=stride, pad=pad, plan_only=True)
-        assert got == plan[0], f"forward routed to kernel code {got}, this case is meant for {plan[0]}"
+        assert plan[0] is None or got == plan[0], f"forward routed to kernel code {got}, this case is meant for {plan[0]}"
     ops.conv2d(xd, wf, out, cin=cinp, cout=cout, coutp=coutp, ipe=ipe, ks=ks, stride=stride, pad=pad, stats=stats)
     y = from_nhwc(out, cout)
     close(y, yr.detach(), dtype, "conv fwd")
@@ -169,6 +170,12 @@ def _conv_case(case, dtype, plan=None):
         nsplit = ops.conv2d_wgrad(xd, dyd, ws_buf, cin=cinp, cout=r16(cout), cinp=cpw, coutp=cow, ipe=ipe, ks=ks, stride=stride,
                                   pad=pad, plan_only=True)
         assert plan[2] is None or nsplit * E * (cow // ckw) * (cpw // ckw) == plan[2], (nsplit, plan[2])
+        if len(plan) > 3:
+            d = hip.WgradDesc()
+            d.n, d.h, d.w_, d.cin, d.cinp, d.ho, d.wo, d.cout, d.coutp = N, H, W, cinp, cpw, Ho, Wo, r16(cout), cow
+            d.x_ld, d.dy_ld, d.ipe, d.ks, d.stride, d.pad, d.dtype = cinp, r16(cout), ipe, ks, stride, pad, ops.dt(xd)
+            got = hip.load().pmoe_conv2d_wgrad_plan(ctypes.byref(d))
+            assert got == plan[3], f"weight gradient routed to kernel code {got}, this case is meant for {plan[3]}"
     ops.conv2d_wgrad(xd, dyd, ws_buf, cin=cinp, cout=r16(cout), cinp=cpw, coutp=cow, ipe=ipe, ks=ks, stride=stride, pad=pad)
     grads = torch.empty(E, cout, cin, ks, ks, device=DEV)
     ops.unpack_conv_wgrad(ws_buf, grads, E, cout, cin, ks, cow, cpw)
@@ -412,6 +419,27 @@ def test_conv_dma_persistent_stream(monkeypatch, case):
         outs.append((y, st))
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
 
+
+
+# The smallest shape of each branch of the weight-gradient launchers (csrc/conv_wgrad.hip: wgrad_select picks, one launcher per
+# kernel family maps the plan to the instantiation), pinned to the code pmoe_conv2d_wgrad_plan reported before the selection
+# became one function.  Two images of one expert: a K-split over more than one workgroup, then the fold.
+WGRAD_BRANCH_CASES = [
+    # (E, ipe, cin, cout, H, W, ks, stride), dtype, weight-gradient code
+    ((1, 2, 64, 64, 32, 32, 3, 1), torch.bfloat16, 7309),      # conv_wgrad_dma2_kernel<5>: 32 x 8 pixel tiles
+    ((1, 2, 64, 64, 16, 16, 3, 1), torch.bfloat16, 7309),      # conv_wgrad_dma2_kernel<4>: 16 x 16
+    ((1, 2, 64, 64, 32, 8, 3, 1), torch.bfloat16, 7009),       # conv_wgrad_dma_kernel<1, 2, false, 1>: 8-pixel rows, the wide layout
+    ((1, 2, 16, 64, 32, 32, 3, 1), torch.bfloat16, 7109),      # conv_wgrad_dma_kernel<1, 1, true>: <= 16 input channels, tap pairs
+    ((1, 2, 32, 64, 32, 32, 3, 1), torch.bfloat16, 7109),      # conv_wgrad_dma_kernel<1, 1>: 32 input channels
+    ((1, 2, 64, 128, 32, 32, 3, 2), torch.bfloat16, 6910),     # conv_wgrad_kernel<bf16, 9, 10>: 3x3 stride 2
+    ((1, 2, 64, 128, 32, 32, 1, 1), torch.bfloat16, 6106),     # conv_wgrad_kernel<bf16, 1, 6>: 1x1
+    ((1, 2, 64, 64, 32, 32, 3, 1), torch.float32, 6912),       # conv_wgrad_kernel<float, 9, 12>
+]
+
+
+@pytest.mark.parametrize("case,dtype,code", WGRAD_BRANCH_CASES)
+def test_conv_wgrad_launcher_branches(case, dtype, code):
+    _conv_case(case, dtype, (None, None, None, code))
 
 
 @pytest.mark.parametrize("req", ["0", "2"])
