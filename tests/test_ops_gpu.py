@@ -1091,9 +1091,9 @@ def test_batchnorm_statistics_are_centred():
 @pytest.mark.parametrize("shape", [(2, 3, 75, 53), (1, 2, 64, 96), (3, 1, 17, 8)])
 def test_stem_tail_row_walking_kernels_match_gather_kernels(dtype, shape, monkeypatch):
     """stem_tail_pool_walk_kernel / stem_tail_dz_walk_kernel (each z2 element loaded and evaluated once, taps as max-keys / SWAR
-    bytes) against the per-output gather kernels they replace (PMOE_STEM_WALK=0, themselves checked against the unfused chain in
-    test_model_gpu): pooled output and winning taps bit-identical, dz2 within one rounding of the output type; odd sizes, image
-    and expert boundaries."""
+    bytes), in both widths (PMOE_STEM_WALK_KO = 2 and 4), against the per-output gather kernels they replace (PMOE_STEM_WALK=0,
+    themselves checked against a float64 reference of their own operation in test_stem_tail_gpu.py): pooled output and winning taps
+    bit-identical, dz2 within one rounding of the output type; odd sizes, image and expert boundaries."""
     E, B, H, W = shape
     C_, N = 64, E * B
     g = torch.Generator().manual_seed(11)
@@ -1105,19 +1105,21 @@ def test_stem_tail_row_walking_kernels_match_gather_kernels(dtype, shape, monkey
     consts = [sc2, sh2, sc1, sh1, mu1, is1, mu2, is2, u(-.01, .01), u(-.01, .01), u(-.01, .01), u(-.01, .01)]
     part = torch.empty(E, 4, 2, C_, device=DEV)
     out = {}
-    for walk in ("0", "1"):
+    for walk, ko in (("0", "2"), ("1", "2"), ("1", "4")):
         monkeypatch.setenv("PMOE_STEM_WALK", walk)
+        monkeypatch.setenv("PMOE_STEM_WALK_KO", ko)
         y = torch.full((N, Ho, Wo, C_), 7.0, dtype=dtype, device=DEV)
         am = torch.full((N, Ho, Wo, C_), 99, dtype=torch.uint8, device=DEV)
         dz = torch.full_like(z2, 7.0)
         ops.stem_tail_pool(z2, y, am, sc2, sh2, sc1, sh1, mu2, mu1, B)
         ops.stem_tail_bwd(3, z2, dp, am, dz, consts, part, 4, E, B)
-        out[walk] = (y, am, dz)
-    assert torch.equal(out["1"][0], out["0"][0]) and torch.equal(out["1"][1], out["0"][1])
-    assert int(out["0"][1].max()) <= 0x88
-    a, b = out["1"][2].float(), out["0"][2].float()
+        out[walk + ko] = (y, am, dz)
+    assert int(out["02"][1].max()) <= 0x88
     ulp = 2.0 ** -7 if dtype == torch.bfloat16 else 2.0 ** -21
-    assert ((a - b).abs() <= ulp * b.abs().clamp_min(1e-3)).all()
+    for walked in ("12", "14"):
+        assert torch.equal(out[walked][0], out["02"][0]) and torch.equal(out[walked][1], out["02"][1])
+        a, b = out[walked][2].float(), out["02"][2].float()
+        assert ((a - b).abs() <= ulp * b.abs().clamp_min(1e-3)).all()
 
 
 def test_conv_c16_shared_input_and_stats_shape_guard():
