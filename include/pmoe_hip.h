@@ -253,7 +253,9 @@ int pmoe_act_bwd(const void* dy, const void* y, void* dx, int64_t n, int32_t act
  * rows = N*H*W activations of C channels; expert e owns rows [e*rows_per_expert, ...).            */
 /* per-(expert,channel) partial sums: part [E][nparts][2][C] f32 of (x - c) and (x - c)^2, where c = the channel's
  * value in the expert's first row, written to shiftc [E][C] (null: c = 0, plain sums).  Summing deviations from a
- * sample keeps the variance exact-to-rounding even when |mean| >> std. */
+ * sample keeps the variance exact-to-rounding even when |mean| >> std.  x is dense (ld <= 0 or C) or the channel
+ * window [coff, coff + C) of rows ld wide; PMOE_ERR_ARG unless ld, coff are multiples of the 16-byte vector,
+ * coff + C <= ld, rows_per_expert >= 1 and E >= 1. */
 int pmoe_colstats(const void* x, int64_t rows_per_expert, int32_t E, int32_t C, int32_t ld, int32_t coff,
                   float* part, int32_t nparts, float* shiftc, int32_t dtype, void* stream);
 /* deterministic tree step: part_in [E][nin][W] -> part_out [E][nout][W] (W = 2*C floats) */

@@ -98,7 +98,9 @@ static int colstats_launch(const void* x, const void* dy, const void* y, const f
                            const float* scale, const float* shift, long long rpe, int E, int C, int ld, int coff, int relu, float* part, int nparts, int mode,
                            float* shiftc, hipStream_t st, void* gmask = nullptr) {
     constexpr int VE = 16 / (int)sizeof(T);
-    if (C % VE || !pow2(C / VE) || C / VE > 256 || nparts < 1) return PMOE_ERR_ARG;
+    if (C % VE || !pow2(C / VE) || C / VE > 256 || nparts < 1 || rpe < 1 || E < 1) return PMOE_ERR_ARG;
+    if (ld <= 0) { ld = C; coff = 0; }                                       // dense, as pmoe_bn_apply reads y_ld
+    if (ld % VE || coff < 0 || coff % VE || coff + C > ld) return PMOE_ERR_ARG;   // 16-byte loads from a window inside the row
     dim3 grid(nparts, E), block(256);
     if (mode == 0)
         hipLaunchKernelGGL((colstats_kernel<T, 0>), grid, block, 0, st, (const T*)x, nullptr, nullptr, nullptr, nullptr,
