@@ -67,7 +67,7 @@ int pmoe_version(void);
 const char* pmoe_error_string(int code);
 /* sizeof() of the descriptor structs as compiled (which: 0 = pmoe_conv_desc, 1 = pmoe_wgrad_desc);
  * lets a foreign-language binding verify its struct layout without launching anything */
-int pmoe_abi_sizeof(int which); /* 0: pmoe_conv_desc, 1: pmoe_wgrad_desc, 2: pmoe_opt_tensor */
+int pmoe_abi_sizeof(int which); /* 0: pmoe_conv_desc, 1: pmoe_wgrad_desc, 2: pmoe_opt_tensor, 3: pmoe_opt_pack */
 
 /* ---- convolution / grouped GEMM -------------------------------------------------------------
  * Replaces nn.Conv2d in model/blocks/basics.py:93-100,113-120 (stem), the torchvision ResNet body
@@ -541,6 +541,32 @@ int pmoe_mt_grad_norm(const pmoe_opt_tensor* table, const int32_t* chunk_tensor,
 int pmoe_mt_adam(const pmoe_opt_tensor* table, const int32_t* chunk_tensor, const int32_t* chunk_index, int32_t n_chunks,
                  float lr, float beta1, float beta2, float eps, float weight_decay, int32_t amsgrad, float bc1_all,
                  float bc2_sqrt_all, const float* norm, void* stream);
+/* The same update for parameters whose values the engine also keeps PACKED (pmoe_pack_conv_weights / pmoe_pack_bias): the
+ * launch stores every updated weight W[co][ci][tp] of table row i, converted to packs[i].dtype, into
+ *   fwd [(row0 + co) * taps + tp][ci]                      (rows of cinp elements), and, where dgrd != NULL,
+ *   dgrd[ci * taps + (taps - 1 - tp)][col0 + co]           (rows of dgrd_ld elements),
+ * so the packs stay current without a repack.  A bias is cin = taps = cinp = 1 with an f32 fwd and no dgrd.  Padding rows and
+ * columns are never written.  Parameters and moments come out bit-identical to pmoe_mt_adam.  Workgroup i handles the tile
+ * co in [tile_co0[i], + tco), ci in [tile_ci0[i], + tci), all taps, of tensor tile_tensor[i]; tco * ((min(tci, cin) * taps) | 1)
+ * <= PMOE_OPT_PACK_STAGE (the tile is staged in LDS), every tile lies inside its tensor and the tiles of a tensor cover it
+ * exactly once.  Offsets inside one tensor and one pack are 32-bit. */
+#define PMOE_OPT_PACK_STAGE 4640
+typedef struct pmoe_opt_pack {
+    void* fwd;             /* expert e's forward operand (or bias panel), element type `dtype` */
+    void* dgrd;            /* expert e's data-gradient operand, or NULL */
+    int32_t cout, cin, taps;
+    int32_t dtype;         /* PMOE_DT_* of fwd / dgrd */
+    int32_t cinp;          /* row length of fwd */
+    int32_t row0;          /* first fwd row of this tensor (a part of a fused head: its row window) */
+    int32_t dgrd_ld;       /* row length of dgrd */
+    int32_t col0;          /* first dgrd column of this tensor */
+    int32_t tco, tci;      /* tile extent along co / ci */
+    int32_t reserved[2];
+} pmoe_opt_pack;
+int pmoe_mt_adam_packs(const pmoe_opt_tensor* table, const pmoe_opt_pack* packs, const int32_t* tile_tensor,
+                       const int32_t* tile_co0, const int32_t* tile_ci0, int32_t n_tiles, float lr, float beta1, float beta2,
+                       float eps, float weight_decay, int32_t amsgrad, float bc1_all, float bc2_sqrt_all, const float* norm,
+                       void* stream);
 /* swa = param (n_averaged == 0) or swa + (param - swa) / (n_averaged + 1) */
 int pmoe_mt_swa_update(const pmoe_opt_tensor* table, const int32_t* chunk_tensor, const int32_t* chunk_index,
                        int32_t n_chunks, int64_t n_averaged, void* stream);

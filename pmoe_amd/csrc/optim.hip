@@ -1,6 +1,6 @@
 // Fused optimizer tail of the stage-2 step (reference trainer/train_2.py:157-165,184):
 //   clip_grad_norm_(params, max_norm)  ->  global L2 norm over ~620 gradient tensors + one scale
-//   Adam(amsgrad=True).step()          ->  one multi-tensor update
+//   Adam(amsgrad=True).step()          ->  one multi-tensor update (optionally also writing the engine's packed operands)
 //   AveragedModel.update_parameters()  ->  one multi-tensor running mean
 // The reference issues a handful of launches (and a .item() sync) PER parameter tensor; here each stage is one launch
 // over a chunk table: tensor t is cut into chunks of PMOE_OPT_CHUNK elements, workgroup i handles chunk
@@ -84,6 +84,81 @@ __global__ void __launch_bounds__(256) mt_scale_kernel(const pmoe_opt_tensor* __
 // torch.optim.Adam (single-tensor formulas of torch/optim/adam.py, maximize=False, capturable=False):
 //   g' = clip * g (+ wd * p);  m = m + (1-b1)(g' - m);  v = b2 v + (1-b2) g'^2;  vmax = max(vmax, v)
 //   p -= (lr / bc1) * m / (sqrt(vmax or v) / sqrt(bc2) + eps)
+struct AdamCoef {
+    float clip, weight_decay, beta1, beta2, eps, step_size, inv_bc2s;
+    int amsgrad;
+};
+
+// The one place the update is written: mt_adam_kernel and mt_adam_pack_kernel both call it, so that a parameter comes out with
+// the same bits whichever launch updates it and wherever in a launch it falls.  The roundings are spelled out and the compiler's
+// own contraction is off in here: left to itself it fused the expressions differently in the 16-byte loop and in the scalar
+// tail, so an element's last bit depended on the path it took.  The form is the one the 16-byte loop has always had.
+__device__ __forceinline__ float adam_upd(const AdamCoef& c, float gi, float pi, float& mi, float& vi, float& mx) {
+#pragma clang fp contract(off)
+    gi *= c.clip;
+    if (c.weight_decay != 0.f) gi = __builtin_fmaf(c.weight_decay, pi, gi);
+    mi = __builtin_fmaf(1.f - c.beta1, gi - mi, mi);
+    vi = __builtin_fmaf(vi, c.beta2, ((1.f - c.beta2) * gi) * gi);
+    float d = vi;
+    if (c.amsgrad) {
+        mx = fmaxf(mx, vi);
+        d = mx;
+    }
+    return __builtin_fmaf(-c.step_size, mi / __builtin_fmaf(sqrtf(d), c.inv_bc2s, c.eps), pi);
+}
+
+// bias corrections: one value for all tensors (kernel argument, > 0) or the per-tensor entries of the table
+__device__ __forceinline__ AdamCoef adam_coef(const pmoe_opt_tensor& t, float lr, float beta1, float beta2, float eps,
+                                              float weight_decay, int amsgrad, float bc1_all, float bc2s_all,
+                                              const float* norm) {
+    AdamCoef c;
+    c.clip = norm ? norm[1] : 1.f;
+    c.weight_decay = weight_decay;
+    c.beta1 = beta1;
+    c.beta2 = beta2;
+    c.eps = eps;
+    c.step_size = lr / (bc1_all > 0.f ? bc1_all : t.bc1);
+    c.inv_bc2s = 1.f / (bc2s_all > 0.f ? bc2s_all : t.bc2_sqrt);
+    c.amsgrad = amsgrad;
+    return c;
+}
+
+// n consecutive elements, one thread: 4 as 16-byte accesses (vec: the caller has checked the alignment), fewer one by one.
+// stage != nullptr also leaves the updated parameters there.
+__device__ __forceinline__ void adam_run(const AdamCoef& c, float* p, const float* g, float* m, float* v, float* vm, int n,
+                                         bool vec, float* stage) {
+    if (vec) {
+        f32x4 pv = *reinterpret_cast<f32x4*>(p), mv = *reinterpret_cast<f32x4*>(m);
+        f32x4 vv = *reinterpret_cast<f32x4*>(v);
+        const f32x4 gv = *reinterpret_cast<const f32x4*>(g);
+        f32x4 xv = c.amsgrad ? *reinterpret_cast<f32x4*>(vm) : vv;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float mi = mv[k], vi = vv[k], mx = xv[k];
+            pv[k] = adam_upd(c, gv[k], pv[k], mi, vi, mx);
+            mv[k] = mi; vv[k] = vi; xv[k] = mx;
+        }
+        *reinterpret_cast<f32x4*>(p) = pv;
+        *reinterpret_cast<f32x4*>(m) = mv;
+        *reinterpret_cast<f32x4*>(v) = vv;
+        if (c.amsgrad) *reinterpret_cast<f32x4*>(vm) = xv;
+        if (stage) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) stage[k] = pv[k];
+        }
+        return;
+    }
+    for (int i = 0; i < n; ++i) {
+        float mi = m[i], vi = v[i], mx = c.amsgrad ? vm[i] : 0.f;
+        const float pn = adam_upd(c, g[i], p[i], mi, vi, mx);
+        p[i] = pn;
+        m[i] = mi;
+        v[i] = vi;
+        if (c.amsgrad) vm[i] = mx;
+        if (stage) stage[i] = pn;
+    }
+}
+
 __global__ void __launch_bounds__(256) mt_adam_kernel(const pmoe_opt_tensor* __restrict__ tab,
                                                      const int32_t* __restrict__ chunk_tensor,
                                                      const int32_t* __restrict__ chunk_index, float lr, float beta1,
@@ -93,57 +168,113 @@ __global__ void __launch_bounds__(256) mt_adam_kernel(const pmoe_opt_tensor* __r
     const long long base = (long long)chunk_index[blockIdx.x] * CHUNK;
     long long n = t.numel - base;
     if (n > CHUNK) n = CHUNK;
-    const float clip = norm ? norm[1] : 1.f;
-    // bias corrections: one value for all tensors (kernel argument, > 0) or the per-tensor entries of the table
-    const float step_size = lr / (bc1_all > 0.f ? bc1_all : t.bc1);
-    const float inv_bc2s = 1.f / (bc2s_all > 0.f ? bc2s_all : t.bc2_sqrt);
+    const AdamCoef c = adam_coef(t, lr, beta1, beta2, eps, weight_decay, amsgrad, bc1_all, bc2s_all, norm);
     float* p = t.param + base;
     const float* g = t.grad + base;
     float* m = t.exp_avg + base;
     float* v = t.exp_avg_sq + base;
     float* vm = amsgrad ? t.max_exp_avg_sq + base : nullptr;
-    auto upd = [&](float gi, float pi, float& mi, float& vi, float& mx) -> float {
-        gi *= clip;
-        if (weight_decay != 0.f) gi += weight_decay * pi;
-        mi = mi + (1.f - beta1) * (gi - mi);
-        vi = vi * beta2 + (1.f - beta2) * gi * gi;
-        float d = vi;
-        if (amsgrad) {
-            mx = fmaxf(mx, vi);
-            d = mx;
-        }
-        return pi - step_size * (mi / (sqrtf(d) * inv_bc2s + eps));
-    };
     const bool aligned = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
                            reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(vm)) & 15) == 0;
     long long done = 0;
     if (aligned) {
         const long long nv = n >> 2;
-        for (long long i = threadIdx.x; i < nv; i += 256) {
-            f32x4 pv = *reinterpret_cast<f32x4*>(p + 4 * i), mv = *reinterpret_cast<f32x4*>(m + 4 * i);
-            f32x4 vv = *reinterpret_cast<f32x4*>(v + 4 * i);
-            const f32x4 gv = *reinterpret_cast<const f32x4*>(g + 4 * i);
-            f32x4 xv = amsgrad ? *reinterpret_cast<f32x4*>(vm + 4 * i) : vv;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                float mi = mv[k], vi = vv[k], mx = xv[k];
-                pv[k] = upd(gv[k], pv[k], mi, vi, mx);
-                mv[k] = mi; vv[k] = vi; xv[k] = mx;
-            }
-            *reinterpret_cast<f32x4*>(p + 4 * i) = pv;
-            *reinterpret_cast<f32x4*>(m + 4 * i) = mv;
-            *reinterpret_cast<f32x4*>(v + 4 * i) = vv;
-            if (amsgrad) *reinterpret_cast<f32x4*>(vm + 4 * i) = xv;
-        }
+        for (long long i = threadIdx.x; i < nv; i += 256)
+            adam_run(c, p + 4 * i, g + 4 * i, m + 4 * i, v + 4 * i, vm ? vm + 4 * i : nullptr, 4, true, nullptr);
         done = nv << 2;
     }
-    for (long long i = done + threadIdx.x; i < n; i += 256) {
-        float mi = m[i], vi = v[i], mx = amsgrad ? vm[i] : 0.f;
-        p[i] = upd(g[i], p[i], mi, vi, mx);
-        m[i] = mi;
-        v[i] = vi;
-        if (amsgrad) vm[i] = mx;
+    for (long long i = done + threadIdx.x; i < n; i += 256)
+        adam_run(c, p + i, g + i, m + i, v + i, vm ? vm + i : nullptr, 1, false, nullptr);
+}
+
+// ---- the same update, leaving the engine's packed operands current (include/pmoe_hip.h: pmoe_mt_adam_packs) -----------------
+// A workgroup owns one (co block) x (ci block) x (all taps) tile of one tensor.  In the parameter W[co][ci][tp] a tile row is one
+// contiguous run of cols * taps floats, so the update streams it exactly like mt_adam_kernel (16-byte accesses from the first
+// 16-byte boundary of each row on) and leaves the new values in LDS; the two operands are then written from LDS in THEIR
+// order: fwd [co][tp][ci] with ci across the lanes (runs of cols elements), dgrd [ci][taps-1-tp][co] with co across the lanes
+// (runs of rows elements) -- tiles of >= 16 x 16 channels make both runs >= 32 bytes in bf16.  A flat chunk of the parameter
+// would instead scatter the dgrd stores as isolated 2-byte writes.  The LDS row stride is odd: the dgrd pass reads a column.
+// All offsets are 32-bit (a tensor and one expert's pack are < 2^31 elements, checked by the caller).
+template <typename T>
+__device__ __forceinline__ void pack_store_tile(const pmoe_opt_pack& k, const float* stage, unsigned rs, unsigned co0,
+                                                unsigned ci0, unsigned rows, unsigned cols) {
+    const unsigned taps = (unsigned)k.taps;
+    const unsigned n = rows * cols * taps;
+    if (T* fwd = reinterpret_cast<T*>(k.fwd)) {
+        const unsigned row = (unsigned)k.row0 + co0;
+        for (unsigned i = threadIdx.x; i < n; i += 256) {
+            const unsigned ci = i % cols;
+            const unsigned t = i / cols;
+            const unsigned tp = t % taps;
+            const unsigned r = t / taps;
+            fwd[((row + r) * taps + tp) * (unsigned)k.cinp + ci0 + ci] = from_f32<T>(stage[r * rs + ci * taps + tp]);
+        }
     }
+    if (T* dgrd = reinterpret_cast<T*>(k.dgrd)) {
+        const unsigned col = (unsigned)k.col0 + co0;
+        for (unsigned i = threadIdx.x; i < n; i += 256) {
+            const unsigned r = i % rows;
+            const unsigned q = i / rows;           // = ci * taps + tp: the element's place in its LDS row
+            const unsigned tp = q % taps;
+            const unsigned ci = q / taps;
+            dgrd[((ci0 + ci) * taps + (taps - 1 - tp)) * (unsigned)k.dgrd_ld + col + r] = from_f32<T>(stage[r * rs + q]);
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) mt_adam_pack_kernel(const pmoe_opt_tensor* __restrict__ tab,
+                                                          const pmoe_opt_pack* __restrict__ packs,
+                                                          const int32_t* __restrict__ tile_tensor,
+                                                          const int32_t* __restrict__ tile_co0,
+                                                          const int32_t* __restrict__ tile_ci0, float lr, float beta1,
+                                                          float beta2, float eps, float weight_decay, int amsgrad,
+                                                          float bc1_all, float bc2s_all, const float* __restrict__ norm) {
+    __shared__ float stage[PMOE_OPT_PACK_STAGE];
+    const int ti = tile_tensor[blockIdx.x];
+    const pmoe_opt_tensor t = tab[ti];
+    const pmoe_opt_pack k = packs[ti];
+    const int co0 = tile_co0[blockIdx.x], ci0 = tile_ci0[blockIdx.x];
+    if (co0 < 0 || ci0 < 0 || co0 >= k.cout || ci0 >= k.cin || k.taps < 1 || k.tco < 1 || k.tci < 1) return;
+    const unsigned rows = (unsigned)min(k.tco, k.cout - co0), cols = (unsigned)min(k.tci, k.cin - ci0);
+    const unsigned len = cols * (unsigned)k.taps;              // one tile row: contiguous in the parameter
+    const unsigned rs = len | 1u;
+    if (rows * rs > (unsigned)PMOE_OPT_PACK_STAGE || (long long)k.cout * k.cin * k.taps != t.numel) return;
+    const AdamCoef c = adam_coef(t, lr, beta1, beta2, eps, weight_decay, amsgrad, bc1_all, bc2s_all, norm);
+    float* vm = amsgrad ? t.max_exp_avg_sq : nullptr;
+    const bool aligned = ((reinterpret_cast<uintptr_t>(t.param) | reinterpret_cast<uintptr_t>(t.grad) |
+                           reinterpret_cast<uintptr_t>(t.exp_avg) | reinterpret_cast<uintptr_t>(t.exp_avg_sq) |
+                           reinterpret_cast<uintptr_t>(vm)) & 15) == 0;
+    const unsigned row_stride = (unsigned)k.cin * (unsigned)k.taps;
+    const unsigned s0 = ((unsigned)co0 * (unsigned)k.cin + (unsigned)ci0) * (unsigned)k.taps;
+    // work units of a row: unit 0 = the elements before the row's first 16-byte boundary, units 1.. = one 16-byte group each,
+    // the last one the (shorter) rest
+    const unsigned upr = 1u + ((len + 3u) >> 2);
+    for (unsigned u = threadIdx.x; u < rows * upr; u += 256) {
+        const unsigned r = u / upr, j = u - r * upr;
+        const unsigned s = s0 + r * row_stride;
+        unsigned head = aligned ? ((4u - (s & 3u)) & 3u) : len;
+        if (head > len) head = len;
+        const unsigned nvec = (len - head) >> 2;
+        unsigned lo, n;
+        bool vec = false;
+        if (j == 0) {
+            lo = 0; n = head;
+        } else if (j - 1 < nvec) {
+            lo = head + 4u * (j - 1); n = 4; vec = true;
+        } else if (j - 1 == nvec) {
+            lo = head + 4u * nvec; n = len - lo;
+        } else {
+            continue;
+        }
+        const unsigned o = s + lo;
+        adam_run(c, t.param + o, t.grad + o, t.exp_avg + o, t.exp_avg_sq + o, vm ? vm + o : nullptr, (int)n, vec,
+                 stage + r * rs + lo);
+    }
+    __syncthreads();
+    if (k.dtype == PMOE_DT_BF16)
+        pack_store_tile<bf16>(k, stage, rs, (unsigned)co0, (unsigned)ci0, rows, cols);
+    else if (k.dtype == PMOE_DT_F32)
+        pack_store_tile<float>(k, stage, rs, (unsigned)co0, (unsigned)ci0, rows, cols);
 }
 
 // AveragedModel.update_parameters (torch/optim/swa_utils.py): first call copies, later p_avg += (p - p_avg) / (n + 1)
@@ -182,6 +313,16 @@ int pmoe_mt_adam(const pmoe_opt_tensor* table, const int32_t* chunk_tensor, cons
     if (n_chunks < 1 || !table) return PMOE_ERR_ARG;
     hipLaunchKernelGGL(mt_adam_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, table, chunk_tensor, chunk_index,
                        lr, beta1, beta2, eps, weight_decay, amsgrad, bc1_all, bc2_sqrt_all, norm);
+    return (int)hipGetLastError();
+}
+
+int pmoe_mt_adam_packs(const pmoe_opt_tensor* table, const pmoe_opt_pack* packs, const int32_t* tile_tensor,
+                       const int32_t* tile_co0, const int32_t* tile_ci0, int32_t n_tiles, float lr, float beta1, float beta2,
+                       float eps, float weight_decay, int32_t amsgrad, float bc1_all, float bc2_sqrt_all, const float* norm,
+                       void* stream) {
+    if (n_tiles < 1 || !table || !packs || !tile_tensor || !tile_co0 || !tile_ci0) return PMOE_ERR_ARG;
+    hipLaunchKernelGGL(mt_adam_pack_kernel, dim3(n_tiles), dim3(256), 0, (hipStream_t)stream, table, packs, tile_tensor,
+                       tile_co0, tile_ci0, lr, beta1, beta2, eps, weight_decay, amsgrad, bc1_all, bc2_sqrt_all, norm);
     return (int)hipGetLastError();
 }
 

@@ -13,6 +13,7 @@ path); the whole network is ONE ``torch.autograd.Function`` towards the outside,
 into one flat f32 arena in backward order, which is also the data-parallel all-reduce buffer
 (bucketed RCCL all-reduce launched while earlier layers are still in backward).
 """
+import collections
 import itertools
 import os
 
@@ -71,6 +72,9 @@ class Var:
     def window(self, coff, c):
         v = Var(self.t, c, coff, self.needs_grad, base=self if self.base is None else self.base)
         return v
+
+
+PackSinks = collections.namedtuple("PackSinks", "gen by_param")      # ExpertGroupEngine.pack_sinks
 
 
 class GroupedConv:
@@ -427,12 +431,73 @@ class ExpertGroupEngine:
         return self._ptr_tab[s:s + n]
 
     def _pack_all(self):
-        ver = sum(p._version for p in self.flat_params)
+        ver = self.param_version()
         if ver == self._packed_version:
             return
         for layer in self.all_convs:
             layer.pack()
         self._packed_version = ver
+
+    # ---- packs kept current by the optimizer (pmoe_amd.optim.FusedAdam(packs=...), csrc/optim.hip: mt_adam_pack_kernel)
+    def param_version(self):
+        """what ``_packed_version`` is compared with: the sum of the version counters of every parameter"""
+        return sum(p._version for p in self.flat_params)
+
+    def pack_sinks(self):
+        """Where the value of every packed parameter lives in the current banks: ``PackSinks(gen, by_param)`` with
+        ``by_param[id(p)] = (fwd pointer, dgrd pointer or 0, cout, cin, taps, PMOE_DT_* of the bank, cinp, fwd row offset, dgrd row
+        length, dgrd column offset)``, the pointers already at p's expert -- pmoe_opt_pack without its tile extents.  Covered: the
+        layers of ``all_convs`` ("w", "b") and the parts of a fused head ("w_part", "b_part": their row window of the head's
+        operands).  BatchNorm / ECA parameters have no pack; layers with derived packs keep their own version keys.  ``gen`` is
+        ``_build_gen``: the pointers are good until the banks are built again.
+
+        None = not eligible, pack as usual: before the banks exist, and while the fp8 policy is on (the e4m3 pack needs a row
+        maximum first: pack_w_fp8_kernel)."""
+        if self._built_for is None or self.fp8 or self._built_for[2]:
+            return None
+        cached = self.__dict__.get("_sinks")
+        if cached is not None and cached.gen == self._build_gen:
+            return cached
+        by_param = {}
+        plain = {id(l) for l in self.all_convs if type(l).pack is GroupedConv.pack}
+        fused = {id(p): l for l in self.all_convs if isinstance(l, FusedHead) for p in l.parts}
+        covered = set()
+        for kind, layer, plist in self.params:
+            if kind in ("w", "b") and id(layer) in plain:
+                host, r0, rows = layer, 0, layer.cout
+            elif kind in ("w_part", "b_part") and id(layer) in fused:
+                host, r0, rows = fused[id(layer)], layer.r0, layer.rows
+            else:
+                continue
+            if host.w_f8 is not None or host.w_fwd is None or len(plist) != self.E:
+                return None
+            covered.add(id(host))
+            for e, p in enumerate(plist):
+                if id(p) in by_param:
+                    return None                # one tensor packed in two places: leave it to the ordinary pack
+                if kind in ("w", "w_part"):
+                    dg = host.w_dg
+                    sink = (host.w_fwd[e].data_ptr(), dg[e].data_ptr() if dg is not None else 0, rows, host.cin, host.taps,
+                            hip._TORCH_DT[host.w_fwd.dtype], host.cinp, r0, host.dg_red if dg is not None else 0, r0)
+                else:
+                    sink = (host.bias_packed[e].data_ptr(), 0, rows, 1, 1, hip._TORCH_DT[F32], 1, r0, 0, 0)
+                if p.numel() != sink[2] * sink[3] * sink[4]:
+                    return None
+                by_param[id(p)] = sink
+        if covered != {id(l) for l in self.all_convs}:
+            return None                        # a layer kind this does not know how to keep current
+        self.__dict__["_sinks"] = sinks = PackSinks(self._build_gen, by_param)
+        return sinks
+
+    def packs_written(self, version_before):
+        """The optimizer's claim: "every sink of every parameter changed since the parameters had version sum ``version_before``
+        now holds the new value".  Taken only if the packs were current at that point -- then a layer whose parameters did not
+        change is still right, and the packs as a whole hold the contents of the present version sum.  Any later in-place change
+        of any parameter moves the sum on and the next forward packs everything as usual.  -> whether the claim was taken"""
+        if self._packed_version is None or self._packed_version != version_before:
+            return False
+        self._packed_version = self.param_version()
+        return True
 
     def replay_key(self, extra_bns=()):
         """Everything a captured / recorded chain (pmoe_amd/infer.py) holds raw pointers into, beyond its private activation pool:

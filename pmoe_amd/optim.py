@@ -9,6 +9,10 @@ Each call is one or two HIP launches over a chunk table (``csrc/optim.hip``) ins
 ``check_grad_norm`` (utils/nn.py:10-19), one ``.item()`` host sync -- per parameter tensor (620 for E=4).  The
 returned gradient norm is a device tensor; nothing here synchronises with the host.  ``FusedAdam.step(clip=norm)``
 consumes the clip coefficient straight from device memory, so clip + step is: 2 launches for the norm, 1 for Adam.
+
+``FusedAdam(..., packs=model)`` (opt-in): the update of a parameter that the model's engine keeps packed also writes the
+packed operands (``mt_adam_pack_kernel``), and the next forward does not pack again (DESIGN.md "Packs kept current by the
+optimizer").
 """
 import ctypes as C
 
@@ -31,6 +35,55 @@ class OptTensor(C.Structure):      # pmoe_opt_tensor
 _ROW = np.dtype([("param", "<u8"), ("grad", "<u8"), ("exp_avg", "<u8"), ("exp_avg_sq", "<u8"), ("max_exp_avg_sq", "<u8"),
                  ("swa", "<u8"), ("numel", "<i8"), ("bc1", "<f4"), ("bc2_sqrt", "<f4")])
 assert _ROW.itemsize == C.sizeof(OptTensor) == 64
+
+
+class OptPack(C.Structure):        # pmoe_opt_pack
+    _fields_ = [("fwd", C.c_void_p), ("dgrd", C.c_void_p), ("cout", C.c_int32), ("cin", C.c_int32), ("taps", C.c_int32),
+                ("dtype", C.c_int32), ("cinp", C.c_int32), ("row0", C.c_int32), ("dgrd_ld", C.c_int32), ("col0", C.c_int32),
+                ("tco", C.c_int32), ("tci", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+_PACK_FIELDS = ("fwd", "dgrd", "cout", "cin", "taps", "dtype", "cinp", "row0", "dgrd_ld", "col0")     # a sink, in this order
+_PACK_ROW = np.dtype([("fwd", "<u8"), ("dgrd", "<u8")] + [(k, "<i4") for k in _PACK_FIELDS[2:] + ("tco", "tci")]
+                     + [("reserved", "<i4", (2,))])
+assert _PACK_ROW.itemsize == C.sizeof(OptPack) == 64
+PACK_STAGE = 4640                  # PMOE_OPT_PACK_STAGE: floats of LDS one tile may take
+
+
+def pack_tile_dims(cout, cin, taps):
+    """Tile extents (tco, tci) of mt_adam_pack_kernel for a [cout][cin][taps] tensor; a tile is tco x tci channels x all taps.
+
+    The forward operand is contiguous along ci and the data-gradient operand along co, so a tile stores runs of tci elements
+    into the one and of tco elements into the other: both extents are >= 16 (32 bytes of bf16) wherever the layer has that
+    many channels.  tci * taps is about 288 floats (32 channels of a 3x3 filter, 288 of a 1x1): with 16 rows that is a tile of
+    ~4.6 K elements, 18 KB of LDS.  A tensor narrower than tci (a bias, the stem) takes more rows instead, in steps of 16; a
+    filter so large that 16 rows of 16 channels do not fit the stage takes fewer rows."""
+    if min(cout, cin, taps) < 1:
+        raise ValueError("pack_tile_dims: empty tensor")
+    tci = max(16, 288 // taps // 16 * 16)
+    stride = (min(tci, cin) * taps) | 1                    # LDS row stride of a full-width tile
+    if stride > PACK_STAGE:
+        raise ValueError(f"pack_tile_dims: a {taps}-tap filter does not fit the LDS stage")
+    fit = PACK_STAGE // stride
+    tco = min(fit, max(16, 4096 // (min(tci, cin) * taps)))
+    tco = tco // 16 * 16 if tco >= 16 else 1 << (tco.bit_length() - 1)
+    return tco, tci
+
+
+def pack_tiles(shapes):
+    """The (tensor, co0, ci0) tile table of ``shapes`` = [(cout, cin, taps), ...] -> (dims, tensor, co0, ci0): dims[t] = (tco,
+    tci) of tensor t and three equally long lists, one entry per workgroup.  Every tile lies inside its tensor and the tiles of
+    a tensor partition it."""
+    dims, tt, c0, i0 = [], [], [], []
+    for t, (cout, cin, taps) in enumerate(shapes):
+        tco, tci = pack_tile_dims(cout, cin, taps)
+        dims.append((tco, tci))
+        for co0 in range(0, cout, tco):
+            for ci0 in range(0, cin, tci):
+                tt.append(t)
+                c0.append(co0)
+                i0.append(ci0)
+    return dims, tt, c0, i0
 
 
 def _f32_cuda(t, what):
@@ -60,9 +113,21 @@ class _Table:
         return tab
 
     def __init__(self, rows, device):
+        packs = None
+        if isinstance(rows, tuple):        # (pmoe_opt_tensor rows, pmoe_opt_pack rows): a tile table instead of chunk lists
+            rows, packs = rows
         self.n = len(rows)
         self.host = torch.from_numpy(rows.view(np.uint8).reshape(-1).copy()).pin_memory()     # kept alive with the table
         self.table = self.host.to(device, non_blocking=True)
+        if packs is not None:
+            dims, tt, c0, i0 = pack_tiles(list(zip(packs["cout"].tolist(), packs["cin"].tolist(), packs["taps"].tolist())))
+            packs["tco"], packs["tci"] = [d[0] for d in dims], [d[1] for d in dims]
+            self._packs_host = torch.from_numpy(packs.view(np.uint8).reshape(-1).copy()).pin_memory()
+            self.packs = self._packs_host.to(device, non_blocking=True)
+            self._tiles_host = torch.tensor([tt, c0, i0], dtype=torch.int32).pin_memory()
+            self.tiles = self._tiles_host.to(device, non_blocking=True)
+            self.n_tiles = len(tt)
+            return
         ct, ci = [], []
         for t, n in enumerate(rows["numel"]):
             k = (int(n) + CHUNK - 1) // CHUNK
@@ -76,6 +141,10 @@ class _Table:
     def args(self):
         return (C.c_void_p(self.table.data_ptr()), C.c_void_p(self.chunk_tensor.data_ptr()),
                 C.c_void_p(self.chunk_index.data_ptr()), self.n_chunks)
+
+    def pack_args(self):
+        return (C.c_void_p(self.table.data_ptr()), C.c_void_p(self.packs.data_ptr())) + tuple(
+            C.c_void_p(self.tiles[i].data_ptr()) for i in range(3)) + (self.n_tiles,)
 
 
 def _rows(n):
@@ -120,15 +189,65 @@ def clip_grad_norm_(parameters, max_norm, norm_type=2.0, scale=True):
     return total
 
 
+def _pack_engines(packs):
+    """``packs`` -> the engine hosts (pmoe_amd.model.host.EngineHost) among the given modules and their submodules; an object
+    that has ``pack_sinks`` itself (an engine) is taken as it is"""
+    from .model.host import EngineHost
+    out = []
+    for m in packs if isinstance(packs, (list, tuple)) else [packs]:
+        if hasattr(m, "pack_sinks"):
+            out.append(m)
+        elif isinstance(m, torch.nn.Module):
+            hosts = [h for h in m.modules() if isinstance(h, EngineHost)]
+            if not hosts:
+                raise ValueError(f"FusedAdam(packs=...): {type(m).__name__} hosts no engine")
+            out.extend(hosts)
+        else:
+            raise TypeError("FusedAdam(packs=...): a module that hosts an engine, or a list of them")
+    return out
+
+
 class FusedAdam(torch.optim.Optimizer):
     """``torch.optim.Adam`` semantics (same arguments, same per-parameter ``state`` keys ``step`` / ``exp_avg`` /
     ``exp_avg_sq`` / ``max_exp_avg_sq``, so ``state_dict()`` checkpoints interchange with the reference's optimizer,
-    train_2.py:300-310), updated by one multi-tensor HIP launch per parameter group."""
+    train_2.py:300-310), updated by one multi-tensor HIP launch per parameter group.
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False):
+    ``packs``: a module that runs on an engine (or a list of them).  The parameters that the engine keeps packed -- conv /
+    linear weights and biases -- are then updated by a second launch per group that also stores the new values into the engine's
+    packed operands, and the engine is told that its packs hold the new parameter versions: the next forward packs nothing.
+    An engine takes part in a step only if its packs were current when the step began, the optimizer holds every parameter
+    the engine packs, and the engine is not on its fp8 policy; otherwise its parameters take the ordinary launch and the
+    engine packs as usual.  ``packs=None``: exactly the launches of before.  ``state_dict()`` does not change."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False, packs=None):
         if lr < 0 or eps < 0 or not (0 <= betas[0] < 1) or not (0 <= betas[1] < 1) or weight_decay < 0:
             raise ValueError("FusedAdam: invalid hyper-parameter")
         super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=amsgrad))
+        self._pack_hosts = _pack_engines(packs) if packs is not None else []
+
+    def _open_packs(self):
+        """-> (sink of every parameter whose update goes through the pack launch, key of the banks they point into, the engines
+        to tell afterwards with the version sum each had)"""
+        sinks, key, claims = {}, (), []
+        mine = None
+        for h in self._pack_hosts:
+            eng = h if hasattr(h, "pack_sinks") else h.__dict__.get("_eng")
+            found = eng.pack_sinks() if eng is not None else None
+            if found is None:
+                continue
+            before = eng.param_version()
+            if eng._packed_version != before:
+                continue                       # the packs are behind already: the next forward packs everything anyway
+            if mine is None:
+                mine = {id(p) for g in self.param_groups for p in g["params"]}
+            if not mine.issuperset(found.by_param):
+                continue                       # parameters this optimizer never sees: leave the whole engine to its own pack
+            if not sinks.keys().isdisjoint(found.by_param):
+                continue                       # a tensor another engine packs too: one launch writes one set of banks
+            sinks.update(found.by_param)
+            key += (id(eng), found.gen)
+            claims.append((eng, before))
+        return sinks, key, claims
 
     @torch.no_grad()
     def step(self, closure=None, clip=None):
@@ -141,14 +260,13 @@ class FusedAdam(torch.optim.Optimizer):
         clip_state = getattr(clip, "clip_state", None) if clip is not None else None
         if clip is not None and clip_state is None:
             raise ValueError("FusedAdam.step(clip=...): pass the tensor returned by pmoe_amd.optim.clip_grad_norm_")
+        sinks, bank_key, claims = self._open_packs() if self._pack_hosts else ({}, (), [])
         for group in self.param_groups:
             ps = [p for p in group["params"] if p.grad is not None]
             if not ps:
                 continue
-            b1, b2 = group["betas"]
             ams = bool(group["amsgrad"])
             keys = ("exp_avg", "exp_avg_sq") + (("max_exp_avg_sq",) if ams else ())
-            steps = []
             for p in ps:
                 if p.grad.is_sparse:
                     raise RuntimeError("FusedAdam does not support sparse gradients")
@@ -158,35 +276,62 @@ class FusedAdam(torch.optim.Optimizer):
                     for k in keys:
                         st[k] = torch.zeros_like(p, memory_format=torch.preserve_format)
                 st["step"] += 1
-                steps.append(float(st["step"]))
-            cols = {"param": tuple(_f32_cuda(p, "parameter") for p in ps),
-                    "grad": tuple(_f32_cuda(p.grad, "gradient") for p in ps)}
-            for k in keys:
-                cols[k] = tuple(_f32_cuda(self.state[p][k], k) for p in ps)
-            uniform = min(steps) == max(steps)
-
-            def build():
-                rows = _rows(len(ps))
-                for k, v in cols.items():
-                    rows[k] = v
-                rows["numel"] = [p.numel() for p in ps]
-                rows["bc1"] = [1.0 - b1 ** k for k in steps]
-                rows["bc2_sqrt"] = [(1.0 - b2 ** k) ** 0.5 for k in steps]
-                return rows
-            key = ("a",) + tuple(v for c in cols.values() for v in c) + (() if uniform else tuple(steps))
-            tab = _Table.get(key, ps[0].device, build, [p.numel() for p in ps])
-            # all tensors at the same step (the normal case): bias corrections travel as kernel arguments and the cached
-            # table is reused; otherwise the per-tensor values of a freshly built table are used (argument < 0)
-            bc1 = 1.0 - b1 ** steps[0] if uniform else -1.0
-            bc2s = (1.0 - b2 ** steps[0]) ** 0.5 if uniform else -1.0
-            check(load().pmoe_mt_adam(*tab.args(), float(group["lr"]), float(b1), float(b2), float(group["eps"]),
-                                      float(group["weight_decay"]), int(ams), float(bc1), float(bc2s),
-                                      C.c_void_p(clip_state.data_ptr()) if clip_state is not None else None, stream_ptr()),
-                  "pmoe_mt_adam")
+            if sinks:
+                packed = [p for p in ps if id(p) in sinks]
+                self._launch(group, [p for p in ps if id(p) not in sinks], keys, clip_state)
+                self._launch(group, packed, keys, clip_state, [sinks[id(p)] for p in packed], bank_key)
+            else:
+                self._launch(group, ps, keys, clip_state)
             # the kernel wrote through raw pointers: tell autograd (and the engine's packed-weight cache, which keys
             # on the version counters) that these tensors changed in place
             torch.autograd.graph.increment_version(ps)
+        for eng, before in claims:
+            eng.packs_written(before)
         return loss
+
+    def _launch(self, group, ps, keys, clip_state, sinks=None, bank_key=()):
+        """one launch over ``ps``: pmoe_mt_adam, or with ``sinks`` (one per tensor) pmoe_mt_adam_packs"""
+        if not ps:
+            return
+        b1, b2 = group["betas"]
+        steps = [float(self.state[p]["step"]) for p in ps]
+        cols = {"param": tuple(_f32_cuda(p, "parameter") for p in ps),
+                "grad": tuple(_f32_cuda(p.grad, "gradient") for p in ps)}
+        for k in keys:
+            cols[k] = tuple(_f32_cuda(self.state[p][k], k) for p in ps)
+        uniform = min(steps) == max(steps)
+
+        def build():
+            rows = _rows(len(ps))
+            for k, v in cols.items():
+                rows[k] = v
+            rows["numel"] = [p.numel() for p in ps]
+            rows["bc1"] = [1.0 - b1 ** k for k in steps]
+            rows["bc2_sqrt"] = [(1.0 - b2 ** k) ** 0.5 for k in steps]
+            if sinks is None:
+                return rows
+            packs = np.zeros(len(ps), dtype=_PACK_ROW)
+            for i, k in enumerate(_PACK_FIELDS):
+                packs[k] = [s[i] for s in sinks]
+            if max(int(p.numel()) for p in ps) >= 2 ** 31:
+                raise RuntimeError("FusedAdam(packs=...): a packed parameter has 2^31 or more elements")
+            return rows, packs
+        # a pack table also holds pointers into the engine's banks: its key carries them, the layout they are written in and the
+        # engines' build counters -- banks built again (another compute dtype or device) never meet a table of the old ones
+        key = (("a",) if sinks is None else ("ap", bank_key, tuple(sinks))) + tuple(v for c in cols.values() for v in c) + (
+            () if uniform else tuple(steps))
+        tab = _Table.get(key, ps[0].device, build, [p.numel() for p in ps])
+        # all tensors at the same step (the normal case): bias corrections travel as kernel arguments and the cached
+        # table is reused; otherwise the per-tensor values of a freshly built table are used (argument < 0)
+        bc1 = 1.0 - b1 ** steps[0] if uniform else -1.0
+        bc2s = (1.0 - b2 ** steps[0]) ** 0.5 if uniform else -1.0
+        hyper = (float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]),
+                 int(bool(group["amsgrad"])), float(bc1), float(bc2s),
+                 C.c_void_p(clip_state.data_ptr()) if clip_state is not None else None, stream_ptr())
+        if sinks is None:
+            check(load().pmoe_mt_adam(*tab.args(), *hyper), "pmoe_mt_adam")
+        else:
+            check(load().pmoe_mt_adam_packs(*tab.pack_args(), *hyper), "pmoe_mt_adam_packs")
 
 
 class FusedAveragedModel(torch.optim.swa_utils.AveragedModel):
