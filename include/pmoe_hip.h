@@ -141,7 +141,14 @@ int pmoe_conv2d_stat_rows(const pmoe_conv_desc* d);
  *   4000 + the latter        the four parity-class launches of a stride-2 3x3 data gradient (the code of class (1, 1);
  *                            9207: conv3x3s2_dma_kernel<true>)
  * A stride-2 1x1 data gradient accumulated in place (dilate, PMOE_RES_ADD with res == out) is ONE class-(0,0) launch: the
- * code of its tile, without the 4000.  One selection (conv_select) decides this code, the launch and pmoe_conv2d_stat_rows. */
+ * code of its tile, without the 4000.  One selection (conv_select) decides this code, the launch and pmoe_conv2d_stat_rows.
+ *
+ * What a non-negative plan means for the FUSED REQUESTS.  A descriptor that sets res_mode to PMOE_RES_INBN or PMOE_RES_DBN, or
+ * sets shuffle_c or in_fp8 (a weight-gradient descriptor: bn_fused), is run by a kernel that implements everything it asks for;
+ * where no such kernel serves it, pmoe_conv2d_plan, pmoe_conv2d_stat_rows and pmoe_conv2d_igemm (pmoe_conv2d_wgrad_plan,
+ * pmoe_conv2d_wgrad_ws_floats, pmoe_conv2d_wgrad and pmoe_conv2d_wgrad_fold) all return PMOE_ERR_UNSUPPORTED -- or PMOE_ERR_ARG
+ * for a descriptor that is malformed whatever the shape.  No request is ever dropped silently, so `plan >= 0` is the complete
+ * answer to "is the fusion applied": a caller falls back to the unfused launches on a negative plan and needs no list of codes. */
 int pmoe_conv2d_plan(const pmoe_conv_desc* d);
 
 /* Weight gradient of the same layers (autograd of nn.Conv2d / nn.Linear at the call sites above).

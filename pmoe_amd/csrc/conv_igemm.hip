@@ -590,16 +590,24 @@ static int select_stride2_dgrad(const ConvArgs& a, int dtype, ConvPlan* p) {
 
 // Which kernel launches serve a descriptor -- the one decision tree behind pmoe_conv2d_igemm, pmoe_conv2d_plan and
 // pmoe_conv2d_stat_rows.  Returns p->code: the plan code (include/pmoe_hip.h), or a PMOE_ERR_* when nothing can run.
+// The contract of the fused requests (include/pmoe_hip.h, "what a non-negative plan means"): a descriptor with shuf_c, in_fp8 or
+// res_mode PMOE_RES_INBN / PMOE_RES_DBN gets a kernel that implements ALL it asks for, or PMOE_ERR_UNSUPPORTED -- each request has its
+// own branch below, every *_plan a branch asks refuses the requests its kernel does not implement, and no such descriptor
+// reaches the general chain at the end.
 int conv_select(const ConvArgs& a, int dtype, ConvPlan* p) {
     memset(p, 0, sizeof(*p));
     p->n = 1;
     ConvLaunch* l = p->l;
     int code = 0;
-    if (a.shuf_c) {                                  // ConvTranspose2d scatter fused into the store: the 1x1 direct kernel only
+    const bool bn_mode = a.res_mode == PMOE_RES_INBN || a.res_mode == PMOE_RES_DBN;
+    if (a.in_fp8 && !a.w_fp8) {                      // e4m3 activations: with e4m3 weights (conv_dma_f8_plan below) or nothing
+        code = PMOE_ERR_UNSUPPORTED;
+    } else if (a.shuf_c) {                           // ConvTranspose2d scatter fused into the store: the 1x1 direct kernel only
         code = conv_c1x1_plan(a, dtype, l) ? 0 : PMOE_ERR_UNSUPPORTED;
     } else if (a.w_fp8) {                            // e4m3 weights: forward convs
         if (dtype != PMOE_DT_BF16 || a.dilate) code = PMOE_ERR_ARG;
         else if (a.in_fp8) code = conv_dma_f8_plan(a, dtype, l) ? 0 : PMOE_ERR_UNSUPPORTED;   // e4m3 activations too: that kernel or nothing
+        else if (bn_mode) code = PMOE_ERR_UNSUPPORTED;                                        // (no e4m3-weight kernel applies a BatchNorm)
         else code = tile_plan(a, 2, 1, l);
     } else if (a.res_mode == PMOE_RES_INBN) {        // BatchNorm + ReLU of the INPUT on load: conv3x3_respipe_kernel<false, 3> or
         if (!(!a.bias && conv_res_plan(a, dtype, l) && l->res_pipe) && !conv_c1x1_plan(a, dtype, l))     // conv1x1_direct_kernel<MT, true>

@@ -1113,8 +1113,7 @@ int conv_res_launch(const ConvLaunch& l, hipStream_t st) {
              : mode == 1 ? launch_respipe<false, 1>(l, grid, st)
                          : launch_respipe<false, 0>(l, grid, st);
     }
-    if (a.res_mode == PMOE_RES_INBN) return PMOE_ERR_UNSUPPORTED;
-    if (l.res_dma) {
+    if (l.res_dma) {                                     // (never PMOE_RES_INBN: conv_select gives that mode to res_pipe or refuses)
         if (a.bias) {
             HIP_RET((ensure_dyn_lds<conv3x3_resdma_kernel<true>>(163840)));
             hipLaunchKernelGGL(conv3x3_resdma_kernel<true>, grid, block, l.smem, st, a, p.tiles_per_expert, p.wgs_per_expert, l.pbuf, l.mpw, l.mph);

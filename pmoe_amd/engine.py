@@ -515,34 +515,27 @@ class ExpertGroupEngine:
     def _conv(self, x, layer, *, bias=True, act=hip.ACT_NONE, drop_p=0.0, out=None, out_coff=0, in_shared=False,
               want_stats=False, tape=True, in_bn=None):
         """``in_bn``: x is the pre-activation z of a BatchNorm + ReLU and in_bn its [4, E, C] coefficient block -- the launch applies
-        them on load (PMOE_RES_INBN: untaped forward launches; the caller has asked pmoe_conv2d_plan)."""
-        H, W = x.t.shape[1], x.t.shape[2]
+        them on load (PMOE_RES_INBN: untaped forward launches; the caller has asked whether such a launch is served)."""
         Ho, Wo, o = self._conv_out(x, layer, out, out_coff)
-        stats = None
         f8 = layer.w_f8 is not None
         if f8 and (bias is not False or act != hip.ACT_NONE):
             raise RuntimeError(f"{layer.name}: an fp8-policy layer has only its e4m3 forward operand (bias-free, no activation)")
-        # e4m3 activations left by the producing BatchNorm pass: the block-scaled MFMA kernel (no conversion in the loader)
-        xin = x.t
-        if f8 and x.f8 is not None and x.coff == 0 and not in_shared:
-            kwp = dict(cin=layer.cinp, cout=layer.cout_st, coutp=layer.coutp, ipe=self.B, ks=layer.ks, stride=layer.stride,
-                       pad=layer.pad, out_coff=o.coff, out_scale=layer.oscale, in_scale=self.fp8_in_scale)
-            if ops.conv2d(x.f8, layer.w_f8, o.t, plan_only=True, **kwp) == 8507:
-                xin = x.f8
-        in8 = xin is not x.t
-        if want_stats:
-            rows = ops.conv2d_stat_rows(self.N, H, W, Ho, Wo, layer.cinp, layer.cout_st, layer.coutp, self.B, layer.ks,
-                                        layer.stride, layer.pad, self.dtype, w_fp8=f8, in_ld=xin.shape[-1],
-                                        out_ld=o.t.shape[-1], in_shared=in_shared, in_fp8=in8)
-            stats = torch.empty(rows, 2, layer.coutp, dtype=F32, device=self.dev)
         seed = (next(self._seed_counter) * 0x9E3779B1 + self.base_seed) & 0xFFFFFFFFFFFF if drop_p > 0 else 0
+        kw = dict(cin=layer.cinp, cout=layer.cout_st, coutp=layer.coutp, ipe=self.B, ks=layer.ks, stride=layer.stride,
+                  pad=layer.pad, in_shared=in_shared, in_coff=x.coff, out_coff=o.coff, bias=layer.bias_packed if bias else None,
+                  act=act, drop_p=drop_p, seed=seed, stats=True if want_stats else None, out_scale=layer.oscale if f8 else None,
+                  in_scale=self.fp8_in_scale, **(dict(res_mode=hip.RES_INBN, bn_coef=in_bn) if in_bn is not None else {}))
+        # e4m3 activations left by the producing BatchNorm pass: the block-scaled MFMA kernel (no conversion in the loader),
+        # where it serves this launch; else the bf16 input through the converting loaders
+        run = None
+        if f8 and x.f8 is not None and x.coff == 0 and not in_shared:
+            run = ops.conv2d_prepare(x.f8, layer.w_f8, o.t, **kw)
+        if run is None or not run.served():
+            run = ops.conv2d_prepare(x.t, layer.w_f8 if f8 else layer.w_fwd, o.t, **kw)
         flop = 2.0 * self.N * Ho * Wo * layer.cout * layer.cin * layer.taps
         ops.set_meta(flop=flop, name=layer.name)
-        ops.conv2d(xin, layer.w_f8 if f8 else layer.w_fwd, o.t, cin=layer.cinp, cout=layer.cout_st, coutp=layer.coutp,
-                   ipe=self.B, ks=layer.ks, stride=layer.stride, pad=layer.pad, in_shared=in_shared, in_coff=x.coff,
-                   out_coff=o.coff, bias=layer.bias_packed if bias else None, act=act, drop_p=drop_p, seed=seed,
-                   stats=stats, out_scale=layer.oscale if f8 else None, in_scale=self.fp8_in_scale,
-                   **(dict(res_mode=hip.RES_INBN, bn_coef=in_bn) if in_bn is not None else {}))
+        run.launch()
+        stats = run.stats
         o.act, o.drop_p = act, drop_p
         if self.debug_acts is not None and act == hip.ACT_RELU:
             self.debug_acts[layer.name] = (o.t, o.coff, layer.cout)
@@ -675,17 +668,13 @@ class ExpertGroupEngine:
         z, bnl, coef, rpe = src
         if bnl.C != kw["cout"] or bnl.C != kw["coutp"] or z.t.shape != x.t.shape:      # (the statistics rows are coutp wide)
             return False
-        common = dict(res=z.t, res_mode=hip.RES_DBN, bn_coef=coef, bn_ipe=self.B, bias=bias, **kw)
-        if ops.conv2d(dy, w_dg, g, plan_only=True, **common) not in (1107, 1117, 1247, 1257, 5007, 5017):
+        run = ops.conv2d_prepare(dy, w_dg, g, res=z.t, res_mode=hip.RES_DBN, bn_coef=coef, bn_ipe=self.B, bias=bias, stats=True, **kw)
+        if not run.served():
             return False
-        n, h, w = dy.shape[0], dy.shape[1], dy.shape[2]
-        rows = ops.conv2d_stat_rows(n, h, w, h, w, kw["cin"], kw["cout"], kw["coutp"], kw["ipe"], 3, 1, 1, self.dtype,
-                                    in_ld=dy.shape[-1], out_ld=g.shape[-1])
-        stats = torch.empty(rows, 2, kw["coutp"], dtype=F32, device=self.dev)
         ops.set_meta(flop=flop, name=name + ":dgrad+bnred")
-        ops.conv2d(dy, w_dg, g, stats=stats, **common)
+        run.launch()
         x.set_grad(g)
-        x.bn_part = (stats, rows // self.E)
+        x.bn_part = (run.stats, run.stats.shape[0] // self.E)
         return True
 
     @staticmethod
@@ -1211,10 +1200,10 @@ class ExpertGroupEngine:
             # round 4: bn_c1's backward apply happens inside conv1's per-image filter gradient (dz1, 2.15 GB at the headline shape,
             # is never written): possible because that launch is the only consumer of dz1 (PMOE_STEM_BN_FUSE=0: A/B switch)
             z1.bn_defer = (self.stem_bn_fuse and self.training and self.bn_reduce_in_dgrad and self.dtype == torch.bfloat16
-                           and fold2 and ops.conv2d_wgrad(x0.t, z1.t, None, cin=self.conv1.cinp, cout=self.conv1.cout_st,
-                                                          cinp=64, coutp=64, ipe=self.B, ks=3, stride=1, pad=self.conv1.pad,
-                                                          x_shared=True, per_image=True, bn_fuse=(z1.t, None, None, None),
-                                                          plan_only=True) == 7209)
+                           and fold2 and ops.conv2d_wgrad_bn_served(z1.t.shape[0], H, W, z1.t.shape[1], z1.t.shape[2], self.conv1.cinp,
+                                                                    self.conv1.cout_st, 64, 64, self.B, 3, 1, self.conv1.pad, self.dtype,
+                                                                    x_ld=x0.t.shape[-1], dy_ld=z1.t.shape[-1], x_shared=True,
+                                                                    per_image=True))
             self.tape.append(lambda: self._stem_in_bwd(x0, z1, gate, gapmean))
             a1 = self._bn(z1, self.bn_c1, relu=True, stats=st, want_gap=fold2)
         else:

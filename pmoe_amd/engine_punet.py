@@ -234,14 +234,10 @@ class PUNetEngine(ExpertGroupEngine):
         if (self.fuse_in_bn and not self.taping and self.training and self.dtype == torch.bfloat16 and self.fuse_conv_stats
                 and self.debug_acts is None and c2.w_f8 is None and c1.cout_st == c2.cinp == bn1.C):
             n, h, w, _ = x.t.shape
-            key = (n, h, w, self.dtype)
-            ok = blk.get("_inbn")
-            if ok is None or ok[0] != key:
-                ho, wo = ops.conv_out_size(h, c2.ks, c2.stride, c2.pad), ops.conv_out_size(w, c2.ks, c2.stride, c2.pad)
-                code = ops.conv2d_plan(n, h, w, ho, wo, c2.cinp, c2.cout_st, c2.coutp, self.B, c2.ks, c2.stride, c2.pad, self.dtype,
-                                       in_ld=c1.cout_st, out_ld=c2.cout_st, res_mode=hip.RES_INBN)
-                ok = blk["_inbn"] = (key, code == 1267)
-            if ok[1]:
+            ho, wo = ops.conv_out_size(h, c2.ks, c2.stride, c2.pad), ops.conv_out_size(w, c2.ks, c2.stride, c2.pad)
+            # asked on every pass (the answer is needed before c1 runs): the library reads its switches per launch
+            if ops.conv2d_plan(n, h, w, ho, wo, c2.cinp, c2.cout_st, c2.coutp, self.B, c2.ks, c2.stride, c2.pad, self.dtype,
+                               in_ld=c1.cout_st, out_ld=c2.cout_st, res_mode=hip.RES_INBN, stats=True) >= 0:
                 z1, st1 = self._conv_stats(x, c1)
                 self._bn_coeffs(bn1, self.B * h * w, st1, st1.shape[0] // self.E, z1)
                 z2, st2 = self._conv_stats(z1, c2, in_bn=self._last_coef)
@@ -279,10 +275,11 @@ class PUNetEngine(ExpertGroupEngine):
         if h.pending_bn is not None:
             n, hh, ww, _ = h.t.shape
             o = torch.empty(n, hh, ww, layer.cout_st, dtype=self.dtype, device=self.dev)
-            kw = dict(cin=layer.cinp, cout=layer.cout_st, coutp=layer.coutp, ipe=self.B, ks=1, stride=1, pad=0, bias=layer.bias_packed)
-            if ops.conv2d(h.t, layer.w_fwd, o, res_mode=hip.RES_INBN, bn_coef=h.pending_bn[0], plan_only=True, **kw) in (1412, 1414):
+            run = ops.conv2d_prepare(h.t, layer.w_fwd, o, cin=layer.cinp, cout=layer.cout_st, coutp=layer.coutp, ipe=self.B, ks=1,
+                                     stride=1, pad=0, bias=layer.bias_packed, res_mode=hip.RES_INBN, bn_coef=h.pending_bn[0])
+            if run.served():
                 ops.set_meta(flop=2.0 * n * hh * ww * layer.cout * layer.cin, name=layer.name + "+bn")
-                ops.conv2d(h.t, layer.w_fwd, o, res_mode=hip.RES_INBN, bn_coef=h.pending_bn[0], **kw)
+                run.launch()
                 return Var(o, layer.cout_st, 0)
             h = self._materialize(h)
         return self._conv(h, layer, bias=True)
@@ -383,12 +380,11 @@ class PUNetEngine(ExpertGroupEngine):
             return False
         if h.pending_bn is not None:                      # (its BatchNorm + ReLU applied on load: conv1x1_direct_kernel<MT, true>)
             kw.update(res_mode=hip.RES_INBN, bn_coef=h.pending_bn[0])
-            if ops.conv2d(h.t, up.w_fwd, cat.t, plan_only=True, **kw) not in (1462, 1464):
-                return False
-        elif ops.conv2d(h.t, up.w_fwd, cat.t, plan_only=True, **kw) not in (1452, 1454):
+        run = ops.conv2d_prepare(h.t, up.w_fwd, cat.t, **kw)
+        if not run.served():
             return False
         ops.set_meta(flop=2.0 * h.t.shape[0] * h.t.shape[1] * h.t.shape[2] * up.cout * up.cin, name=up.name + "+shuffle")
-        ops.conv2d(h.t, up.w_fwd, cat.t, **kw)
+        run.launch()
         return True
 
     fold_entry_eca = True  # round 4: the entry block's two ECA gates folded into per-image weights of the convolutions they feed

@@ -48,27 +48,89 @@ def _conv_desc(n, h, w_, ho, wo, cin, cout, coutp, ipe, ks, stride, pad, dtype, 
     return d
 
 
+def _stand_in(t, name=None, dtype=None):
+    """planning stand-in for the pointer of ``t``: non-null, never dereferenced, equal only for the same tensor (the kernel
+    selection asks which pointers are present and whether ``res`` aliases ``out``)"""
+    return None if t is None else C.c_void_p(id(t))
+
+
 def _planning_desc(n, h, w_, ho, wo, cin, cout, coutp, ipe, ks, stride, pad, dtype, bias=False, stats=False, **kw):
     """descriptor of a planning call: the pointers the launch would pass (only their presence matters to the kernel choice) are
-    set to a placeholder that nothing dereferences"""
+    set to stand-ins that nothing dereferences"""
     d = _conv_desc(n, h, w_, ho, wo, cin, cout, coutp, ipe, ks, stride, pad, hip._TORCH_DT[dtype], **kw)
-    one = C.c_void_p(1)
+    d.in_, d.w, d.out = 1, 2, 3
     if d.res_mode not in (hip.RES_NONE, hip.RES_INBN):
-        d.res = one
+        d.res = 4
     if d.res_mode in (hip.RES_DBN, hip.RES_INBN):
-        d.bn_coef = one
+        d.bn_coef = 5
     if d.w_fp8:
-        d.out_scale = one
-    d.bias, d.stats = (one if bias else None), (one if stats else None)
+        d.out_scale = 6
+    d.bias, d.stats = (7 if bias else None), (8 if stats else None)
     return d
 
 
-def conv2d(x, w_packed, out, *, cin, cout, coutp, ipe, ks, stride, pad, dilate=False, in_shared=False,
-           in_coff=0, out_coff=0, res=None, res_coff=0, res_mode=hip.RES_NONE, bias=None, act=hip.ACT_NONE,
-           drop_p=0.0, seed=0, stats=None, plan_only=False, out_scale=None, in_scale=1.0, bn_coef=None, bn_ipe=0, shuffle2_c=0):
-    """out[..., out_coff:out_coff+cout] = epilogue(conv(x[..., in_coff:in_coff+cin], w)).
-    ``x`` [Nin,H,W,ldx], ``out`` [N,Ho,Wo,ldo] preallocated; also used for dgrad and grouped GEMM.
-    ``plan_only``: launch nothing, return the kernel-instantiation code of ``pmoe_conv2d_plan`` (include/pmoe_hip.h)."""
+class ConvLaunch:
+    """One conv2d launch, prepared (:func:`conv2d_prepare`): ONE validated descriptor says whether a kernel serves the launch,
+    how many statistics rows it writes, and runs it.  ``served()`` is the whole answer to "is the fused request applied": a
+    descriptor that asks for PMOE_RES_INBN / PMOE_RES_DBN / shuffle_c / in_fp8 runs on a kernel that implements the request or
+    on none (include/pmoe_hip.h), so callers fall back on ``not served()`` and never look at plan codes."""
+    __slots__ = ("d", "out", "stats")
+
+    def __init__(self, d, out, stats):
+        self.d, self.out, self.stats = d, out, stats
+
+    def plan(self):
+        """the kernel-instantiation code of pmoe_conv2d_plan (include/pmoe_hip.h), or a negative PMOE_ERR_*"""
+        return load().pmoe_conv2d_plan(C.byref(self.d))
+
+    def served(self):
+        return self.plan() >= 0
+
+    def stat_rows(self):
+        return _stat_rows(self.d)
+
+    def launch(self):
+        """run it; -> ``out``.  Prepared with ``stats=True``: ``self.stats`` becomes the [stat_rows(), 2, coutp] f32 buffer."""
+        return _conv2d_launch(self)
+
+
+def _stat_rows(d):
+    rows = load().pmoe_conv2d_stat_rows(C.byref(d))
+    if rows < 0:
+        check(rows, "pmoe_conv2d_stat_rows")
+    return rows
+
+
+def _conv2d_launch(p):
+    d = p.d
+    if p.out is None:
+        raise ValueError("conv2d: a launch prepared from shapes only can be asked, not run")
+    if p.stats is not None:
+        # the launch writes exactly pmoe_conv2d_stat_rows(d) partial-sum rows: a buffer sized from a different descriptor
+        # (other row lengths can mean another kernel) would be folded with unwritten rows
+        rows = p.stat_rows()
+        if p.stats is True:
+            p.stats = torch.empty(rows, 2, d.coutp, dtype=torch.float32, device=p.out.device)
+        elif p.stats.dim() != 3 or p.stats.shape[0] != rows or p.stats.shape[1] != 2 or p.stats.shape[2] != d.coutp:
+            raise ValueError(f"conv2d: stats must be [{rows}, 2, {d.coutp}] for this launch, got {tuple(p.stats.shape)}")
+        d.stats = ptr(p.stats, "stats", torch.float32)
+    elif d.res_mode == hip.RES_DBN:
+        raise ValueError("conv2d: RES_DBN writes the BatchNorm-backward reductions to `stats`")
+    if _prof is not None:            # profiling: remember which kernel instantiation serves this launch
+        _launch_info["kernel"] = p.plan()
+    check(load().pmoe_conv2d_igemm(C.byref(d), stream_ptr()), "pmoe_conv2d_igemm")
+    return p.out
+
+
+def conv2d_prepare(x, w_packed, out, *, cin, cout, coutp, ipe, ks, stride, pad, dilate=False, in_shared=False,
+                   in_coff=0, out_coff=0, res=None, res_coff=0, res_mode=hip.RES_NONE, bias=None, act=hip.ACT_NONE,
+                   drop_p=0.0, seed=0, stats=None, out_scale=None, in_scale=1.0, bn_coef=None, bn_ipe=0, shuffle2_c=0,
+                   shapes_only=False):
+    """The :class:`ConvLaunch` of out[..., out_coff:out_coff+cout] = epilogue(conv(x[..., in_coff:in_coff+cin], w)).
+    ``x`` [Nin,H,W,ldx], ``out`` [N,Ho,Wo,ldo] preallocated; also used for dgrad and grouped GEMM.  ``stats``: the partial-sum
+    buffer, or True = the launch allocates it.  ``shapes_only``: the tensors give shapes and dtypes only (they may live
+    anywhere); every pointer is a planning stand-in and the result answers ``plan`` / ``served`` / ``stat_rows`` but cannot run."""
+    at = _stand_in if shapes_only else ptr
     nin, h, w_, ldx = _nhwc(x, "x")
     n, ho, wo, ldo = _nhwc(out, "out")
     if shuffle2_c:
@@ -83,10 +145,9 @@ def conv2d(x, w_packed, out, *, cin, cout, coutp, ipe, ks, stride, pad, dilate=F
         raise ValueError("conv2d: x, w and out must share one dtype")
     if w_fp8 and (out_scale is None or out.dtype != torch.bfloat16):
         raise ValueError("conv2d: e4m3 weights need bf16 activations and the per-channel out_scale of the pack")
-    in_, w, o = ptr(x, "x"), ptr(w_packed, "w"), ptr(out, "out")
-    res_p = ptr(res, "res", out.dtype) if res is not None else None
-    bias_p = ptr(bias, "bias", torch.float32) if bias is not None else None
-    stats_p = ptr(stats, "stats", torch.float32) if stats is not None else None
+    in_, w, o = at(x, "x"), at(w_packed, "w"), at(out, "out")
+    res_p, bias_p = at(res, "res", out.dtype), at(bias, "bias", torch.float32)
+    stats_p = C.c_void_p(8) if stats is True else at(stats, "stats", torch.float32)
     d = _conv_desc(n, h, w_, ho, wo, cin, cout, coutp, ipe, ks, stride, pad, dt(out), dilate=dilate, in_shared=in_shared,
                    in_ld=ldx, in_coff=in_coff, out_ld=ldo, out_coff=out_coff,
                    res_mode=res_mode if (res is not None or res_mode == hip.RES_INBN) else hip.RES_NONE,
@@ -94,40 +155,32 @@ def conv2d(x, w_packed, out, *, cin, cout, coutp, ipe, ks, stride, pad, dilate=F
                    w_fp8=w_fp8, in_fp8=in_fp8, in_scale=in_scale, bn_ipe=bn_ipe, shuffle2_c=shuffle2_c)
     d.in_, d.w, d.out, d.res, d.bias, d.stats = in_, w, o, res_p, bias_p, stats_p
     if w_fp8:
-        d.out_scale = ptr(out_scale, "out_scale", torch.float32)
-    if d.res_mode == hip.RES_DBN:
-        # data gradient into relu(BatchNorm(z)): res = z, bn_coef = [4][n / bn_ipe][cout] (mean, invstd, gamma*invstd, beta);
-        # the launch masks the gradient and leaves the BatchNorm backward's channel reductions in `stats`
-        nset = n // (bn_ipe or ipe)
-        if bn_coef is None or bn_coef.dtype != torch.float32 or tuple(bn_coef.shape) != (4, nset, cout):
-            raise ValueError(f"conv2d: RES_DBN needs bn_coef [4, {nset}, {cout}] f32")
-        if stats is None and not plan_only:
-            raise ValueError("conv2d: RES_DBN writes the BatchNorm-backward reductions to `stats`")
-        d.bn_coef = ptr(bn_coef, "bn_coef", torch.float32)
-    if d.res_mode == hip.RES_INBN:
-        # the INPUT is the pre-activation z of a BatchNorm + ReLU: bn_coef = [4][n / bn_ipe][cin], applied on load
-        nset = n // (bn_ipe or ipe)
-        if res is not None or bn_coef is None or bn_coef.dtype != torch.float32 or tuple(bn_coef.shape) != (4, nset, cin):
-            raise ValueError(f"conv2d: RES_INBN takes no `res` and needs bn_coef [4, {nset}, {cin}] f32")
-        d.bn_coef = ptr(bn_coef, "bn_coef", torch.float32)
+        d.out_scale = at(out_scale, "out_scale", torch.float32)
+    if d.res_mode in (hip.RES_DBN, hip.RES_INBN):
+        # RES_DBN: data gradient into relu(BatchNorm(z)): res = z, bn_coef = [4][n / bn_ipe][cout] (mean, invstd, gamma*invstd,
+        # beta); the launch masks the gradient and leaves the BatchNorm backward's channel reductions in `stats`.
+        # RES_INBN: the INPUT is the pre-activation z of a BatchNorm + ReLU: bn_coef = [4][n / bn_ipe][cin], applied on load
+        inbn = d.res_mode == hip.RES_INBN
+        want = (4, n // (bn_ipe or ipe), cin if inbn else cout)
+        if (inbn and res is not None) or bn_coef is None or bn_coef.dtype != torch.float32 or tuple(bn_coef.shape) != want:
+            raise ValueError(f"conv2d: RES_{'INBN takes no `res` and' if inbn else 'DBN'} needs bn_coef {list(want)} f32")
+        d.bn_coef = at(bn_coef, "bn_coef", torch.float32)
     if in_shared and nin != ipe:
         raise ValueError("conv2d: shared input must hold exactly ipe images")
     if not in_shared and nin != n:
         raise ValueError("conv2d: input/output image counts differ")
     if w_packed.numel() < (n // ipe) * coutp * ks * ks * cin:
         raise ValueError("conv2d: packed weight tensor too small")
-    if plan_only:
-        return load().pmoe_conv2d_plan(C.byref(d))
-    if stats is not None:
-        # the launch writes exactly pmoe_conv2d_stat_rows(d) partial-sum rows: a buffer sized from a different descriptor
-        # (other row lengths can mean another kernel) would be folded with unwritten rows
-        rows = load().pmoe_conv2d_stat_rows(C.byref(d))
-        if stats.dim() != 3 or stats.shape[0] != rows or stats.shape[1] != 2 or stats.shape[2] != coutp:
-            raise ValueError(f"conv2d: stats must be [{rows}, 2, {coutp}] for this launch, got {tuple(stats.shape)}")
-    if _prof is not None:            # profiling: remember which kernel instantiation serves this launch
-        _launch_info["kernel"] = load().pmoe_conv2d_plan(C.byref(d))
-    check(load().pmoe_conv2d_igemm(C.byref(d), stream_ptr()), "pmoe_conv2d_igemm")
-    return out
+    return ConvLaunch(d, None if shapes_only else out, stats)
+
+
+def conv2d(x, w_packed, out, *, plan_only=False, **kw):
+    """:func:`conv2d_prepare` (its keywords) + launch.  ``plan_only``: launch nothing, return the kernel-instantiation code of
+    ``pmoe_conv2d_plan`` (include/pmoe_hip.h)."""
+    if kw.get("stats") is True:
+        raise ValueError("conv2d: stats=True (the launch allocates the buffer) is conv2d_prepare's: conv2d returns only `out`")
+    p = conv2d_prepare(x, w_packed, out, **kw)
+    return p.plan() if plan_only else p.launch()
 
 
 def conv2d_plan(n, h, w_, ho, wo, cin, cout, coutp, ipe, ks, stride, pad, dtype, *, bias=False, stats=False, **kw):
@@ -142,12 +195,8 @@ def conv2d_stat_rows(n, h, w_, ho, wo, cin, cout, coutp, ipe, ks, stride, pad, d
                      in_shared=False, in_fp8=False):
     """Partial-sum rows the launch will write.  in_ld / out_ld: row lengths (elements) of the tensors the launch will get --
     the kernel choice can depend on them (0 = dense)."""
-    d = _planning_desc(n, h, w_, ho, wo, cin, cout, coutp, ipe, ks, stride, pad, dtype, w_fp8=w_fp8, in_fp8=in_fp8,
-                       in_ld=in_ld, out_ld=out_ld, in_shared=in_shared)
-    rows = load().pmoe_conv2d_stat_rows(C.byref(d))
-    if rows < 0:
-        check(rows, "pmoe_conv2d_stat_rows")
-    return rows
+    return _stat_rows(_planning_desc(n, h, w_, ho, wo, cin, cout, coutp, ipe, ks, stride, pad, dtype, w_fp8=w_fp8, in_fp8=in_fp8,
+                                     in_ld=in_ld, out_ld=out_ld, in_shared=in_shared))
 
 
 _wgrad_scratch = {}
@@ -163,15 +212,55 @@ def _wgrad_part_ws(device, floats):
     return buf
 
 
+def _wgrad_desc(n, h, w_, ho, wo, cin, cout, cinp, coutp, ipe, ks, stride, pad, dtype, *, x_ld=0, dy_ld=0, x_coff=0, dy_coff=0,
+                x_shared=False, per_image=False, bn_z_ld=None):
+    """The pmoe_wgrad_desc of a launch from its shapes alone (``dtype``: PMOE_DT_*; x_ld / dy_ld 0 = dense rows); the pointers are
+    left null for the caller.  ``bn_z_ld``: the launch is ``bn_fused`` and its z has rows of that length (0 = those of dy)."""
+    d = WgradDesc()
+    d.n, d.h, d.w_, d.cin, d.cinp = n, h, w_, cin, cinp
+    d.ho, d.wo, d.cout, d.coutp = ho, wo, cout, coutp
+    d.x_ld, d.x_coff, d.dy_ld, d.dy_coff = x_ld or x_coff + cin, x_coff, dy_ld or dy_coff + cout, dy_coff
+    d.ipe, d.x_shared = ipe, int(x_shared)
+    d.ks, d.stride, d.pad, d.dtype = ks, stride, pad, dtype
+    d.per_image = int(per_image)
+    if bn_z_ld is not None:
+        d.bn_fused, d.bn_z_ld = 1, bn_z_ld or d.dy_ld
+    return d
+
+
+def _wgrad_ws(d):
+    """(floats of K-split scratch the launch needs, its number of K-split slices = workgroups along the pixel axis): the selection
+    reports the scratch as the size of its ``nsplit`` slabs (0: the launch writes dw_ws itself)"""
+    need = load().pmoe_conv2d_wgrad_ws_floats(C.byref(d))
+    if need < 0:
+        check(int(need), "pmoe_conv2d_wgrad_ws_floats")
+    return need, max(1, need // ((d.n // d.ipe) * d.ks * d.ks * d.coutp * d.cinp))
+
+
+def conv2d_wgrad_bn_served(n, h, w_, ho, wo, cin, cout, cinp, coutp, ipe, ks, stride, pad, dtype, *, bn_z_ld=0, **kw):
+    """Whether a kernel serves the weight-gradient launch of these shapes (``kw``: _wgrad_desc's) that applies the backward of the
+    BatchNorm + ReLU behind the conv on load (``bn_fuse`` of conv2d_wgrad; include/pmoe_hip.h, bn_fused): that kernel or none."""
+    d = _wgrad_desc(n, h, w_, ho, wo, cin, cout, cinp, coutp, ipe, ks, stride, pad, hip._TORCH_DT[dtype], bn_z_ld=bn_z_ld, **kw)
+    return load().pmoe_conv2d_wgrad_plan(C.byref(d)) >= 0
+
+
+def conv2d_wgrad_nsplit(n, h, w_, ho, wo, cin, cout, cinp, coutp, ipe, ks, stride, pad, dtype, **kw):
+    """Number of K-split slices the weight-gradient launch of these shapes would use (``kw``: _wgrad_desc's)."""
+    return _wgrad_ws(_wgrad_desc(n, h, w_, ho, wo, cin, cout, cinp, coutp, ipe, ks, stride, pad, hip._TORCH_DT[dtype], **kw))[1]
+
+
 def conv2d_wgrad(x, dy, dw_ws, *, cin, cout, cinp, coutp, ipe, ks, stride, pad, x_shared=False, x_coff=0, dy_coff=0,
                  per_image=False, plan_only=False, grads=None, grads_cout=0, grads_cin=0, defer_fold=False, bn_fuse=None):
     """dw_ws [E | N][ks*ks][coutp][cinp] f32 is OVERWRITTEN with the weight gradient (deterministic: fixed-order folds
     of the pixel split, no atomics; csrc/conv_wgrad.hip).  ``grads`` (flat f32, E * grads_cout * grads_cin * ks * ks): the
     parameters' own gradient layout, written by the fold instead of dw_ws (which then is scratch only).  ``defer_fold``: run the
-    MFMA launch only and return the descriptor for :func:`conv2d_wgrad_fold` (the two kernels are then timed apart)."""
+    MFMA launch only and return the descriptor for :func:`conv2d_wgrad_fold` (the two kernels are then timed apart).
+    ``plan_only`` (older callers; new code asks conv2d_wgrad_bn_served / conv2d_wgrad_nsplit): launch nothing; with ``bn_fuse``
+    return the plan code or a negative error, else the K-split count."""
     nin, h, w_, ldx = _nhwc(x, "x")
     n, ho, wo, ldy = _nhwc(dy, "dy")
-    d = WgradDesc()
+    d = _wgrad_desc(n, h, w_, ho, wo, cin, cout, cinp, coutp, ipe, ks, stride, pad, dt(x), x_ld=ldx, dy_ld=ldy, x_coff=x_coff,
+                    dy_coff=dy_coff, x_shared=x_shared, per_image=per_image, bn_z_ld=None if bn_fuse is None else bn_fuse[0].shape[-1])
     d.x, d.dy = ptr(x, "x"), ptr(dy, "dy", x.dtype)
     d.dw_ws = ptr(dw_ws, "dw_ws", torch.float32) if dw_ws is not None else None
     if bn_fuse is not None:
@@ -180,33 +269,23 @@ def conv2d_wgrad(x, dy, dw_ws, *, cin, cout, cinp, coutp, ipe, ks, stride, pad, 
         z, coef, c1, c2 = bn_fuse
         if z.shape[:3] != dy.shape[:3]:
             raise ValueError("conv2d_wgrad: bn_fuse z must have the geometry of dy")
-        d.bn_fused, d.bn_z_ld = 1, z.shape[-1]
         if not plan_only:
             E_ = n // ipe
             if coef.shape != (4, E_, cout) or c1.shape != (E_, cout) or c2.shape != (E_, cout):
                 raise ValueError("conv2d_wgrad: bn_fuse coefficient blocks must be [4,E,cout] / [E,cout]")
             d.bn_z, d.bn_coef = ptr(z, "bn_z", x.dtype), ptr(coef, "bn_coef", torch.float32)
             d.bn_c1, d.bn_c2 = ptr(c1, "bn_c1", torch.float32), ptr(c2, "bn_c2", torch.float32)
-    d.n, d.h, d.w_, d.cin, d.cinp = n, h, w_, cin, cinp
-    d.ho, d.wo, d.cout, d.coutp = ho, wo, cout, coutp
-    d.x_ld, d.x_coff, d.dy_ld, d.dy_coff = ldx, x_coff, ldy, dy_coff
-    d.ipe, d.x_shared = ipe, int(x_shared)
-    d.ks, d.stride, d.pad, d.dtype = ks, stride, pad, dt(x)
-    d.per_image = int(per_image)
     if grads is not None:
         if per_image or grads.dtype != torch.float32 or grads.numel() != (n // ipe) * grads_cout * grads_cin * ks * ks:
             raise ValueError("conv2d_wgrad: grads must hold E * cout * cin * ks * ks float32 values (not with per_image)")
         d.grads, d.cout_real, d.cin_real = ptr(grads, "grads", torch.float32), int(grads_cout), int(grads_cin)
-    if bn_fuse is not None and plan_only:       # -> 7209 if the fused kernel serves this shape, else a negative error code
+    if bn_fuse is not None and plan_only:
         return load().pmoe_conv2d_wgrad_plan(C.byref(d))
-    slab = (n // ipe) * ks * ks * coutp * cinp          # one [E][taps][coutp][cinp] gradient: dw_ws, and each K-split slab
-    if dw_ws.numel() < (n * ks * ks * coutp * cinp if per_image else slab):
+    if dw_ws.numel() < (n if per_image else n // ipe) * ks * ks * coutp * cinp:      # [E | N][taps][coutp][cinp]
         raise ValueError("conv2d_wgrad: workspace too small")
-    need = load().pmoe_conv2d_wgrad_ws_floats(C.byref(d))
-    if need < 0:
-        check(int(need), "pmoe_conv2d_wgrad_ws_floats")
-    if plan_only:                    # number of K-split slices (workgroups along the pixel axis) the launch would use: the
-        return max(1, need // slab)  # selection reports it as the size of its `nsplit` slabs (0: the launch writes dw_ws itself)
+    need, nsplit = _wgrad_ws(d)
+    if plan_only:
+        return nsplit
     if need > 0:
         part = _wgrad_part_ws(x.device, need)
         d.part_ws, d.part_ws_floats = ptr(part, "part_ws"), part.numel()
@@ -526,7 +605,10 @@ def profile_end():
     return [(n, m, e0.elapsed_time(e1)) for n, m, e0, e1 in recs]
 
 
-def _timed(fn):
+def _timed(fn, name=None):
+    """``name``: the op name of the profile records, where it is not the function's own"""
+    name = name or fn.__name__
+
     @_functools.wraps(fn)
     def wrapper(*a, **k):
         global _next_meta
@@ -540,17 +622,18 @@ def _timed(fn):
         if _launch_info:
             meta.update(_launch_info)
             _launch_info.clear()
-        _prof.append((fn.__name__, meta, e0, e1))
+        _prof.append((name, meta, e0, e1))
         return r
     return wrapper
 
 
-for _n in ("stem_tail_stats", "stem_tail_pool", "stem_tail_bwd", "stem_tail_pooled", "stem_tail_combine", "conv2d", "conv2d_wgrad", "conv2d_wgrad_fold", "pack_conv_weights", "pack_conv_weights_scaled", "pack_conv_weights_gated", "unpack_conv_wgrad", "pack_bias", "colstats",
+for _n in ("stem_tail_stats", "stem_tail_pool", "stem_tail_bwd", "stem_tail_pooled", "stem_tail_combine", "conv2d_wgrad", "conv2d_wgrad_fold", "pack_conv_weights", "pack_conv_weights_scaled", "pack_conv_weights_gated", "unpack_conv_wgrad", "pack_bias", "colstats",
            "reduce_partials", "bn_finalize", "bn_apply", "bn_apply_gap", "bn_bwd_reduce", "bn_bwd_finalize", "bn_bwd_apply",
            "maxpool_fwd", "maxpool_bwd", "gap_partial", "gap_finish", "gap_bwd", "eca_gate", "eca_scale",
            "eca_bwd_small", "eca_bwd_apply", "eca_stem_fold", "nchw_to_nhwc", "pad_rows", "gate_mixture_fwd", "gate_mixture_bwd",
            "moe_loss"):
     globals()[_n] = _timed(globals()[_n])
+_conv2d_launch = _timed(_conv2d_launch, "conv2d")        # every conv2d launch, however prepared: the records' op name stays "conv2d"
 
 
 # ---------------------------------------------------------------------------------------------- PU-Net / PMoE

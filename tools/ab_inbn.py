@@ -31,13 +31,12 @@ for C, H in ((64, 256), (128, 128), (256, 64)):
     out, a_ = torch.empty_like(z), torch.empty_like(z)
     coef = torch.rand(4, 1, C, device=DEV) + 0.5
     kw = dict(cin=C, cout=C, coutp=C, ipe=N, ks=3, stride=1, pad=1)
-    rows = ops.conv2d_stat_rows(N, H, H, H, H, C, C, C, N, 3, 1, 1, BF)
-    st = torch.zeros(rows, 2, C, device=DEV)
+    plain = ops.conv2d_prepare(z, w, out, stats=True, **kw)
+    plain.launch()                                  # (allocates plain.stats; the launch on load writes the same rows)
+    on_load = ops.conv2d_prepare(z, w, out, stats=plain.stats, res_mode=hip.RES_INBN, bn_coef=coef, **kw)
     for rep in range(2):
-        p = t(lambda: ops.conv2d(z, w, out, stats=st, **kw))
-        code = ops.conv2d(z, w, out, res_mode=hip.RES_INBN, bn_coef=coef, plan_only=True, **kw)
-        i = t(lambda: ops.conv2d(z, w, out, stats=st, res_mode=hip.RES_INBN, bn_coef=coef, **kw)) if code > 0 else float("nan")
+        p = t(plain.launch)
+        i = t(on_load.launch) if on_load.served() else float("nan")
         b = t(lambda: ops.bn_apply(z, None, a_, coef[2], coef[3], coef[0], N * H * H, 1, C, True))
-        print(f"C={C:3d} {H}x{H}: plain {p:.3f} ms (plan {ops.conv2d(z, w, out, plan_only=True, **kw)})  on load {i:.3f} ms "
-              f"(plan {code})  bn_apply {b:.3f} ms  "
+        print(f"C={C:3d} {H}x{H}: plain {p:.3f} ms (plan {plain.plan()})  on load {i:.3f} ms (plan {on_load.plan()})  bn_apply {b:.3f} ms  "
               f"pair {p + b:.3f} -> {i:.3f}", flush=True)
