@@ -67,7 +67,7 @@ int pmoe_version(void);
 const char* pmoe_error_string(int code);
 /* sizeof() of the descriptor structs as compiled (which: 0 = pmoe_conv_desc, 1 = pmoe_wgrad_desc);
  * lets a foreign-language binding verify its struct layout without launching anything */
-int pmoe_abi_sizeof(int which); /* 0: pmoe_conv_desc, 1: pmoe_wgrad_desc, 2: pmoe_opt_tensor, 3: pmoe_opt_pack */
+int pmoe_abi_sizeof(int which); /* 0: pmoe_conv_desc, 1: pmoe_wgrad_desc, 2: pmoe_opt_tensor, 3: pmoe_opt_pack, 4: pmoe_aug_plan */
 
 /* ---- convolution / grouped GEMM -------------------------------------------------------------
  * Replaces nn.Conv2d in model/blocks/basics.py:93-100,113-120 (stem), the torchvision ResNet body
@@ -596,6 +596,71 @@ int pmoe_resample_u8_vertical_to_f32(const uint8_t* src, float* dst_nchw, int32_
 int pmoe_resample_u8_vertical_to_i64(const uint8_t* src, int64_t* dst_nchw, int32_t n_img, int32_t Hin, int32_t W,
                                      int32_t C, int32_t Hout, const int32_t* bounds, const int32_t* coeffs,
                                      int32_t ksize, void* stream);
+
+/* the same vertical pass writing the 8-bit result as it is, dst [n][Hout][W][C] (NHWC): the Resize output that the train-time
+ * augmenter below reads before ToTensor's / 255 */
+int pmoe_resample_u8_vertical_to_u8(const uint8_t* src, uint8_t* dst_nhwc, int32_t n_img, int32_t Hin, int32_t W, int32_t C,
+                                    int32_t Hout, const int32_t* bounds, const int32_t* coeffs, int32_t ksize, void* stream);
+
+/* ---- train-time augmenter (model/augmenter.py:get_augmenter, applied between Resize and ToTensor by
+ * model/data_loader.py:255-271) on uint8 RGB frames [n][h][w][3].  The reference's operator set, schedules, probabilities and
+ * ranges; the arithmetic per operator is defined HERE (v = a channel value as int, rint = round-half-even, clamp to [0, 255],
+ * every float step one f32 operation without contraction) and makes no claim of parity with imgaug's random stream or cv2:
+ *   ADD            clamp(v + (int)p[c])
+ *   MULTIPLY       clamp(rint(f32(v) * p[c]))
+ *   CONTRAST       clamp(rint(p[c] * f32(v - 128) + 128))
+ *   GRAYSCALE      g = (4899 R + 9617 G + 1868 B + 8192) >> 14;  clamp(rint(f32(v) + p[c] * f32(g - v)))
+ *   DROPOUT        v = 0 unless hash_uniform(seed, idx) >= p[0];  idx = (y w + x) 3 + c if per_channel else y w + x
+ *                  (hash_uniform: csrc/common.h, the counter hash of pmoe_dropout2d_table)
+ *   COARSE_DROPOUT the same on the cell yl = y hl / h, xl = x wl / w (integer division), idx over [hl][wl](3); no mask buffer
+ *   NOISE          clamp(rint(f32(v) + p[0] z)), z = sqrt(-2 ln(1 - u1)) cos(2 pi u2), u1 = hash_uniform(seed, 2 idx),
+ *                  u2 = hash_uniform(seed, 2 idx + 1); p[0] in 0..255 units (libm-dependent: not bit-reproducible off the device)
+ *   BLUR           two separable passes (horizontal, then vertical) with the row's blur_k integer taps (sum 65536), each
+ *                  (sum taps[i] v + 32768) >> 16 into an 8-bit image, reflect-101 borders (index -1 -> 1, n -> n - 2)
+ * One pmoe_aug_plan row per frame is the only input besides pixels.  A frame runs its slots in order; with a blur slot the
+ * point operators split into phase 0 (slots before it) and phase 1 (slots after it); without one, phase 0 runs all slots and
+ * phase 1 none.  Rows are sanitised on the device (n_slots clamped to 0..8, blur_k outside odd 3..33 means no blur, mask sizes
+ * below 1 read as 1, reflected indices clamped), so a malformed row cannot address outside the frame. */
+#define PMOE_AUG_NONE 0
+#define PMOE_AUG_ADD 1
+#define PMOE_AUG_MULTIPLY 2
+#define PMOE_AUG_CONTRAST 3
+#define PMOE_AUG_GRAYSCALE 4
+#define PMOE_AUG_DROPOUT 5
+#define PMOE_AUG_COARSE_DROPOUT 6
+#define PMOE_AUG_NOISE 7
+#define PMOE_AUG_BLUR 8
+#define PMOE_AUG_MAX_SLOTS 8
+#define PMOE_AUG_MAX_TAPS 33
+typedef struct pmoe_aug_slot {
+    int32_t op;            /* PMOE_AUG_* */
+    int32_t per_channel;   /* DROPOUT / COARSE_DROPOUT / NOISE: one draw per channel value (else per pixel / cell) */
+    int32_t hl, wl;        /* COARSE_DROPOUT: low-resolution mask size */
+    float p[3];            /* per-channel parameter (equal when the operator is not per-channel); mask and noise ops read p[0] */
+    int32_t reserved;
+    uint64_t seed;         /* DROPOUT / COARSE_DROPOUT / NOISE */
+} pmoe_aug_slot;           /* 40 bytes */
+typedef struct pmoe_aug_plan {
+    int32_t n_slots;       /* 0 .. PMOE_AUG_MAX_SLOTS, in execution order */
+    int32_t blur_slot;     /* index of the PMOE_AUG_BLUR slot, -1 without one */
+    int32_t blur_k;        /* its tap count (odd), 0 without one */
+    int32_t reserved;
+    pmoe_aug_slot slot[PMOE_AUG_MAX_SLOTS];
+    int32_t taps[PMOE_AUG_MAX_TAPS];   /* 16-bit fixed-point Gaussian weights, taps[0 .. blur_k) */
+    int32_t reserved2;
+} pmoe_aug_plan;           /* 472 bytes: pmoe_abi_sizeof(4) */
+/* src [n][h][w][3] -> dst [n][h][w][3] uint8 (dst != src), the slots of `phase` (0 or 1) */
+int pmoe_augment_point_to_u8(const uint8_t* src, uint8_t* dst, const pmoe_aug_plan* plan, int32_t n_img, int32_t h, int32_t w,
+                             int32_t phase, void* stream);
+/* ... -> dst [n][3][h][w] f32 = value / 255 (ToTensor): a frame with no slot in `phase` gets exactly what
+ * pmoe_resample_u8_vertical_to_f32 would have written */
+int pmoe_augment_point_to_f32(const uint8_t* src, float* dst_nchw, const pmoe_aug_plan* plan, int32_t n_img, int32_t h, int32_t w,
+                              int32_t phase, void* stream);
+/* the two blur passes, src -> dst (dst != src); frames whose row has no blur are copied through */
+int pmoe_augment_blur_h(const uint8_t* src, uint8_t* dst, const pmoe_aug_plan* plan, int32_t n_img, int32_t h, int32_t w,
+                        void* stream);
+int pmoe_augment_blur_v(const uint8_t* src, uint8_t* dst, const pmoe_aug_plan* plan, int32_t n_img, int32_t h, int32_t w,
+                        void* stream);
 
 #ifdef __cplusplus
 }

@@ -54,7 +54,8 @@ int pmoe_version(void) { return PMOE_ABI_VERSION; }
 
 int pmoe_abi_sizeof(int which) {
     return which == 0 ? (int)sizeof(pmoe_conv_desc) : which == 1 ? (int)sizeof(pmoe_wgrad_desc)
-           : which == 2 ? (int)sizeof(pmoe_opt_tensor) : which == 3 ? (int)sizeof(pmoe_opt_pack) : PMOE_ERR_ARG;
+           : which == 2 ? (int)sizeof(pmoe_opt_tensor) : which == 3 ? (int)sizeof(pmoe_opt_pack)
+           : which == 4 ? (int)sizeof(pmoe_aug_plan) : PMOE_ERR_ARG;
 }
 
 const char* pmoe_error_string(int code) {

@@ -141,6 +141,11 @@ SIGNATURES = {
     "pmoe_resample_u8_horizontal": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P],
     "pmoe_resample_u8_vertical_to_f32": [_P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P],
     "pmoe_resample_u8_vertical_to_i64": [_P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P],
+    "pmoe_resample_u8_vertical_to_u8": [_P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P],
+    "pmoe_augment_point_to_u8": [_P, _P, _P, _I, _I, _I, _I, _P],
+    "pmoe_augment_point_to_f32": [_P, _P, _P, _I, _I, _I, _I, _P],
+    "pmoe_augment_blur_h": [_P, _P, _P, _I, _I, _I, _P],
+    "pmoe_augment_blur_v": [_P, _P, _P, _I, _I, _I, _P],
     "pmoe_mt_grad_norm": [_P, _P, _P, _I, _F, _P, _P, _I, _P],
     "pmoe_mt_adam": [_P, _P, _P, _I, _F, _F, _F, _F, _F, _I, _F, _F, _P, _P],
     "pmoe_mt_adam_packs": [_P, _P, _P, _P, _P, _I, _F, _F, _F, _F, _F, _I, _F, _F, _P, _P],

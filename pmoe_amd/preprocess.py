@@ -4,6 +4,10 @@ on raw uint8 camera frames that are already on the device.  Bit-exact with Pillo
 torchvision's Resize runs on a PIL image): the coefficient tables are computed here exactly as Pillow's
 ``precompute_coeffs`` / ``normalize_coeffs_8bpc`` do (double precision, 22-bit fixed point) and the two integer passes run
 in ``csrc/preprocess.hip``.
+
+The training path of the reference puts its augmenter between ``Resize`` and ``ToTensor`` (``data_loader.py:255-271``):
+``pre(frames, augment=get_augmenter(...))`` does the same on the device (``pmoe_amd/augment.py``, which also says what that
+augmenter does and does not claim).
 """
 import ctypes as C
 import math
@@ -60,14 +64,26 @@ class FramePreprocessor:
                                      torch.tensor(kk, dtype=torch.int32, device=device))
         return t
 
-    def __call__(self, frames):
+    def __call__(self, frames, augment=None, generator=None, plan=None):
+        """``augment``: an ``pmoe_amd.augment.Augmenter`` -> ``ToTensor(augment(Resize(Crop(frame))))``, the plan drawn from
+        ``generator`` (default: torch's CPU generator) unless ``plan`` (an ``AugmentPlan``, one row per frame) is given.
+        Without ``augment`` nothing changes: the same two launches, the same bits."""
         if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8:
             raise TypeError("FramePreprocessor: expected a uint8 tensor [..., H0, W0, C]")
         if not frames.is_cuda:
             raise RuntimeError("FramePreprocessor: frames must be on the MI355X (cuda) device; pmoe_amd has no CPU path")
         if frames.dim() < 3:
             raise ValueError("FramePreprocessor: expected [..., H0, W0, C]")
-        return self._run(frames, labels=False)
+        if augment is None:
+            if plan is not None or generator is not None:
+                raise ValueError("FramePreprocessor: plan / generator need an augment")
+            return self._run(frames, labels=False)
+        from .augment import Augmenter
+        if not isinstance(augment, Augmenter):
+            raise TypeError("FramePreprocessor: augment must be a pmoe_amd.augment.Augmenter")
+        if frames.shape[-1] != 3:
+            raise ValueError("FramePreprocessor: the augmenter takes RGB frames [..., H0, W0, 3]")
+        return self._run(frames, labels=False, augment=(augment, generator, plan))
 
     def labels(self, masks):
         """Label pipeline of stage-1 training (``data_loader.py:282-286,305-309``: ``Crop`` -> ``Resize`` ->
@@ -82,7 +98,7 @@ class FramePreprocessor:
         out = self._run(masks.unsqueeze(-1), labels=True)
         return out.squeeze(-3)
 
-    def _run(self, frames, labels):
+    def _run(self, frames, labels, augment=None):
         lead = frames.shape[:-3]
         H0, W0, Cc = frames.shape[-3:]
         rows = H0 - self.top - self.bottom
@@ -95,10 +111,20 @@ class FramePreprocessor:
         kh, bh, ch = self._table(W0, w, dev)
         kv, bv, cv = self._table(rows, h, dev)
         tmp = torch.empty(n, rows, w, Cc, dtype=torch.uint8, device=dev)
+        if augment is not None:                     # the plan first: a refused one (blur too wide for the frame) launches nothing
+            from .augment import run_plan
+            aug, generator, plan = augment
+            plan = aug._plan_for(n, h, w, generator, plan)
         out = torch.empty(n, Cc, h, w, dtype=torch.int64 if labels else torch.float32, device=dev)
         p = lambda t: C.c_void_p(t.data_ptr())      # noqa: E731
         check(load().pmoe_resample_u8_horizontal(p(src), p(tmp), n, H0, W0, self.top, rows, Cc, w, p(bh), p(ch), kh,
                                                  stream_ptr()), "pmoe_resample_u8_horizontal")
+        if augment is not None:                     # Resize output as uint8 NHWC -> augmenter -> ToTensor in its last launch
+            res = torch.empty(n, h, w, Cc, dtype=torch.uint8, device=dev)
+            check(load().pmoe_resample_u8_vertical_to_u8(p(tmp), p(res), n, rows, w, Cc, h, p(bv), p(cv), kv, stream_ptr()),
+                  "pmoe_resample_u8_vertical_to_u8")
+            run_plan(res, plan, out)
+            return out.view(*lead, Cc, h, w)
         vert = load().pmoe_resample_u8_vertical_to_i64 if labels else load().pmoe_resample_u8_vertical_to_f32
         check(vert(p(tmp), p(out), n, rows, w, Cc, h, p(bv), p(cv), kv, stream_ptr()), "pmoe_resample_u8_vertical")
         return out.view(*lead, Cc, h, w)
