@@ -134,3 +134,20 @@ template <auto KERNEL> static inline hipError_t ensure_dyn_lds(int bytes) {
         hipError_t _e = (expr);             \
         if (_e != hipSuccess) return (int)_e; \
     } while (0)
+
+// One kernel launch: the opt-in of KERNEL to OPT_IN bytes of dynamic LDS (0: it uses none), the launch, its error code.
+template <auto KERNEL, int OPT_IN = 160 * 1024, typename... Args>
+static inline int launch(dim3 grid, dim3 block, size_t smem, hipStream_t st, const Args&... args) {
+    if constexpr (OPT_IN > 0) HIP_RET((ensure_dyn_lds<KERNEL>(OPT_IN)));
+    hipLaunchKernelGGL(KERNEL, grid, block, smem, st, args...);
+    return (int)hipGetLastError();
+}
+
+// The one reader of the library's PMOE_* switches (the table: DESIGN.md, "Switches the library reads"): the integer value of
+// the variable, `dflt` when it is unset.  Read at the call: every switch takes effect at the next launch or planning call.
+#include <limits.h>
+#include <stdlib.h>
+static inline int sw(const char* name, int dflt) {
+    const char* ev = getenv(name);
+    return ev ? atoi(ev) : dflt;
+}

@@ -185,8 +185,7 @@ __global__ void __launch_bounds__(256, 2) conv3x3_c16_kernel(ConvArgs a, int til
 
 // PMOE_CONV_C16=0: A/B switch back to conv3x3_res_kernel<5> (read per launch)
 bool conv_c16_plan(const ConvArgs& a, int dtype, ConvLaunch* l) {
-    const char* ev = getenv("PMOE_CONV_C16");
-    if (ev && !atoi(ev)) return false;
+    if (!sw("PMOE_CONV_C16", 1)) return false;
     if (dtype != PMOE_DT_BF16 || a.w_fp8 || a.ks != 3 || a.stride != 1 || a.pad != 1 || a.dilate) return false;
     if (a.Cin != 16 || a.CoutP != 64 || a.Cout % 8 || a.Cout > 64) return false;
     if (a.bias || a.act != PMOE_ACT_NONE || a.res_mode != PMOE_RES_NONE || a.drop_p > 0.f) return false;
@@ -210,6 +209,5 @@ int conv_c16_launch(const ConvLaunch& l, hipStream_t st) {
     const ConvArgs& a = l.a;
     const long long in_b = (long long)a.ipe * a.H * a.W * a.in_ld * 2 - (long long)a.in_coff * 2;
     const long long out_b = (long long)a.ipe * a.H * a.W * a.out_ld * 2 - (long long)a.out_coff * 2;
-    hipLaunchKernelGGL(conv3x3_c16_kernel, dim3(l.wpe, a.N / a.ipe), dim3(256), 0, st, a, l.tiles_x, l.tpe, l.wpe, (unsigned)in_b, (unsigned)out_b);
-    return (int)hipGetLastError();
+    return launch<conv3x3_c16_kernel, 0>(dim3(l.wpe, a.N / a.ipe), dim3(256), 0, st, a, l.tiles_x, l.tpe, l.wpe, (unsigned)in_b, (unsigned)out_b);
 }

@@ -223,8 +223,7 @@ __global__ void __launch_bounds__(256, 2) conv1x1_direct_kernel(ConvArgs a, int 
 
 // PMOE_CONV_C1X1=0: A/B switch back to the LDS-tiled kernels (read per launch)
 bool conv_c1x1_plan(const ConvArgs& a, int dtype, ConvLaunch* l) {
-    const char* ev = getenv("PMOE_CONV_C1X1");
-    if (ev && !atoi(ev)) return false;
+    if (!sw("PMOE_CONV_C1X1", 1)) return false;
     if (dtype != PMOE_DT_BF16 || a.w_fp8 || a.ks != 1 || a.pad != 0 || a.dilate || a.kh != 1 || a.kw != 1) return false;
     if (a.stride != 1 && a.stride != 2) return false;
     if (a.use_tapmap || a.out_step != 1) return false;
@@ -264,18 +263,10 @@ int conv_c1x1_launch(const ConvLaunch& l, hipStream_t st) {
     const long long out_b = (long long)a.ipe * a.Ho * a.Wo * a.out_ld * 2 * (a.shuf_c ? 4 : 1) - (long long)a.out_coff * 2;
     const int kch = (a.Cin + 127) / 128;
     dim3 grid(wpe * slabs, a.N / a.ipe), block(256);
-    if (a.res_mode == PMOE_RES_INBN && m == 4) {
-        HIP_RET((ensure_dyn_lds<conv1x1_direct_kernel<4, true>>(160 * 1024)));
-        hipLaunchKernelGGL((conv1x1_direct_kernel<4, true>), grid, block, sm, st, a, tpe, wpe, slabs, (unsigned)in_b, (unsigned)out_b, kch);
-    } else if (a.res_mode == PMOE_RES_INBN) {
-        HIP_RET((ensure_dyn_lds<conv1x1_direct_kernel<2, true>>(160 * 1024)));
-        hipLaunchKernelGGL((conv1x1_direct_kernel<2, true>), grid, block, sm, st, a, tpe, wpe, slabs, (unsigned)in_b, (unsigned)out_b, kch);
-    } else if (m == 4) {
-        HIP_RET((ensure_dyn_lds<conv1x1_direct_kernel<4>>(160 * 1024)));
-        hipLaunchKernelGGL(conv1x1_direct_kernel<4>, grid, block, sm, st, a, tpe, wpe, slabs, (unsigned)in_b, (unsigned)out_b, kch);
-    } else {
-        HIP_RET((ensure_dyn_lds<conv1x1_direct_kernel<2>>(160 * 1024)));
-        hipLaunchKernelGGL(conv1x1_direct_kernel<2>, grid, block, sm, st, a, tpe, wpe, slabs, (unsigned)in_b, (unsigned)out_b, kch);
-    }
-    return (int)hipGetLastError();
+    const unsigned in_lim = (unsigned)in_b, out_lim = (unsigned)out_b;
+    if (a.res_mode == PMOE_RES_INBN)
+        return m == 4 ? launch<conv1x1_direct_kernel<4, true>>(grid, block, sm, st, a, tpe, wpe, slabs, in_lim, out_lim, kch)
+                      : launch<conv1x1_direct_kernel<2, true>>(grid, block, sm, st, a, tpe, wpe, slabs, in_lim, out_lim, kch);
+    return m == 4 ? launch<conv1x1_direct_kernel<4>>(grid, block, sm, st, a, tpe, wpe, slabs, in_lim, out_lim, kch)
+                  : launch<conv1x1_direct_kernel<2>>(grid, block, sm, st, a, tpe, wpe, slabs, in_lim, out_lim, kch);
 }

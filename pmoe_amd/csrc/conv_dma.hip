@@ -1183,24 +1183,17 @@ __global__ void __launch_bounds__(NTHR, 2) conv3x3_dma_f8_kernel(const ConvArgs 
 // l->a and the launch sizes.
 static bool dma_tile(const ConvArgs& a, int halo, int ltw_max, int nbuf, int ring, int esz, ConvLaunch* l) {
     if ((long long)a.ipe * a.Ho * a.Wo < 4096) return false;
-    auto p2 = [](int v) { int l = 0; while ((1 << l) < v) ++l; return l; };
-    int lTW = p2(a.Wo); if (lTW > ltw_max) lTW = ltw_max;
-    if (lTW < 4) return false;
-    int lTH = p2(a.Ho); if (lTH > 8 - lTW) lTH = 8 - lTW;
-    const int TN = BM >> (lTW + lTH);
-    const int npiece = (TN * ((1 << lTH) + halo) * ((1 << lTW) + halo) + 7) / 8;
+    const PixelTile t = pixel_tile(a.Ho, a.Wo, a.ipe, 8, ltw_max);
+    if (t.lTW < 4) return false;
+    const int npiece = (t.TN * ((1 << t.lTH) + halo) * ((1 << t.lTW) + halo) + 7) / 8;
     if (npiece > 48) return false;                      // 6 pieces per wave
     const int pb = npiece * 1024;
     const size_t need = (size_t)nbuf * pb + (size_t)ring * WSLOT;
     if (need > 160 * 1024) return false;
     if ((long long)a.ipe * a.H * a.W * a.in_ld * esz >= 0x7ff00000ll) return false;
-    ConvArgs& c = l->a;
-    c = a;
-    c.lTW = lTW; c.lTH = lTH; c.TN = TN;
-    c.n_groups = (a.ipe + TN - 1) / TN;
-    c.tiles_y = (a.Ho + (1 << lTH) - 1) >> lTH;
-    c.tiles_x = (a.Wo + (1 << lTW) - 1) >> lTW;
-    l->mblocks = (a.N / a.ipe) * c.n_groups * c.tiles_y * c.tiles_x;
+    l->a = a;
+    set_tile(l->a, t);
+    l->mblocks = (a.N / a.ipe) * t.per_expert();
     l->smem = need < (size_t)BM / 2 * BN * 4 ? (size_t)BM / 2 * BN * 4 : need;
     l->pbuf = pb;
     return true;
@@ -1226,34 +1219,30 @@ static bool dma_tile(const ConvArgs& a, int halo, int ltw_max, int nbuf, int rin
 // The persistent kernel also needs rows 0..159 (NT = 2) or all 256 half-rows (NT = 1) of the epilogue's staging to fit the patch
 // buffer and its packed (image, row, column) piece fields to fit.
 bool conv_dma_plan(const ConvArgs& a, int dtype, ConvLaunch* l) {
-    const char* ev = getenv("PMOE_CONV_DMA");
-    if ((ev && !atoi(ev)) || dtype != PMOE_DT_BF16 || a.w_fp8) return false;
+    if (!sw("PMOE_CONV_DMA", 1) || dtype != PMOE_DT_BF16 || a.w_fp8) return false;
     if (a.ks != 3 || a.kh != 3 || a.kw != 3 || a.use_tapmap || a.stride != 1 || a.pad != 1 || a.dilate || a.in_shared) return false;
     if (a.out_step != 1 || a.Ho != a.H || a.Wo != a.W) return false;
     if (a.Cin % CK || a.Cout % 8 || a.N % a.ipe) return false;
     const bool plain = a.res_mode == PMOE_RES_NONE && !a.bias && a.act == PMOE_ACT_NONE && a.drop_p == 0.f;
-    const char* evn = getenv("PMOE_DMA_NARROW");
-    bool narrow = !(evn && !atoi(evn)) && a.CoutP == 64 && a.Cin >= 2 * CK && plain;
-    const char* evs = getenv("PMOE_DMA_STREAM");
-    bool stream = !(evs && !atoi(evs)) && plain && (a.Cin <= 256 || (evs && atoi(evs) == 2));
+    const int stream_sw = sw("PMOE_DMA_STREAM", 1), producer_sw = sw("PMOE_DMA_PRODUCER", 1);
+    bool narrow = sw("PMOE_DMA_NARROW", 1) && a.CoutP == 64 && a.Cin >= 2 * CK && plain;
+    bool stream = stream_sw && plain && (a.Cin <= 256 || stream_sw == 2);
 #ifdef PMOE_STAMP
     narrow = stream = false;                             // (the stamped epilogue ends the workgroup after its first tile)
 #endif
     if (a.CoutP % BN && !narrow) return false;
     if (!dma_tile(a, 2, 5, 2, RING, 2, l)) return false;
     const ConvArgs& c = l->a;
-    const int PW = (1 << c.lTW) + 2, PH = (1 << c.lTH) + 2;
+    const int PW = patch_extent(c.lTW, 3, 1), PH = patch_extent(c.lTH, 3, 1);
     const int npiece = (c.TN * PH * PW + 7) / 8;
     const bool stream_ok = l->pbuf >= 160 * 256 && magic_div_exact(npiece * 8, PW, PH, &l->mpw, &l->mph) &&
                            c.TN * PH < 1024 && PW < 1024 && a.ipe < 2047;
     if (narrow && !stream_ok) return false;
-    const char* evm = getenv("PMOE_DMA_MF16");
-    const char* evp = getenv("PMOE_DMA_PRODUCER");
     l->kind = CONV_DMA;
     l->narrow = narrow;
     l->stream = narrow || (stream && stream_ok);
-    l->producer = !l->stream && !(evp && !atoi(evp)) && plain && (a.Cin >= 256 || (evp && atoi(evp) == 2));
-    l->mf16 = !narrow && (evm ? atoi(evm) != 0 : a.Cin >= 256);
+    l->producer = !l->stream && producer_sw && plain && (a.Cin >= 256 || producer_sw == 2);
+    l->mf16 = !narrow && sw("PMOE_DMA_MF16", a.Cin >= 256) != 0;
     // 5007 / 5017 = conv3x3_dma_kernel<MF16>, + 20 with the producer wave, + 40 = conv3x3_dma_stream_kernel<MF16>,
     // 5067 = conv3x3_dma_stream_kernel<false, true> (64-cout tiles)
     l->code = narrow ? 5067 : (l->mf16 ? 5017 : 5007) + (l->stream ? 40 : l->producer ? 20 : 0);
@@ -1261,11 +1250,9 @@ bool conv_dma_plan(const ConvArgs& a, int dtype, ConvLaunch* l) {
 }
 
 // Stride-2 3x3 forward convolutions (pad 1) of >= 128 output-channel rows over whole 64-channel chunks, bf16, output maps of
-// >= 4096 pixels per expert that tile into 16 x 16 squares: conv3x3s2_dma_kernel.  PMOE_CONV_S2DMA=0: back to the generic
-// kernel (A/B runs; read per launch).
+// >= 4096 pixels per expert that tile into 16 x 16 squares: conv3x3s2_dma_kernel.
 bool conv_dma_s2_plan(const ConvArgs& a, int dtype, ConvLaunch* l) {
-    const char* ev = getenv("PMOE_CONV_S2DMA");
-    if ((ev && !atoi(ev)) || dtype != PMOE_DT_BF16 || a.w_fp8) return false;
+    if (dtype != PMOE_DT_BF16 || a.w_fp8) return false;
     if (a.ks != 3 || a.kh != 3 || a.kw != 3 || a.use_tapmap || a.stride != 2 || a.pad != 1 || a.dilate || a.in_shared) return false;
     if (a.out_step != 1 || a.Ho != (a.H - 1) / 2 + 1 || a.Wo != (a.W - 1) / 2 + 1) return false;
     if (a.Cin % CK || a.CoutP % BN || a.Cout % 8 || a.N % a.ipe) return false;
@@ -1278,16 +1265,13 @@ bool conv_dma_s2_plan(const ConvArgs& a, int dtype, ConvLaunch* l) {
 
 // One parity class of a stride-2 3x3 data gradient (the class fields of ConvArgs set by conv_select, conv_igemm.hip): bf16, whole
 // 64-channel chunks of dy, gradient rows in multiples of 64, class lattices of >= 4096 pixels per expert that tile into 16 x 16
-// squares.  PMOE_CONV_S2DMA=0: back to the generic kernel.
+// squares.
 bool conv_dma_s2cls_plan(const ConvArgs& a, int dtype, ConvLaunch* l) {
-    const char* ev = getenv("PMOE_CONV_S2DMA");
-    if ((ev && !atoi(ev)) || dtype != PMOE_DT_BF16 || a.w_fp8) return false;
+    if (dtype != PMOE_DT_BF16 || a.w_fp8) return false;
     if (a.ks != 3 || !a.use_tapmap || a.out_step != 2 || a.stride != 1 || a.pad != 0 || a.dilate || a.in_shared) return false;
     if (a.kh < 1 || a.kh > 2 || a.kw < 1 || a.kw > 2) return false;
-    // (64 gradient rows -- layer2.0.conv1 -- would run half a tile of zero weights: measured 0.77 vs 0.58 ms on the generic kernel;
-    //  PMOE_S2CLS_64=1 admits them for that A/B)
-    const char* e64 = getenv("PMOE_S2CLS_64");
-    if (a.Cin % CK || a.CoutP % ((e64 && atoi(e64)) ? 64 : BN) || a.Cout % 8 || a.N % a.ipe || a.stats || a.res_mode > PMOE_RES_ADD) return false;
+    // (64 gradient rows -- layer2.0.conv1 -- would run half a tile of zero weights: measured 0.77 vs 0.58 ms on the generic kernel)
+    if (a.Cin % CK || a.CoutP % BN || a.Cout % 8 || a.N % a.ipe || a.stats || a.res_mode > PMOE_RES_ADD) return false;
     if (!dma_tile(a, 1, 4, 3, RING3, 2, l)) return false;
     l->kind = CONV_DMA_S2CLS;
     l->code = 5207;
@@ -1298,8 +1282,7 @@ bool conv_dma_s2cls_plan(const ConvArgs& a, int dtype, ConvLaunch* l) {
 // 3x3 stride 1, whole 128-channel chunks, >= 128 output-channel rows, maps of >= 4096 pixels per expert.  PMOE_CONV_F8DMA=0: the
 // activations go through the bf16 -> e4m3 converting loaders of round 2 instead.
 bool conv_dma_f8_plan(const ConvArgs& a, int dtype, ConvLaunch* l) {
-    const char* ev = getenv("PMOE_CONV_F8DMA");
-    if ((ev && !atoi(ev)) || dtype != PMOE_DT_BF16 || !a.w_fp8 || !a.in_fp8 || !a.oscale) return false;
+    if (!sw("PMOE_CONV_F8DMA", 1) || dtype != PMOE_DT_BF16 || !a.w_fp8 || !a.in_fp8 || !a.oscale) return false;
     if (a.ks != 3 || a.kh != 3 || a.kw != 3 || a.use_tapmap || a.stride != 1 || a.pad != 1 || a.dilate || a.in_shared) return false;
     if (a.out_step != 1 || a.Ho != a.H || a.Wo != a.W || a.res_mode != PMOE_RES_NONE) return false;
     if (a.Cin % 128 || a.CoutP % BN || a.Cout % 8 || a.N % a.ipe || a.in_ld % 16 || a.in_coff % 16) return false;
@@ -1309,20 +1292,14 @@ bool conv_dma_f8_plan(const ConvArgs& a, int dtype, ConvLaunch* l) {
     return true;
 }
 
-template <auto KERNEL, typename... Args> static int dma_go(dim3 grid, int nthr, size_t smem, hipStream_t st, Args... args) {
-    HIP_RET((ensure_dyn_lds<KERNEL>(160 * 1024)));
-    hipLaunchKernelGGL(KERNEL, grid, dim3(nthr), smem, st, args...);
-    return (int)hipGetLastError();
-}
-
 int conv_dma_launch(const ConvLaunch& l, hipStream_t st) {
     const ConvArgs& a = l.a;
     const int wgs = l.mblocks * (a.CoutP / BN);
     switch (l.kind) {
-    case CONV_DMA_F8: return dma_go<conv3x3_dma_f8_kernel>(dim3(wgs), NTHR, l.smem, st, a, l.pbuf);
-    case CONV_DMA_S2: return dma_go<conv3x3s2_dma_kernel<false>>(dim3(wgs), NTHR, l.smem, st, a, l.pbuf);
+    case CONV_DMA_F8: return launch<conv3x3_dma_f8_kernel>(dim3(wgs), NTHR, l.smem, st, a, l.pbuf);
+    case CONV_DMA_S2: return launch<conv3x3s2_dma_kernel<false>>(dim3(wgs), NTHR, l.smem, st, a, l.pbuf);
     case CONV_DMA_S2CLS:
-        return dma_go<conv3x3s2_dma_kernel<true>>(dim3(l.mblocks * ((a.CoutP + BN - 1) / BN)), NTHR, l.smem, st, a, l.pbuf);
+        return launch<conv3x3s2_dma_kernel<true>>(dim3(l.mblocks * ((a.CoutP + BN - 1) / BN)), NTHR, l.smem, st, a, l.pbuf);
     case CONV_DMA: break;
     default: return PMOE_ERR_ARG;
     }
@@ -1330,14 +1307,14 @@ int conv_dma_launch(const ConvLaunch& l, hipStream_t st) {
         // persistent workgroups, one per CU; the request stream of each runs across its tiles
         const int ntiles = l.narrow ? l.mblocks : wgs;
         const dim3 grid(ntiles < 256 ? ntiles : 256);
-        if (l.narrow) return dma_go<conv3x3_dma_stream_kernel<false, true>>(grid, NTHR + 4 * 64, l.smem, st, a, l.pbuf, ntiles, l.mpw, l.mph);
-        if (l.mf16) return dma_go<conv3x3_dma_stream_kernel<true>>(grid, NTHR + 4 * 64, l.smem, st, a, l.pbuf, ntiles, l.mpw, l.mph);
-        return dma_go<conv3x3_dma_stream_kernel<false>>(grid, NTHR + 4 * 64, l.smem, st, a, l.pbuf, ntiles, l.mpw, l.mph);
+        if (l.narrow) return launch<conv3x3_dma_stream_kernel<false, true>>(grid, NTHR + 4 * 64, l.smem, st, a, l.pbuf, ntiles, l.mpw, l.mph);
+        if (l.mf16) return launch<conv3x3_dma_stream_kernel<true>>(grid, NTHR + 4 * 64, l.smem, st, a, l.pbuf, ntiles, l.mpw, l.mph);
+        return launch<conv3x3_dma_stream_kernel<false>>(grid, NTHR + 4 * 64, l.smem, st, a, l.pbuf, ntiles, l.mpw, l.mph);
     }
     if (l.producer) {
-        if (l.mf16) return dma_go<conv3x3_dma_kernel<true, true>>(dim3(wgs), NTHR + 64, l.smem, st, a, l.pbuf);
-        return dma_go<conv3x3_dma_kernel<false, true>>(dim3(wgs), NTHR + 64, l.smem, st, a, l.pbuf);
+        if (l.mf16) return launch<conv3x3_dma_kernel<true, true>>(dim3(wgs), NTHR + 64, l.smem, st, a, l.pbuf);
+        return launch<conv3x3_dma_kernel<false, true>>(dim3(wgs), NTHR + 64, l.smem, st, a, l.pbuf);
     }
-    if (l.mf16) return dma_go<conv3x3_dma_kernel<true>>(dim3(wgs), NTHR, l.smem, st, a, l.pbuf);
-    return dma_go<conv3x3_dma_kernel<false>>(dim3(wgs), NTHR, l.smem, st, a, l.pbuf);
+    if (l.mf16) return launch<conv3x3_dma_kernel<true>>(dim3(wgs), NTHR, l.smem, st, a, l.pbuf);
+    return launch<conv3x3_dma_kernel<false>>(dim3(wgs), NTHR, l.smem, st, a, l.pbuf);
 }

@@ -426,24 +426,14 @@ __global__ void __launch_bounds__(512, 4) conv_igemm_lite_kernel(const ConvArgs 
 
 template <typename T, int LOG_RB, typename TL = T>
 static int launch_lite(const ConvArgs& a, int mblocks, size_t smem, hipStream_t st) {
-    auto k = conv_igemm_lite_kernel<T, LOG_RB, TL>;
-    HIP_RET((ensure_dyn_lds<conv_igemm_lite_kernel<T, LOG_RB, TL>>(160 * 1024)));
-    dim3 grid(mblocks * (a.CoutP / 128), 1, 1), block(512, 1, 1);
-    hipLaunchKernelGGL(k, grid, block, smem, st, a);
-    return (int)hipGetLastError();
+    return launch<conv_igemm_lite_kernel<T, LOG_RB, TL>>(dim3(mblocks * (a.CoutP / 128)), dim3(512), smem, st, a);
 }
 
 // ------------------------------------------------------------------------------------------------
 template <typename T, int LOG_RB, int WM, int WN, typename TL = T>
 static int launch_cfg(const ConvArgs& a, int mblocks, size_t smem, hipStream_t st) {
-    auto k = conv_igemm_kernel<T, LOG_RB, WM, WN, TL>;
-    HIP_RET((ensure_dyn_lds<conv_igemm_kernel<T, LOG_RB, WM, WN, TL>>(160 * 1024)));
-    dim3 grid(mblocks, a.CoutP / (WN * 64), 1), block(WM * WN * 64, 1, 1);
-    hipLaunchKernelGGL(k, grid, block, smem, st, a);
-    return (int)hipGetLastError();
+    return launch<conv_igemm_kernel<T, LOG_RB, WM, WN, TL>>(dim3(mblocks, a.CoutP / (WN * 64)), dim3(WM * WN * 64), smem, st, a);
 }
-
-static int env_switch(const char* name) { const char* ev = getenv(name); return ev ? atoi(ev) : 1; }
 
 // The tile of conv_igemm_body for a descriptor whose activations have `tsz`-byte elements (2 = bf16, 4 = f32) and whose MFMA
 // operands `esz`-byte elements in LDS (tsz, or 1: e4m3 weights).  Fills the tile fields of l->a with its chunk prefetch and
@@ -454,42 +444,33 @@ static int tile_plan(const ConvArgs& a, int tsz, int esz, ConvLaunch* l) {
     if (F8 && a.Cin % 64) return PMOE_ERR_ARG;
     if ((a.ks != 1 && a.ks != 3) || (a.stride != 1 && a.stride != 2) || (a.dilate && a.stride != 1)) return PMOE_ERR_ARG;
     if (a.N % a.ipe) return PMOE_ERR_ARG;
-    // A/B switches, read once: PMOE_CONV_CFG42=0 back to the 4-wave tile, PMOE_CONV_LITE=0 / PMOE_CONV_STAGGER=0 /
-    // PMOE_CONV_PREFETCH=0 without the LITE instantiation / the stagger / the chunk prefetch
-    static const int cfg42 = env_switch("PMOE_CONV_CFG42"), lite_on = env_switch("PMOE_CONV_LITE"),
-                     stg_on = env_switch("PMOE_CONV_STAGGER"), pf_on = env_switch("PMOE_CONV_PREFETCH");
     const int E = a.N / a.ipe;
     const bool wide = (a.CoutP % 128 == 0);
     // bf16, >= 128 output channels: 8 waves on a 256-pixel x 128-channel tile (each weight tile and each barrier serves
     // twice the pixels of the 4-wave 128 x 128 tile: +5-8 % on the 3x3 layers, +30 % on the stride-2 forward convs)
-    const bool big = wide && cfg42 && tsz == 2 && (long long)a.ipe * a.Ho * a.Wo >= 4096;   // not the MLP GEMMs
+    const bool big = wide && tsz == 2 && (long long)a.ipe * a.Ho * a.Wo >= 4096;   // not the MLP GEMMs
     const int log_rb_min = F8 ? 6 : 5;              // fp8: 64 or 128 channels per chunk
     // (measured on the stage-1 U-Net at B = 10, where the 28x28 / 14x14 layers give < 256 workgroups: falling back to the
     // 128-pixel 4-wave tile to double the workgroup count is SLOWER, 41.9 vs 32.3 ms of conv time per step)
     const int BM = wide ? (big ? 256 : 128) : 256, BN = wide ? 128 : 64;
-    auto p2 = [](int v) { int l = 0; while ((1 << l) < v) ++l; return l; };
     // candidate chunk widths (bytes per pixel row in LDS), widest first
     for (int log_rb = 7; log_rb >= log_rb_min; --log_rb) {
         const int rb = 1 << log_rb, ck = rb / esz;
         if (a.Cin % ck) continue;
-        int lTW = p2(a.Wo); if (lTW > 5) lTW = 5;
-        int lBM = p2(BM);
-        int lTH = p2(a.Ho); if (lTH > lBM - lTW) lTH = lBM - lTW;
-        const int TN = BM >> (lTW + lTH);
-        const int TW = 1 << lTW, TH = 1 << lTH;
-        const int lstride = a.ks == 1 ? 1 : a.stride;
-        const int PW = (TW - 1) * lstride + a.kw, PH = (TH - 1) * lstride + a.kh;
+        const PixelTile t = pixel_tile(a.Ho, a.Wo, a.ipe, ceil_log2(BM), 5);
+        const int TN = t.TN, lstride = a.ks == 1 ? 1 : a.stride;
+        const int PW = patch_extent(t.lTW, a.kw, lstride), PH = patch_extent(t.lTH, a.kh, lstride);
         const size_t pbytes = ((size_t)TN * PH * PW * rb + 255) & ~(size_t)255;
         // chunk prefetch: 8-wave tile, >= 2 channel chunks, the whole patch in <= 6 vectors per thread (24 VGPRs)
         const int nthr = big ? 512 : 256;
         // 64-channel chunks: the LITE instantiation (<= 128 VGPRs, 73 KiB LDS) puts TWO 8-wave workgroups on a CU, which
         // beats one workgroup with chunk prefetch + stagger by 12-30 % (l2 +12 %, l3 +30 %, l4 +25 %: 980-1000 TFLOP/s).
-        const bool lite = lite_on && big && log_rb == 7 && pbytes + 2 * (size_t)BN * rb <= 80 * 1024;   // two must fit a CU
+        const bool lite = big && log_rb == 7 && pbytes + 2 * (size_t)BN * rb <= 80 * 1024;   // two must fit a CU
         // (LITE with every load of a chunk's halo patch in flight at once -- one L2 round trip instead of two -- measured
         // within noise, +-2 %, and tools/stamp_conv.py still showed 28 % of the wave cycles in patch staging: the cost is
         // not the number of round trips)
         // (also the expert MLP GEMMs: 1x1 "images", K = 512..1536 in 64-channel chunks -- a latency chain of 8..24 chunks)
-        const bool prefetch = !F8 && !lite && pf_on && (big || (a.H == 1 && a.W == 1 && a.ks == 1)) && a.Cin / ck >= 2 &&
+        const bool prefetch = !F8 && !lite && (big || (a.H == 1 && a.W == 1 && a.ks == 1)) && a.Cin / ck >= 2 &&
                               (size_t)TN * PH * PW * (rb / 16) <= (size_t)6 * nthr && 2 * pbytes + 2 * (size_t)BN * rb <= 150 * 1024;
         size_t smem = pbytes * (prefetch ? 2 : 1) + 2 * (size_t)BN * rb;
         const size_t stg = (size_t)BM * BN * 4 / (lite ? 2 : 1);
@@ -497,14 +478,11 @@ static int tile_plan(const ConvArgs& a, int tsz, int esz, ConvLaunch* l) {
         if (smem > 150 * 1024) continue;
         ConvArgs& c = l->a;
         c = a;
-        c.stagger = stg_on && big && !lite;
+        c.stagger = big && !lite;
         c.prefetch = prefetch;
-        c.lTW = lTW; c.lTH = lTH; c.TN = TN;
-        c.n_groups = (a.ipe + TN - 1) / TN;
-        c.tiles_y = (a.Ho + TH - 1) / TH;
-        c.tiles_x = (a.Wo + TW - 1) / TW;
+        set_tile(c, t);
         l->kind = CONV_TILE;
-        l->mblocks = E * c.n_groups * c.tiles_y * c.tiles_x;
+        l->mblocks = E * t.per_expert();
         l->smem = smem;
         l->log_rb = log_rb; l->lite = lite;
         l->wm = big || !wide ? 4 : 2; l->wn = wide ? 2 : 1;

@@ -403,7 +403,7 @@ __global__ void __launch_bounds__(512, 2) conv3x3_resdma_kernel(const ConvArgs a
     const bool cvalid = cc * VE < a.Cout;
     bf16* out = (bf16*)a.out;
     const bf16* res = (const bf16*)a.res;
-    const bool res_pref = (a.res_mode == PMOE_RES_ADD || dbn) && a.prefetch;      // (a.prefetch: launcher, PMOE_RES_PREFETCH=0 = A/B)
+    const bool res_pref = (a.res_mode == PMOE_RES_ADD || dbn) && a.prefetch;      // (a.prefetch: the planner sets it wherever this kernel runs)
 
     if (ntile > 0) issue_patch(0, 0);
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");     // filter bank + first patch (DMA), the bias row (ds_write)
@@ -1002,16 +1002,12 @@ __global__ void __launch_bounds__(512, 2) conv3x3_respipe_kernel(const ConvArgs 
 
 // ------------------------------------------------------------------------------------------------
 // Which of this file's kernels takes the descriptor (l->res_dma, l->res_pipe; conv_select adds the per-mode requirements):
-//  - the all-waves-compute / LDS-DMA variant conv3x3_resdma_kernel (res_dma).  PMOE_RES_DMA=0: A/B switch back to the ping-pong
-//    kernel.  Its prefetch: PMOE_RES_PREFETCH=0 turns it off.
+//  - the all-waves-compute / LDS-DMA variant conv3x3_resdma_kernel (res_dma), with its patch prefetch.  PMOE_RES_DMA=0: A/B switch
+//    back to the ping-pong kernel.
 //  - the software-pipelined variant conv3x3_respipe_kernel (register read-out under the next tile's MFMAs) of what the LDS-DMA
-//    variant takes (res_pipe).  PMOE_RES_PIPE=0: A/B switch back to conv3x3_resdma_kernel.  Its residual / z loads:
-//    PMOE_RES_RZ_LATE=0 puts them back at the start of the tile.
-// (All read per launch.)
+//    variant takes (res_pipe).  PMOE_RES_PIPE=0: A/B switch back to conv3x3_resdma_kernel.
+// (Both read per launch.)
 bool conv_res_plan(const ConvArgs& a, int dtype, ConvLaunch* l) {
-    static int res_on = -1;       // PMOE_CONV_RES=0: route the <=64-channel layers to the generic kernel (A/B runs)
-    if (res_on < 0) { const char* ev = getenv("PMOE_CONV_RES"); res_on = ev ? atoi(ev) : 1; }
-    if (!res_on) return false;
     if (dtype != PMOE_DT_BF16 || a.ks != 3 || a.stride != 1 || a.pad != 1 || a.dilate) return false;
     if (a.CoutP != 64 || a.Cout % 8 || (a.Cin != 64 && a.Cin != 16)) return false;
     if (a.act != PMOE_ACT_NONE || a.drop_p > 0.f) return false;
@@ -1020,12 +1016,9 @@ bool conv_res_plan(const ConvArgs& a, int dtype, ConvLaunch* l) {
     if (a.res_mode == PMOE_RES_DBN && a.Cin != 64) return false;    // (conv3x3_resdma_kernel only: conv_select)
     if (a.res_mode == PMOE_RES_INBN && (a.Cin != 64 || a.in_shared || !a.bn)) return false;      // (conv3x3_respipe_kernel<false, 3> only)
     if (a.N % a.ipe || a.Ho != a.H || a.Wo != a.W) return false;
-    auto p2 = [](int v) { int l = 0; while ((1 << l) < v) ++l; return l; };
-    int lTW = p2(a.Wo); if (lTW > 5) lTW = 5;
-    int lTH = p2(a.Ho); if (lTH > 8 - lTW) lTH = 8 - lTW;
-    const int TN = 256 >> (lTW + lTH);
-    const int TW = 1 << lTW, TH = 1 << lTH;
-    const int NPIX = TN * (TH + 2) * (TW + 2);
+    const PixelTile t = pixel_tile(a.Ho, a.Wo, a.ipe, 8, 5);
+    const int PW = patch_extent(t.lTW, 3, 1), PH = patch_extent(t.lTH, 3, 1);
+    const int NPIX = t.TN * PH * PW;
     const int log_rb = a.Cin == 64 ? 7 : 5;
     const int rb = 1 << log_rb, cpr = rb / 16;
     if (NPIX * cpr > 11 * 256) return false;
@@ -1036,11 +1029,7 @@ bool conv_res_plan(const ConvArgs& a, int dtype, ConvLaunch* l) {
     if (smem + (a.bias ? 256 : 0) > 163840) return false;
     const int E = a.N / a.ipe;
     ResPlan& p = l->res;
-    p.lTW = lTW; p.lTH = lTH; p.TN = TN;
-    p.n_groups = (a.ipe + TN - 1) / TN;
-    p.tiles_y = (a.Ho + TH - 1) / TH;
-    p.tiles_x = (a.Wo + TW - 1) / TW;
-    p.tiles_per_expert = p.n_groups * p.tiles_y * p.tiles_x;
+    p.tiles_per_expert = t.per_expert();
     int wpe = 256 / E; if (wpe < 1) wpe = 1;
     if (wpe > p.tiles_per_expert) wpe = p.tiles_per_expert;
     p.wgs_per_expert = wpe;
@@ -1048,54 +1037,36 @@ bool conv_res_plan(const ConvArgs& a, int dtype, ConvLaunch* l) {
     p.smem = smem;
     ConvArgs& c = l->a;
     c = a;
-    c.lTW = p.lTW; c.lTH = p.lTH; c.TN = p.TN; c.n_groups = p.n_groups; c.tiles_y = p.tiles_y; c.tiles_x = p.tiles_x;
+    set_tile(c, t);
     l->kind = CONV_RES;
     l->mblocks = E * wpe;
 
     // the LDS-DMA variant: patch pieces of 1 KiB (a region of at least the 256 x 128-byte staging), the piece decode exact
-    const char* evd = getenv("PMOE_RES_DMA");
-    const int PW = (1 << p.lTW) + 2, PH = (1 << p.lTH) + 2;
-    const int npiece = (p.TN * PH * PW + 7) / 8;
+    const int npiece = (NPIX + 7) / 8;
     int pb = npiece * 1024;
     if (pb < 256 * 128) pb = 256 * 128;
     const size_t sm = (size_t)9 * 64 * 128 + 2 * (size_t)pb + 256 + 1024;     // + bias row + BatchNorm coefficient rows
-    l->res_dma = p.log_rb == 7 && !a.in_shared && !(evd && !atoi(evd)) && magic_div_exact(npiece * 8, PW, PH, &l->mpw, &l->mph) &&
-                 npiece <= 48 && sm <= 163840 && p.lTW >= 4 && (long long)a.ipe * a.H * a.W * a.in_ld * 2 < 0x7ff00000ll;
+    l->res_dma = p.log_rb == 7 && !a.in_shared && sw("PMOE_RES_DMA", 1) && magic_div_exact(npiece * 8, PW, PH, &l->mpw, &l->mph) &&
+                 npiece <= 48 && sm <= 163840 && t.lTW >= 4 && (long long)a.ipe * a.H * a.W * a.in_ld * 2 < 0x7ff00000ll;
     if (l->res_dma) { l->pbuf = pb; l->smem = sm; }
     // the pipelined variant: (no statistics with a residual), 11-bit image index, 32-bit offsets of the output and residual
     // (measured and not kept, same box, profiles/r03_kernel_ab.log: the requests for the next patch as straight-line code inside
     //  the MFMA block -- range checks as one guarded subtraction per bound, a wave without a 6th piece requesting its 5th again --
     //  and the residual / z vectors loaded into the registers the read-out has just freed: within 1 % on the stem, 3-5 % slower
     //  on layer1)
-    const char* evp = getenv("PMOE_RES_PIPE");
-    l->res_pipe = l->res_dma && !(evp && !atoi(evp)) && a.ipe <= 2047 && !(a.res_mode == PMOE_RES_ADD && a.stats) &&
+    l->res_pipe = l->res_dma && sw("PMOE_RES_PIPE", 1) && a.ipe <= 2047 && !(a.res_mode == PMOE_RES_ADD && a.stats) &&
                   (long long)a.ipe * a.Ho * a.Wo * a.out_ld * 2 < 0x7ff00000ll &&
                   (a.res_mode == PMOE_RES_NONE || (long long)a.ipe * a.Ho * a.Wo * a.res_ld * 2 < 0x7ff00000ll);
-    const char* evz = getenv("PMOE_RES_RZ_LATE");
-    l->rz_late = !(evz && !atoi(evz));
-    const char* evf = getenv("PMOE_RES_PREFETCH");
-    if (l->res_dma && !l->res_pipe) c.prefetch = !(evf && !atoi(evf));
+    if (l->res_dma && !l->res_pipe) c.prefetch = 1;
     // 1000 + LOG_RB = conv3x3_res_kernel; + 100 (+ 10 bias) = conv3x3_resdma_kernel; + 200 + 10 bias + 20 mode = conv3x3_respipe_kernel
     const int mode = a.res_mode == PMOE_RES_INBN ? 3 : a.res_mode == PMOE_RES_DBN ? 2 : a.res_mode == PMOE_RES_ADD ? 1 : 0;
     l->code = 1000 + p.log_rb + (l->res_dma ? (l->res_pipe ? 200 + 20 * mode : 100) + (a.bias ? 10 : 0) : 0);
     return true;
 }
 
-template <bool BIAS, int MODE>
-static int launch_respipe(const ConvLaunch& l, dim3 grid, hipStream_t st) {
-    const ResPlan& p = l.res;
-    if constexpr (MODE == 1 || MODE == 2) {              // PMOE_RES_RZ_LATE=0: the side-input loads back at the start of the tile (A/B)
-        if (!l.rz_late) {
-            HIP_RET((ensure_dyn_lds<conv3x3_respipe_kernel<BIAS, MODE, false>>(163840)));
-            hipLaunchKernelGGL((conv3x3_respipe_kernel<BIAS, MODE, false>), grid, dim3(512), l.smem, st, l.a, p.tiles_per_expert,
-                               p.wgs_per_expert, l.pbuf, l.mpw, l.mph);
-            return (int)hipGetLastError();
-        }
-    }
-    HIP_RET((ensure_dyn_lds<conv3x3_respipe_kernel<BIAS, MODE>>(163840)));
-    hipLaunchKernelGGL((conv3x3_respipe_kernel<BIAS, MODE>), grid, dim3(512), l.smem, st, l.a, p.tiles_per_expert, p.wgs_per_expert,
-                       l.pbuf, l.mpw, l.mph);
-    return (int)hipGetLastError();
+template <bool BIAS, int MODE> static int launch_respipe(const ConvLaunch& l, dim3 grid, hipStream_t st) {
+    return launch<conv3x3_respipe_kernel<BIAS, MODE>>(grid, dim3(512), l.smem, st, l.a, l.res.tiles_per_expert, l.res.wgs_per_expert,
+                                                       l.pbuf, l.mpw, l.mph);
 }
 
 int conv_res_launch(const ConvLaunch& l, hipStream_t st) {
@@ -1114,26 +1085,12 @@ int conv_res_launch(const ConvLaunch& l, hipStream_t st) {
                          : launch_respipe<false, 0>(l, grid, st);
     }
     if (l.res_dma) {                                     // (never PMOE_RES_INBN: conv_select gives that mode to res_pipe or refuses)
-        if (a.bias) {
-            HIP_RET((ensure_dyn_lds<conv3x3_resdma_kernel<true>>(163840)));
-            hipLaunchKernelGGL(conv3x3_resdma_kernel<true>, grid, block, l.smem, st, a, p.tiles_per_expert, p.wgs_per_expert, l.pbuf, l.mpw, l.mph);
-        } else {
-            HIP_RET((ensure_dyn_lds<conv3x3_resdma_kernel<false>>(163840)));
-            hipLaunchKernelGGL(conv3x3_resdma_kernel<false>, grid, block, l.smem, st, a, p.tiles_per_expert, p.wgs_per_expert, l.pbuf, l.mpw, l.mph);
-        }
-        return (int)hipGetLastError();
+        if (a.bias) return launch<conv3x3_resdma_kernel<true>>(grid, block, l.smem, st, a, p.tiles_per_expert, p.wgs_per_expert, l.pbuf, l.mpw, l.mph);
+        return launch<conv3x3_resdma_kernel<false>>(grid, block, l.smem, st, a, p.tiles_per_expert, p.wgs_per_expert, l.pbuf, l.mpw, l.mph);
     }
     const int region = (int)((p.smem - (size_t)9 * 64 * (1 << p.log_rb)) / 2);
-    if (p.log_rb == 7 && a.bias) {
-        HIP_RET((ensure_dyn_lds<conv3x3_res_kernel<7, true>>(163840)));
-        hipLaunchKernelGGL((conv3x3_res_kernel<7, true>), grid, block, p.smem + 256, st, a, p.tiles_per_expert,
-                           p.wgs_per_expert, region);
-    } else if (p.log_rb == 7) {
-        HIP_RET((ensure_dyn_lds<conv3x3_res_kernel<7, false>>(163840)));
-        hipLaunchKernelGGL((conv3x3_res_kernel<7, false>), grid, block, p.smem, st, a, p.tiles_per_expert, p.wgs_per_expert, region);
-    } else {
-        HIP_RET((ensure_dyn_lds<conv3x3_res_kernel<5, false>>(163840)));
-        hipLaunchKernelGGL((conv3x3_res_kernel<5, false>), grid, block, p.smem, st, a, p.tiles_per_expert, p.wgs_per_expert, region);
-    }
-    return (int)hipGetLastError();
+    if (p.log_rb == 7 && a.bias)
+        return launch<conv3x3_res_kernel<7, true>>(grid, block, p.smem + 256, st, a, p.tiles_per_expert, p.wgs_per_expert, region);
+    if (p.log_rb == 7) return launch<conv3x3_res_kernel<7, false>>(grid, block, p.smem, st, a, p.tiles_per_expert, p.wgs_per_expert, region);
+    return launch<conv3x3_res_kernel<5, false>>(grid, block, p.smem, st, a, p.tiles_per_expert, p.wgs_per_expert, region);
 }

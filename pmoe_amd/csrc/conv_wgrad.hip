@@ -61,7 +61,7 @@ __global__ void __launch_bounds__(WgradCfg<T>::NW * 64) conv_wgrad_kernel(const 
     const int npairs = n_ci_blk * ((a.Cout + CKW - 1) / CKW);
     const unsigned flat = xcd_remap(blockIdx.x, gridDim.x);
     const int nsplit = (int)(gridDim.x / npairs);
-    // (a.slice_fastest: the round-1 order, K slice fastest -- A/B switch PMOE_WGRAD_SLICE_FASTEST=1)
+    // (a.slice_fastest: the round-1 order, K slice fastest -- its A/B switch is retired, the launcher always passes 0)
     const int pair = a.slice_fastest ? (int)(blockIdx.x / nsplit) : (int)(flat % npairs);
     const int split = a.slice_fastest ? (int)(blockIdx.x % nsplit) : (int)(flat / npairs);
     const int cob = pair / n_ci_blk, cib = pair % n_ci_blk;
@@ -1089,8 +1089,6 @@ static int wgrad_finish(const WgradPlan& p, hipStream_t st, bool force = false) 
     return 0;
 }
 
-static int wgrad_p2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
-
 // per-image filter gradient of a <= 16-input-channel 3x3 stride-1 convolution whose output gradient is given as (g, z) of the
 // BatchNorm + ReLU behind it (conv_wgrad_bnbwd_kernel): the plan, or the reason why the kernel does not serve the descriptor
 static int wgrad_bnbwd_plan(int dtype, int z_ld, WgradPlan* p) {
@@ -1099,11 +1097,12 @@ static int wgrad_bnbwd_plan(int dtype, int z_ld, WgradPlan* p) {
     if (a.Cin > 16 || a.Cin % 8 || a.Cout > 64 || a.Cout % 8 || a.CoutP != 64 || a.CinP != 64) return PMOE_ERR_UNSUPPORTED;
     if (a.Ho != a.H || a.Wo != a.W || a.N % a.ipe || (long long)a.H * a.W < 256) return PMOE_ERR_UNSUPPORTED;
     if (z_ld % 8 || z_ld < a.Cout || a.x_ld % 8 || a.dy_ld % 8) return PMOE_ERR_ARG;
-    a.lTW = wgrad_p2(a.W) > 5 ? 5 : wgrad_p2(a.W);
+    // (not pixel_tile: one image per 256-pixel block whatever the map height -- lTH is not clamped by it and TN stays 1)
+    a.lTW = ceil_log2(a.W) > 5 ? 5 : ceil_log2(a.W);
     a.lTH = 8 - a.lTW; a.TN = 1; a.n_groups = a.ipe;
     a.tiles_y = (a.H + (1 << a.lTH) - 1) >> a.lTH;
     a.tiles_x = (a.W + (1 << a.lTW) - 1) >> a.lTW;
-    const int NPIX = ((1 << a.lTW) + 2) * ((1 << a.lTH) + 2);
+    const int NPIX = patch_extent(a.lTW, 3, 1) * patch_extent(a.lTH, 3, 1);
     if (NPIX * 2 > 1024) return PMOE_ERR_UNSUPPORTED;                 // two 16-byte patch items per thread
     p->kind = WGRAD_BNBWD;
     p->E = a.N / a.ipe; p->taps = 9; p->nsplit = 1; p->ws_floats = 0;   // per image: no K-split scratch
@@ -1115,44 +1114,40 @@ static int wgrad_bnbwd_plan(int dtype, int z_ld, WgradPlan* p) {
 
 // The LDS-DMA kernels: dense 3x3 stride 1 in bf16 on 256-pixel blocks (NPIX patch pixels, PW x PH per image; `tiles` channel tiles
 // per expert; the tile and the K-split are already in *p).  conv_wgrad_dma_kernel<PIN, WCI, PAIRS, REQ> with its 2 x 4 wave layout (WCI = 1) for <= 32 input channels,
-// conv_wgrad_dma2_kernel<lTW, AHEAD> (separated roles) for the wide layout on 16- or 32-pixel-wide tiles.  false: the
+// conv_wgrad_dma2_kernel<lTW> (separated roles) for the wide layout on 16- or 32-pixel-wide tiles.  false: the
 // register-staged kernel serves the descriptor.  Every switch is read per call (tools/ab_conv.py flips them inside one process).
 static bool wgrad_dma_plan(int NPIX, int PW, int PH, int tiles, WgradPlan* p) {
     const WgradArgs& a = p->a;
-    const char* evd = getenv("PMOE_WGRAD_DMA");          // A/B: 0 = back to register staging
     const long long xbytes = (long long)a.ipe * a.H * a.W * a.x_ld * 2, dybytes = (long long)a.ipe * a.Ho * a.Wo * a.dy_ld * 2;
     const int npiece = (NPIX + 7) / 8;
     const size_t sm = 2 * ((size_t)256 * 128 + (size_t)npiece * 1024);
-    if ((evd && !atoi(evd)) || a.ks != 3 || a.stride != 1 || a.lTW < 2 || npiece > 48 || sm > 160 * 1024 ||
+    if (!sw("PMOE_WGRAD_DMA", 1) || a.ks != 3 || a.stride != 1 || a.lTW < 2 || npiece > 48 || sm > 160 * 1024 ||
         xbytes >= 0x7ff00000ll || dybytes >= 0x7ff00000ll || !magic_div_exact(npiece * 8, PW, PH, &p->mpw, &p->mph))
         return false;
-    const char* evn = getenv("PMOE_WGRAD_NARROW");       // A/B: 0 = the 2 x 2 x 2 wave layout for every layer
-    const char* ev2 = getenv("PMOE_WGRAD_V2");           // A/B: 0 = the 8-wave kernel for the wide layout too
-    const char* evx = getenv("PMOE_WGRAD_PIPE");         // set: the PIN / timing modes, which belong to the 8-wave kernel
-    const bool narrow = a.Cin <= 32 && !(evn && !atoi(evn));
-    const bool v2 = !narrow && !(ev2 && !atoi(ev2)) && !evx && (a.lTW == 4 || a.lTW == 5) && a.ipe <= 511;
+    // A/B switches: PMOE_WGRAD_DMA=0 back to register staging (above), PMOE_WGRAD_NARROW=0 the 2 x 2 x 2 wave layout for every layer,
+    // PMOE_WGRAD_V2=0 the 8-wave kernel for the wide layout too; PMOE_WGRAD_PIPE, when set at all: the PIN / timing modes, which
+    // belong to the 8-wave kernel
+    const int pipe_unset = INT_MIN, pipe_sw = sw("PMOE_WGRAD_PIPE", pipe_unset);
+    const bool narrow = a.Cin <= 32 && sw("PMOE_WGRAD_NARROW", 1);
+    const bool v2 = !narrow && sw("PMOE_WGRAD_V2", 1) && pipe_sw == pipe_unset && (a.lTW == 4 || a.lTW == 5) && a.ipe <= 511;
     p->kind = v2 ? WGRAD_DMA2 : WGRAD_DMA;
     p->code = narrow ? 7109 : v2 ? 7309 : 7009;
     p->grid = dim3(p->nsplit * tiles, 1, p->E); p->block = dim3(512);
     p->smem = sm < 49152 ? 49152 : sm;                   // room for the flush's fold
-    const int pipe = evx ? atoi(evx) : 1;
+    const int pipe = pipe_sw == pipe_unset ? 1 : pipe_sw;
     p->pin = 1; p->wci = narrow ? 1 : 2;
     if (v2) {
-        const char* eva = getenv("PMOE_WGRAD_AHEAD");    // A/B: fragment read-ahead in taps (5 | 6)
-        p->ahead = eva && atoi(eva) == 6 ? 6 : 5;
 #ifdef PMOE_STAMP          // tools build only (tools/stamp_conv.py --build): timing modes with WRONG results, see the kernel's main loop
     } else if (pipe == 2 || pipe == 3) {
         p->pin = pipe; p->wci = 2;
 #endif
     } else if (narrow) {
-        const char* evp = getenv("PMOE_WGRAD_PAIRS");    // A/B: 0 = one tap per MFMA column block
-        p->pairs = a.Cin <= 16 && !(evp && !atoi(evp));
+        p->pairs = a.Cin <= 16;                          // two taps per MFMA column block
         if (p->smem < (size_t)3 * 3 * 2 * 4096) p->smem = (size_t)3 * 3 * 2 * 4096;      // fold room: (WK - 1) x 3 taps x 2 tile waves
     } else if (pipe == 0) {
         p->pin = 0;
     } else {
-        const char* evr = getenv("PMOE_WGRAD_REQ");      // A/B: 0 = round-2 request code, 1 = precomputed, at the top
-        const int req = a.ipe > 511 ? 0 : evr ? atoi(evr) : 1;
+        const int req = a.ipe > 511 ? 0 : sw("PMOE_WGRAD_REQ", 1);      // A/B: 0 = round-2 request code, 1 = precomputed, at the top
         p->req = req == 1 || req == 2 ? req : 0;
     }
     return true;
@@ -1179,29 +1174,22 @@ int wgrad_select(const WgradArgs& a0, int dtype, const WgradBn& bn, WgradPlan* p
     p->E = a.N / a.ipe; p->taps = a.ks * a.ks;
     // the largest pixel block (256, 128, 64) whose halo patch fits the per-thread load budget and LDS; rows of up to 32 pixels
     const int lstride = a.ks == 1 ? 1 : a.stride;
-    a.lTW = wgrad_p2(a.Wo) > 5 ? 5 : wgrad_p2(a.Wo);
     int lBM = 8, PW, PH, NPIX, need;
     size_t smem;
     for (;; --lBM) {
         if (lBM < 6) return done(PMOE_ERR_UNSUPPORTED);
-        a.lTH = wgrad_p2(a.Ho) > lBM - a.lTW ? lBM - a.lTW : wgrad_p2(a.Ho);
-        a.TN = (1 << lBM) >> (a.lTW + a.lTH);
-        PW = ((1 << a.lTW) - 1) * lstride + a.ks; PH = ((1 << a.lTH) - 1) * lstride + a.ks;
+        set_tile(a, pixel_tile(a.Ho, a.Wo, a.ipe, lBM, 5));
+        PW = patch_extent(a.lTW, a.ks, lstride); PH = patch_extent(a.lTH, a.ks, lstride);
         NPIX = a.TN * PH * PW;
         need = (NPIX * 8 + NW * 64 - 1) / (NW * 64);   // 16-byte patch loads per thread
         smem = ((size_t)(1 << lBM) + NPIX) * 192;
         if (need <= M2 && smem <= 150 * 1024) break;
     }
-    a.n_groups = (a.ipe + a.TN - 1) / a.TN;
-    a.tiles_y = (a.Ho + (1 << a.lTH) - 1) >> a.lTH;
-    a.tiles_x = (a.Wo + (1 << a.lTW) - 1) >> a.lTW;
     const int mbpe = a.n_groups * a.tiles_y * a.tiles_x;
     // K-split: one workgroup per CU is resident; ONE round of 256 workgroups measured best (each walks more m-blocks,
     // flushes its 9 x 64 x 64 accumulators once, no second-round tail): 2 rounds -10 %, 1.25-1.5 rounds -25..30 %.
-    // PMOE_WGRAD_WGS overrides the target for A/B runs (latched on first use).
     const int tiles = ((a.Cout + CKW - 1) / CKW) * ((a.Cin + CKW - 1) / CKW);     // channel tiles per expert
-    static int target = 0;
-    if (!target) { const char* ev = getenv("PMOE_WGRAD_WGS"); target = ev ? atoi(ev) : 256; }
+    const int target = 256;
     int want = (target + tiles * p->E - 1) / (tiles * p->E);
     if (want < 1) want = 1;
     if (want > mbpe) want = mbpe;
@@ -1210,7 +1198,7 @@ int wgrad_select(const WgradArgs& a0, int dtype, const WgradBn& bn, WgradPlan* p
         if (a.TN != 1) return done(PMOE_ERR_UNSUPPORTED);
         a.mb_per_wg = a.tiles_y * a.tiles_x;
     }
-    { const char* ev = getenv("PMOE_WGRAD_SLICE_FASTEST"); a.slice_fastest = ev ? atoi(ev) : 0; }
+    a.slice_fastest = 0;
     p->nsplit = (mbpe + a.mb_per_wg - 1) / a.mb_per_wg;
     p->ws_floats = (a.per_image || p->nsplit == 1) ? 0 : (long long)p->nsplit * p->E * p->taps * a.CoutP * a.CinP;
     if (esz == 2 && lBM == 8 && wgrad_dma_plan(NPIX, PW, PH, tiles, p)) return p->code;
@@ -1223,10 +1211,8 @@ int wgrad_select(const WgradArgs& a0, int dtype, const WgradBn& bn, WgradPlan* p
     return p->code = 6000 + p->taps * 100 + p->maxv;
 }
 
-template <auto KERNEL, typename... Args> static int wgrad_go(const WgradPlan& p, hipStream_t st, Args... args) {
-    HIP_RET((ensure_dyn_lds<KERNEL>(160 * 1024)));
-    hipLaunchKernelGGL(KERNEL, p.grid, p.block, p.smem, st, p.a, args...);
-    return (int)hipGetLastError();
+template <auto KERNEL, typename... Args> static int wgrad_go(const WgradPlan& p, hipStream_t st, const Args&... args) {
+    return launch<KERNEL>(p.grid, p.block, p.smem, st, p.a, args...);
 }
 
 template <typename T> static int wgrad_tile_launch(const WgradPlan& p, hipStream_t st) {
@@ -1252,8 +1238,8 @@ static int wgrad_dma_launch(const WgradPlan& p, hipStream_t st) {
 
 // round 4: four accumulating waves (one per SIMD, k-block-deep fragment read-ahead) + one request-only wave
 static int wgrad_dma2_launch(const WgradPlan& p, hipStream_t st) {
-    if (p.a.lTW == 5) return p.ahead == 6 ? wgrad_go<conv_wgrad_dma2_kernel<5, 6>>(p, st, p.mpw, p.mph) : wgrad_go<conv_wgrad_dma2_kernel<5>>(p, st, p.mpw, p.mph);
-    return p.ahead == 6 ? wgrad_go<conv_wgrad_dma2_kernel<4, 6>>(p, st, p.mpw, p.mph) : wgrad_go<conv_wgrad_dma2_kernel<4>>(p, st, p.mpw, p.mph);
+    if (p.a.lTW == 5) return wgrad_go<conv_wgrad_dma2_kernel<5>>(p, st, p.mpw, p.mph);
+    return wgrad_go<conv_wgrad_dma2_kernel<4>>(p, st, p.mpw, p.mph);
 }
 
 static int conv_wgrad_bnbwd_launch(const WgradPlan& p, const WgradBn& bn, hipStream_t st) {

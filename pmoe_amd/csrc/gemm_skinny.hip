@@ -2,7 +2,7 @@
 //   Y[m][n] = epilogue( sum_k X[m][k] * W[n][k] ),   m < images-per-expert (the batch, 64), n = 16..1536, k = 16..1536
 // i.e. the 1x1 "convolutions" over 1x1 images of the grouped engine -- and, with a loop over the filter taps (row m = output
 // pixel, its operand row = the tap-shifted input pixel, zero outside the image), the 3x3 / 1x1 convolutions of feature maps
-// with at most PMOE_SKINNY_MAXROWS (default 3200) pixels per expert (closed-loop inference at B = 1: layer2 .. layer4; the 14x14
+// with at most 3200 pixels (gemm_skinny_plan) per expert (closed-loop inference at B = 1: layer2 .. layer4; the 14x14
 // bottleneck of the stage-1 U-Net at B = 10; beyond that the LDS-staged kernels win: measured).  On the generic implicit-GEMM kernel these are a
 // serial chain of 8..24 channel chunks on 16 workgroups (~90 us per launch: 2 TFLOP/s).  Here one workgroup owns a
 // 64-row x 64-column tile of ONE expert and its 4 waves split K between them: every wave streams its k-slices of both
@@ -170,18 +170,10 @@ __global__ void __launch_bounds__(NW * 64) gemm_skinny_kernel(const ConvArgs a) 
 // bf16, no fused statistics, dense output lattice, and FEW output rows per expert: the expert MLP layers (1x1 "images") and
 // their data gradients, and the 3x3 / 1x1 convolutions of tiny feature maps at tiny batches (closed-loop inference, B = 1:
 // layer3 / layer4 are 14x14 / 7x7 -- on the generic kernel a serial chain of 36..72 tap-chunks on a dozen workgroups)
-// PMOE_SKINNY_NW8: reduction length (taps * Cin) from which 8 waves split K (default 0 = never: measured no faster)
+// (8 waves splitting K measured no faster than 4 at any reduction length: gemm_skinny_kernel<4> is the one instantiation)
 bool gemm_skinny_plan(const ConvArgs& a, int dtype, ConvLaunch* l) {
-    static int on = -1, maxrows = 0, nw8 = 0;   // PMOE_GEMM_SKINNY=0: back to the generic implicit-GEMM kernel (A/B measurements)
-    if (on < 0) {
-        const char* ev = getenv("PMOE_GEMM_SKINNY");
-        on = ev ? atoi(ev) : 1;
-        const char* mr = getenv("PMOE_SKINNY_MAXROWS");
-        maxrows = mr ? atoi(mr) : 3200;
-        const char* nw = getenv("PMOE_SKINNY_NW8");
-        nw8 = nw ? atoi(nw) : 0;
-    }
-    if (!on || dtype != PMOE_DT_BF16 || a.stats || a.dilate || a.use_tapmap || a.out_step != 1) return false;
+    const int maxrows = 3200;                   // output rows per expert up to which a conv counts as "few rows"
+    if (dtype != PMOE_DT_BF16 || a.stats || a.dilate || a.use_tapmap || a.out_step != 1) return false;
     if ((a.ks != 1 && a.ks != 3) || a.kh != a.ks || a.kw != a.ks || (a.stride != 1 && a.stride != 2)) return false;
     const bool mlp = a.H == 1 && a.W == 1 && a.Ho == 1 && a.Wo == 1 && a.ks == 1;
     if (!mlp && (long long)a.ipe * a.Ho * a.Wo > maxrows) return false;
@@ -191,21 +183,14 @@ bool gemm_skinny_plan(const ConvArgs& a, int dtype, ConvLaunch* l) {
           (!a.res_mode || (a.res && a.res_ld % VE == 0 && a.res_coff % VE == 0))))
         return false;
     l->kind = CONV_SKINNY; l->code = 3000; l->a = a; l->mblocks = 0;      // (no statistics: a.stats is null)
-    l->nw = nw8 > 0 && a.ks * a.ks * a.Cin >= nw8 ? 8 : 4;
     return true;
-}
-
-template <int NW> static int skinny_launch_nw(const ConvArgs& a, const dim3& grid, hipStream_t st) {
-    const int smem = NREG * BM * BN * (int)sizeof(float);
-    HIP_RET((ensure_dyn_lds<gemm_skinny_kernel<NW>>(smem)));
-    hipLaunchKernelGGL(gemm_skinny_kernel<NW>, grid, dim3(NW * 64), smem, st, a);
-    return (int)hipGetLastError();
 }
 
 int gemm_skinny_launch(const ConvLaunch& l, hipStream_t st) {
     const ConvArgs& a = l.a;
     const dim3 grid(a.CoutP / BN, (a.ipe * a.Ho * a.Wo + BM - 1) / BM, a.N / a.ipe);
-    return l.nw == 8 ? skinny_launch_nw<8>(a, grid, st) : skinny_launch_nw<4>(a, grid, st);
+    constexpr int smem = NREG * BM * BN * (int)sizeof(float);        // (also the size of the kernel's dynamic-LDS opt-in)
+    return launch<gemm_skinny_kernel<4>, smem>(grid, dim3(4 * 64), smem, st, a);
 }
 
 
@@ -305,8 +290,7 @@ int mlp_wgrad_launch(const MlpWgradArgs& a, hipStream_t st) {
     if (a.x_coff + a.Cin > a.x_ld || a.dy_coff + a.Cout > a.dy_ld) return PMOE_ERR_ARG;
     if (a.cin_real <= 0 || a.cin_real > a.Cin || a.cout_real <= 0 || a.cout_real > a.Cout) return PMOE_ERR_ARG;
     const dim3 grid((a.Cin + 63) / 64, (a.Cout + 63) / 64, a.N / a.ipe);
-    hipLaunchKernelGGL(mlp_wgrad_kernel, grid, dim3(256), 0, st, a);
-    return (int)hipGetLastError();
+    return launch<mlp_wgrad_kernel, 0>(grid, dim3(256), 0, st, a);
 }
 
 extern "C" int pmoe_mlp_wgrad(const void* x, const void* dy, float* grads, float* bias_grads, int32_t n, int32_t ipe,

@@ -55,7 +55,7 @@ struct WgradArgs {
     int cout_real, cin_real;
     int defer_fold;        // 1: conv_wgrad_launch stops after the MFMA kernel (conv_wgrad_fold runs the tail)
     int lTW, lTH, TN, n_groups, tiles_y, tiles_x, mb_per_wg;
-    int slice_fastest;     // launcher: grid order of round 1 (A/B switch)
+    int slice_fastest;     // grid order of round 1: always 0 (its switch is retired; the kernels still read the field)
 };
 
 // The piece decode of the LDS-DMA kernels divides by multiply-and-shift: patch pixel pp of PH rows x PW pixels per image lies in
@@ -67,9 +67,40 @@ inline bool magic_div_exact(int n, int PW, int PH, int* mpw, int* mph) {
     return true;
 }
 
-// resident-weight ping-pong kernel and its LDS-DMA successors for the <=64-channel 3x3 stride-1 layers (conv_res.hip)
+// ceil(log2(v)): the smallest l with 2^l >= v
+inline int ceil_log2(int v) {
+    int l = 0;
+    while ((1 << l) < v) ++l;
+    return l;
+}
+
+// The pixel tile of the conv and weight-gradient kernels: a block of 2^lBM output pixels cut as TN images x 2^lTH rows x 2^lTW
+// pixels -- rows as wide as the map needs (at most 2^ltw_max), then as many rows as it needs, the rest of the block over images --
+// and how many of them cover one expert's ipe maps of Ho x Wo pixels.
+struct PixelTile {
+    int lTW, lTH, TN, n_groups, tiles_y, tiles_x;
+    int per_expert() const { return n_groups * tiles_y * tiles_x; }
+};
+inline PixelTile pixel_tile(int Ho, int Wo, int ipe, int lBM, int ltw_max) {
+    PixelTile t;
+    t.lTW = ceil_log2(Wo) > ltw_max ? ltw_max : ceil_log2(Wo);
+    t.lTH = ceil_log2(Ho) > lBM - t.lTW ? lBM - t.lTW : ceil_log2(Ho);
+    t.TN = (1 << lBM) >> (t.lTW + t.lTH);
+    t.n_groups = (ipe + t.TN - 1) / t.TN;
+    t.tiles_y = (Ho + (1 << t.lTH) - 1) >> t.lTH;
+    t.tiles_x = (Wo + (1 << t.lTW) - 1) >> t.lTW;
+    return t;
+}
+// input pixels under 2^l output pixels along one axis (the halo patch is patch_extent(lTW, ..) x patch_extent(lTH, ..) per image)
+inline int patch_extent(int l, int k, int stride) { return ((1 << l) - 1) * stride + k; }
+template <typename Args> inline void set_tile(Args& a, const PixelTile& t) {      // ConvArgs | WgradArgs
+    a.lTW = t.lTW; a.lTH = t.lTH; a.TN = t.TN; a.n_groups = t.n_groups; a.tiles_y = t.tiles_y; a.tiles_x = t.tiles_x;
+}
+
+// resident-weight ping-pong kernel and its LDS-DMA successors for the <=64-channel 3x3 stride-1 layers (conv_res.hip): what the
+// tile fields of ConvLaunch.a do not say
 struct ResPlan {
-    int lTW, lTH, TN, n_groups, tiles_y, tiles_x, tiles_per_expert, wgs_per_expert, log_rb;
+    int tiles_per_expert, wgs_per_expert, log_rb;
     size_t smem;
 };
 
@@ -87,10 +118,9 @@ struct ConvLaunch {
     int pbuf, mpw, mph;    // LDS-DMA (+ RES with res_dma): patch buffer bytes, magic numbers of the piece decode
     int mf16, stream, producer, narrow;        // DMA: conv3x3_dma_kernel<MF16, PROD> | conv3x3_dma_stream_kernel<MF16, NARROW>
     ResPlan res;           // RES
-    int res_dma, res_pipe, rz_late;            // RES: conv3x3_resdma_kernel, conv3x3_respipe_kernel<BIAS, MODE, RZ_LATE>
+    int res_dma, res_pipe;                     // RES: conv3x3_resdma_kernel, conv3x3_respipe_kernel<BIAS, MODE>
     int wpe, tpe, tiles_x, slabs, mt;           // C16 / C1X1: workgroups and tiles per expert, (C16) tiles per row, (C1X1) slabs, MT
     int log_rb, wm, wn, lite;                   // TILE: conv_igemm_kernel<T, LOG_RB, WM, WN> | conv_igemm_lite_kernel<T, LOG_RB>
-    int nw;                // SKINNY: gemm_skinny_kernel<NW>
 };
 
 // what conv_select decided for a descriptor: up to four launches (a stride-2 data gradient: one per output parity class)
@@ -143,8 +173,7 @@ struct WgradPlan {
     int code;              // pmoe_conv2d_wgrad_plan code, or a PMOE_ERR_* (< 0): nothing runs
     WgradArgs a;
     int esz, maxv;         // TILE: conv_wgrad_kernel<T, taps, MAXV> (esz = sizeof(T))
-    int pin, wci, pairs, req;      // DMA: conv_wgrad_dma_kernel<PIN, WCI, PAIRS, REQ>
-    int ahead;             // DMA2: conv_wgrad_dma2_kernel<a.lTW, AHEAD>
+    int pin, wci, pairs, req;      // DMA: conv_wgrad_dma_kernel<PIN, WCI, PAIRS, REQ> (DMA2: conv_wgrad_dma2_kernel<a.lTW>)
     dim3 grid, block;
     size_t smem;           // dynamic LDS bytes of the launch
     int mpw, mph;          // DMA / DMA2: magic numbers of the piece decode

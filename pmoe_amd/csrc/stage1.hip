@@ -487,9 +487,7 @@ int pmoe_cat_windows(const void* const* srcs, int32_t K, int32_t c, int32_t src_
         if (dst_c % VE || dst_ld % VE) return PMOE_ERR_ARG;
         bool aligned = src_ld % VE == 0 && (size_t)CAT_ROWS * dst_c * sizeof(T) <= 48 * 1024;
         for (int k = 0; k < K; ++k) aligned = aligned && ((uintptr_t)srcs[k] & 15) == 0;
-        static int lds_on = -1;             // PMOE_CAT_LDS=0: the element-wise kernel for every call (A/B)
-        if (lds_on < 0) { const char* ev = getenv("PMOE_CAT_LDS"); lds_on = ev ? atoi(ev) : 1; }
-        if (aligned && lds_on) {
+        if (aligned) {
             hipLaunchKernelGGL((cat_windows_lds_kernel<T>), dim3((unsigned)((rows + CAT_ROWS - 1) / CAT_ROWS)), dim3(256),
                                (size_t)CAT_ROWS * dst_c * sizeof(T), (hipStream_t)stream, cs, K, c, src_ld, src_coff, (T*)dst,
                                dst_ld, dst_c, (long long)rows);

@@ -574,14 +574,8 @@ __global__ void __launch_bounds__(256) stem_tail_dz_walk_kernel(const T* __restr
     }
 }
 
-static inline int walk_enabled() {
-    const char* ev = getenv("PMOE_STEM_WALK");
-    return !ev || atoi(ev);
-}
-static inline int walk_ko() {                    // pooled columns per lane group (tools/ab_stem_tail.py: 2 vs 4)
-    const char* ev = getenv("PMOE_STEM_WALK_KO");
-    return ev && atoi(ev) == 4 ? 4 : 2;
-}
+static inline int walk_enabled() { return sw("PMOE_STEM_WALK", 1) != 0; }
+static inline int walk_ko() { return sw("PMOE_STEM_WALK_KO", 2) == 4 ? 4 : 2; }      // pooled columns per lane group (tools/ab_stem_tail.py: 2 vs 4)
 static inline int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 
 static inline bool pow2i(int v) { return v > 0 && !(v & (v - 1)); }

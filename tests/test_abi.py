@@ -307,6 +307,68 @@ def test_wgrad_selection_table_is_the_recorded_one(lib, monkeypatch):
     assert {7009, 7109, 7209, 7309, 6106, 6906, 6910, 6112, 6912, 6920, hip.ERR_UNSUPPORTED} <= codes, sorted(codes)
 
 
+CONV_PLANS = REPO / "tests" / "golden" / "conv_plans.txt"
+
+
+def test_whole_launch_plans_are_the_recorded_ones(lib, tmp_path):
+    """tools/dump_plans.cpp against tests/golden/conv_plans.txt, line by line: every non-pointer field of every ConvLaunch and
+    WgradPlan (tile geometry, grid, LDS bytes, patch buffer, magic numbers, instantiation parameters, K-split, workspace) that
+    conv_select / wgrad_select fill over a sampled sweep -- both dtypes, 3x3 and 1x1, both strides, the stride-2 data gradients,
+    the fused requests, the expert MLP layers, e4m3 operands -- at the defaults and at every switch value some test sets.
+
+    The fixture was recorded from the library of commit d0a8bf3 (the last one with a tile-geometry computation per planner, the
+    launch sequence written out per site and 34 switches), with tools/dump_plans.cpp built against that commit's kernels.h and
+    library: ``dump_plans > tests/golden/conv_plans.txt``.  It prints the tile fields from the descriptor a kernel receives and
+    none of the plan fields that went with the retired switches, so one source builds against both."""
+    import shutil
+    import subprocess
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    exe = tmp_path / "dump_plans"
+    libdir = hip.lib_path().parent
+    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-std=c++17", str(REPO / "tools" / "dump_plans.cpp"), f"-L{libdir}",
+                           "-lpmoe_hip", f"-Wl,-rpath,{libdir}", "-o", str(exe)], stderr=subprocess.DEVNULL)
+    got = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split("\n")
+    want = CONV_PLANS.read_text().split("\n")
+    for n, (g, w) in enumerate(zip(got, want)):
+        assert g == w, (n + 1, g, w)
+    assert len(got) == len(want)
+    # the sweep reaches every kernel family of both selections, both failure codes, and every switch changes some row
+    conv = [l for l in want if l.startswith("conv ")]
+    wgrad = [l for l in want if l.startswith("wgrad ")]
+    assert {int(k) for l in conv for k in re.findall(r"\| kind=(\d+)", l)} == set(range(1, 10))           # ConvKind
+    assert {int(k) for l in wgrad for k in re.findall(r"[\]}] kind=(\d+)", l)} == {1, 2, 3, 4}               # WgradKind
+    for lines in (conv, wgrad):
+        assert {hip.ERR_ARG, hip.ERR_UNSUPPORTED} <= {int(c) for l in lines for c in re.findall(r"[\]}] code=(-\d+)", l)}
+    flipped = {name for l in want for env in re.findall(r"\{([^}]*)\}", l) for name in re.findall(r"(PMOE_\w+)=", env)}
+    assert flipped == _switch_table() - {"PMOE_STEM_WALK", "PMOE_STEM_WALK_KO"}                             # (those two plan nothing)
+
+
+def _switch_table():
+    """the names in the table of DESIGN.md's section "Switches the library reads" """
+    text = (REPO / "DESIGN.md").read_text()
+    section = text.split("### Switches the library reads", 1)[1].split("\n#", 1)[0]
+    return set(re.findall(r"^\| `(PMOE_\w+)` \|", section, flags=re.M))
+
+
+def test_switch_table_is_what_the_sources_read():
+    """One reader (sw, csrc/common.h), one read rule (at the call), and a switch exists only while some test names it: the names
+    the native sources pass to sw() are exactly DESIGN.md's table, nothing else in csrc/ reads the environment, and every name
+    occurs in a file under tests/."""
+    csrc = REPO / "pmoe_amd" / "csrc"
+    sources = {f: f.read_text() for f in sorted(csrc.glob("*.hip")) + sorted(csrc.glob("*.h")) + sorted(csrc.glob("*.inc"))}
+    read = {name for text in sources.values() for name in re.findall(r'\bsw\(\s*"(\w+)"', text)}
+    assert read and read == _switch_table(), read ^ _switch_table()
+    calls = [(f.name, n + 1) for f, text in sources.items() for n, l in enumerate(text.split("\n")) if re.search(r"\bsw\(", l)]
+    named = [(f.name, n + 1) for f, text in sources.items() for n, l in enumerate(text.split("\n")) if re.search(r'\bsw\(\s*"PMOE_', l)]
+    assert [c for c in calls if c not in named] == [("common.h", dict(calls)["common.h"])]       # (the definition; no computed names)
+    getenv = [(f.name, n + 1) for f, text in sources.items() for n, l in enumerate(text.split("\n")) if "getenv" in l]
+    assert len(getenv) == 1 and getenv[0][0] == "common.h", getenv
+    tests = "".join(f.read_text() for f in sorted((REPO / "tests").rglob("*.py")) if f.name != "test_abi.py")
+    tests += (REPO / "tests" / "test_abi.py").read_text().split("def _switch_table", 1)[0]
+    unnamed = sorted(name for name in read if not re.search(name + r"\b", tests))
+    assert not unnamed, unnamed
+
+
 def test_wgrad_queries_answer_what_the_launch_does(lib):
     """Plan, size and fold go through the launch's own selection.  Three places where they once answered differently:"""
     import ctypes as C

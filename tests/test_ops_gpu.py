@@ -226,6 +226,8 @@ BASELINE_CONV_CASES = [
     ((1, 1, 12, 64, 256, 256, 3, 1), (1316, 1207, 256)),       # stem conv1 (12 -> 16 input channels): direct-form conv3x3_c16_kernel
     ((2, 3, 12, 64, 40, 40, 3, 1), (1316, None, None)),        # ... ragged: 40-wide rows = one full + one 8-pixel tile, 2 experts x 3 images
     ((1, 2, 9, 48, 33, 96, 3, 1), (1316, None, None)),         # ... 9 input / 48 output channels (zero-padded filter rows, masked stores)
+    ((1, 1, 128, 128, 64, 64, 1, 1), (2007, 2007, None)),      # conv_igemm_lite_kernel: a 1x1 layer of 4096 pixels (below the direct kernel's
+                                                               # 8192, above the skinny kernel's 3200), forward and data gradient
 ]
 
 
@@ -460,6 +462,22 @@ def test_conv_resident_pingpong_fallback(monkeypatch):
     _conv_case((2, 2, 64, 64, 128, 128, 3, 1), torch.bfloat16, (1007, 1007, 256))
     monkeypatch.setenv("PMOE_CONV_C16", "0")            # ... and the 16-channel stem convolution back on conv3x3_res_kernel<5>
     _conv_case((1, 2, 12, 64, 64, 64, 3, 1), torch.bfloat16, (1005, None, None))
+    # ... and with a bias: conv3x3_res_kernel<7, true> (the bias row behind the patch regions in LDS), ragged tiles
+    g = torch.Generator().manual_seed(11)
+    E, ipe, H, W, BF = 2, 4, 40, 24, torch.bfloat16              # (3840 pixels per expert: past the skinny kernel)
+    x = rnd((E * ipe, 64, H, W), g, BF)
+    ws = [rnd((64, 64, 3, 3), g, BF, (2.0 / (64 * 9)) ** 0.5) for _ in range(E)]
+    bs = [rnd((64,), g, torch.float32, 0.3) for _ in range(E)]
+    wf, _, _keep = pack(ws, 3, BF)
+    dev_b = [b.to(DEV) for b in bs]
+    bias = torch.empty(E, 64, device=DEV)
+    ops.pack_bias(hip.ptr_table(dev_b, DEV), bias, E, 64, 64)
+    out = torch.full((E * ipe, H, W, 64), 7.0, dtype=BF, device=DEV)
+    kw = dict(cin=64, cout=64, coutp=64, ipe=ipe, ks=3, stride=1, pad=1, bias=bias)
+    assert ops.conv2d(nhwc(x, 64, BF), wf, out, plan_only=True, **kw) == 1007
+    ops.conv2d(nhwc(x, 64, BF), wf, out, **kw)
+    ref = torch.cat([F.conv2d(x[e * ipe:(e + 1) * ipe], ws[e], bias=bs[e], padding=1) for e in range(E)])
+    close(from_nhwc(out, 64), ref, BF, "conv + bias on the ping-pong kernel")
 
 
 @pytest.mark.parametrize("case", [c for c, _ in BASELINE_CONV_CASES[:4]])
