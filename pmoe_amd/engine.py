@@ -50,7 +50,7 @@ class Var:
         self.bn_defer = False                # t feeds a BatchNorm and the ONLY consumer of dL/dt applies that BatchNorm's backward on load
         self.bn_fused = None                 # (g, coef, c1, c2) left by _bn_bwd for that consumer instead of dL/dt (round 4: _stem_in_bwd)
         self.pending_bn = None               # (coef [4,E,C], rpe): t is the PRE-activation z of a BatchNorm + ReLU that its one consumer
-                                             # applies on load (PMOE_RES_INBN) or engine_punet._materialize writes out (untaped PU-Net forward)
+                                             # applies on load (PMOE_RES_INBN) or engine_punet._materialize writes out (untaped U-Net forward)
 
     @property
     def grad(self):
@@ -62,8 +62,7 @@ class Var:
             # BatchNorm backward (_dgrad_with_bn_reduce): it assumed this activation has exactly one consumer.  A second
             # contribution would be added unmasked and would be missing from the reductions -- silently wrong dgamma / dbeta / dz
             raise RuntimeError("relu(BatchNorm(z)) whose backward reductions came out of its consumer's data gradient "
-                               "(PMOE_RES_DBN) must have exactly one consumer; a second gradient contribution arrived "
-                               "(set PMOE_BN_REDUCE_IN_DGRAD=0 for graphs that fan this activation out)")
+                               "(PMOE_RES_DBN) takes exactly one consumer; a second gradient contribution arrived")
         if self.base is not None:
             self.base.g = g
         else:
@@ -104,8 +103,7 @@ class GroupedConv:
         """this layer's forward runs on e4m3 operands (BASELINE config 5: engine.fp8 + bf16 activations).  Round 3: the
         policy selects the dense 3x3 stride-1 convolutions with whole 128-channel chunks (ResNet layer2-4: 46 % of the forward
         MACs) -- the launches the block-scaled fp8 matrix instruction serves at twice the bf16 rate; everything else stays bf16."""
-        return (self.fp8_ok and self.eng.fp8 and self.ks == 3 and self.stride == 1 and self.cin % 128 == 0
-                and self.cin >= self.eng.fp8_min_cin)
+        return self.fp8_ok and self.eng.fp8 and self.ks == 3 and self.stride == 1 and self.cin % 128 == 0
 
     def alloc(self, dtype, dev):
         E = self.eng.E
@@ -213,7 +211,17 @@ class GroupedECA:
 
 
 class ExpertGroupEngine:
-    """Executes ``experts`` (list of pmoe_amd.model.moe.BaseExpert[Alt]) as one grouped network."""
+    """Executes ``experts`` (list of pmoe_amd.model.moe.BaseExpert[Alt]) as one grouped network.  The engines of
+    pmoe_amd.engine_punet run a group of one whose member is the module they serve: a PUNetExpert, a PredictiveUnet, a UNet."""
+    # Options (DESIGN.md section 6, "Options of the Python engines"): each selects a fused path whose other side a test runs by
+    # setting the attribute on an engine instance.  Declared here, read at the call; tests/test_abi.py pins the list.
+    fuse_conv_stats = True        # train-mode bf16 BatchNorm statistics come out of the conv epilogue (else: a centred colstats pass)
+    fuse_stem_tail = True         # stem: BatchNorm + ReLU, bn1 + ReLU and the max-pool as one fused chain (_stem_tail)
+    fold_stem_input = True        # taped stem: (ECA gate -> conv1) backward from per-image filter gradients, no data-gradient conv
+    fold_bn_eval = True           # inference: eval-mode BatchNorm folded into the conv weights / epilogue
+    pooled_stem_bwd = True        # stem-tail BatchNorm reductions from the pooled tensors (train mode)
+    fold_eca_gate = True          # ECA gate folded into per-image conv weights (no gated activation in memory)
+    overlap_wgrad = False         # weight gradients on a side HIP stream; the one option with an environment name (see __init__)
 
     def __init__(self, experts, alt=False, shared_k=0):
         """``shared_k`` > 0: MixtureOfExpertsShared (moe.py:180-233) -- ``experts`` is the one module that owns the
@@ -232,34 +240,14 @@ class ExpertGroupEngine:
         self._built_for = self._ptr_key = self._packed_version = None
         self._build_gen = 0           # counts re-allocations of the packed banks: recorded pointers into the old ones are stale
         self._seed_counter = itertools.count(1)
-        self.fuse_conv_stats = True
-        self.fuse_stem_tail = True
-        self.fold_stem_input = True
         # weight gradients on a side HIP stream, overlapped with the BatchNorm backward passes and the next data gradient
         # (+2 % step throughput at the headline shape).  Off by default: co-running kernels stretch each other, which
         # makes per-kernel durations (bench.py roofline, rocprofv3 traces) meaningless; PMOE_OVERLAP_WGRAD=1 turns it on
         self.overlap_wgrad = os.environ.get("PMOE_OVERLAP_WGRAD", "0") == "1"
-        self.fold_bn_eval = True      # inference: eval-mode BatchNorm folded into the conv weights / epilogue
-        self.pooled_stem_bwd = True   # stem-tail BatchNorm reductions from the pooled tensors (train mode)
-        self.fold_eca_gate = True     # ECA gate folded into per-image conv weights (no gated activation in memory)
-        # residual-block BatchNorm backward: the reduce pass stores the ReLU-masked gradient, the apply pass reads it (7 tensor
-        # passes per block output instead of 8).  PMOE_BN_MASK_IN_REDUCE=0: A/B switch
-        self.bn_mask_in_reduce = os.environ.get("PMOE_BN_MASK_IN_REDUCE", "1") != "0"
-        # round 3: the reductions of a BatchNorm+ReLU's backward come out of the data-gradient epilogue of the convolution that
-        # consumed its output (PMOE_RES_DBN: one extra read of z there instead of a pass over dy and z).  bf16, LDS-DMA kernels
-        self.bn_reduce_in_dgrad = os.environ.get("PMOE_BN_REDUCE_IN_DGRAD", "1") != "0"
-        # stem: the BatchNorm+ReLU pass that writes a1 also leaves the ECA block's per-image channel sums (no GAP pass over a1)
-        self.fuse_bn_gap = os.environ.get("PMOE_FUSE_BN_GAP", "1") != "0"
-        # round 4: the stem's first BatchNorm backward applied on load by conv1's per-image filter gradient (no dz1 tensor)
-        self.stem_bn_fuse = os.environ.get("PMOE_STEM_BN_FUSE", "1") != "0"
-        # round 4: weight + bias gradient of the expert MLP layers in one small launch each (PMOE_MLP_WGRAD=0: the generic
-        # weight-gradient kernel + fold + column-sum chain of rounds 1-3)
-        self.mlp_wgrad_fused = os.environ.get("PMOE_MLP_WGRAD", "1") != "0"
         # BASELINE config 5: e4m3 weights + e4m3 activations on the fp8 matrix cores for the layer1-4 forward convolutions
-        # (policy: include/pmoe_hip.h, pmoe_pack_conv_weights_fp8).  fp8_min_cin: smallest input-channel count that takes it
+        # (policy: include/pmoe_hip.h, pmoe_pack_conv_weights_fp8; the layers: GroupedConv.fp8)
         self.fp8 = False
         self.fp8_in_scale = 16.0
-        self.fp8_min_cin = int(os.environ.get("PMOE_FP8_MIN_CIN", "64"))
         self.raw_alpha = False        # lone BaseExpert.forward: the gate kernel returns alpha itself instead of softmax(alpha)
         self.debug_grads = None       # dict -> backward stores the gradient entering every BatchNorm (tests/experiments/probe_layers.py)
         # dict -> forward keeps a reference to every tensor that carries a DISCRETE decision of the network: the outputs of
@@ -320,8 +308,6 @@ class ExpertGroupEngine:
         self._mk = dict(conv=conv, bn=bn, eca=eca, mlp=mlp)
         self._collect_network(ex)
         del self._mk
-        if self.conv1 is not None:
-            self.conv1.need_dgrad = self._stem_needs_dgrad()
         self.all_bns = [p[1] for p in self.params if p[0] == "gamma"]
         self.flat_params = [p for _, _, plist in self.params for p in plist]
 
@@ -336,9 +322,6 @@ class ExpertGroupEngine:
 
     def _collect_pre_backbone(self, ex):
         """hook: layers that run before the ResNet backbone (the frozen PU-Net of PUNetExpert)."""
-
-    def _stem_needs_dgrad(self):
-        return True
 
     def _collect_backbone(self, bbs):
         conv, bn, eca = self._mk["conv"], self._mk["bn"], self._mk["eca"]
@@ -384,7 +367,7 @@ class ExpertGroupEngine:
 
     # ------------------------------------------------------------------ buffers
     def _ensure_built(self, dev, dtype):
-        key = (str(dev), dtype, self.fp8, self.fp8_min_cin)
+        key = (str(dev), dtype, self.fp8)             # ([2]: pack_sinks reads it)
         if self._built_for == key:
             return
         for layer in self.all_convs:
@@ -520,7 +503,7 @@ class ExpertGroupEngine:
         f8 = layer.w_f8 is not None
         if f8 and (bias is not False or act != hip.ACT_NONE):
             raise RuntimeError(f"{layer.name}: an fp8-policy layer has only its e4m3 forward operand (bias-free, no activation)")
-        seed = (next(self._seed_counter) * 0x9E3779B1 + self.base_seed) & 0xFFFFFFFFFFFF if drop_p > 0 else 0
+        seed = self._next_seed() if drop_p > 0 else 0
         kw = dict(cin=layer.cinp, cout=layer.cout_st, coutp=layer.coutp, ipe=self.B, ks=layer.ks, stride=layer.stride,
                   pad=layer.pad, in_shared=in_shared, in_coff=x.coff, out_coff=o.coff, bias=layer.bias_packed if bias else None,
                   act=act, drop_p=drop_p, seed=seed, stats=True if want_stats else None, out_scale=layer.oscale if f8 else None,
@@ -545,6 +528,10 @@ class ExpertGroupEngine:
         if tape and self.taping and o.needs_grad:
             self.tape.append(lambda: self._conv_bwd(x, layer, o, in_shared, flop))
         return (o, stats) if want_stats else o
+
+    def _next_seed(self):
+        """the seed of the next dropout site: a function of (base_seed, site order), see _begin"""
+        return (next(self._seed_counter) * 0x9E3779B1 + self.base_seed) & 0xFFFFFFFFFFFF
 
     def _conv_out(self, x, layer, out=None, out_coff=0):
         """(Ho, Wo, o) of ``layer`` applied to x: o is a fresh activation, or the channel window of ``out`` at out_coff"""
@@ -593,10 +580,10 @@ class ExpertGroupEngine:
         plain = layer.scatter_grads is None
         want_b = layer.biases is not None and layer.route_bias
         gw = self._grad_slot("w", layer) if plain else torch.empty(E, layer.cout, layer.cin, dtype=F32, device=self.dev)
-        if (self.mlp_wgrad_fused and layer.ks == 1 and self.dtype == torch.bfloat16 and dy.shape[1] == 1 and dy.shape[2] == 1
+        if (layer.ks == 1 and self.dtype == torch.bfloat16 and dy.shape[1] == 1 and dy.shape[2] == 1
                 and x.t.shape[1] == 1 and x.t.shape[2] == 1 and layer.route_bias):
-            # round 4: a Linear layer of the expert MLPs -- weight AND bias gradient in one launch, written in the parameters'
-            # own layout (csrc/gemm_skinny.hip mlp_wgrad_kernel)
+            # a Linear layer of the expert MLPs -- weight AND bias gradient in one launch, written in the parameters' own layout
+            # (csrc/gemm_skinny.hip mlp_wgrad_kernel); f32 and layers with a bias route of their own take the generic chain below
             gb = None
             if want_b:
                 gb = self._grad_slot("b", layer) if plain else torch.empty(E, layer.cout, dtype=F32, device=self.dev)
@@ -735,7 +722,7 @@ class ExpertGroupEngine:
         else:
             y = out.window(out_coff, C_)
         ops.set_meta(name=layer.name, bytes=z.t.numel() * z.t.element_size() * (3 if res is not None else 2))
-        if want_gap and res is None and out is None and self.fuse_bn_gap:
+        if want_gap and res is None and out is None:
             nparts = self._gap_parts(h * w)
             part = torch.empty(n, nparts, C_, dtype=F32, device=self.dev)
             ops.bn_apply_gap(z.t, y.t, scale, shift, mean, part, nparts, self.B, relu)
@@ -750,8 +737,7 @@ class ExpertGroupEngine:
                          y_fp8=y.f8, in_scale=self.fp8_in_scale)
         if self.debug_acts is not None and relu:
             self.debug_acts[layer.name] = (y.t, y.coff, C_)
-        if (relu and res is None and out is None and self.taping and self.training and self.bn_reduce_in_dgrad
-                and self.dtype == torch.bfloat16 and z.needs_grad):
+        if relu and res is None and out is None and self.taping and self.training and self.dtype == torch.bfloat16 and z.needs_grad:
             y.bn_src = (z, layer, self._last_coef, rpe)
         y.needs_grad = z.needs_grad or layer.trainable or (res is not None and res.needs_grad)
         if out is not None and y.needs_grad:
@@ -796,7 +782,7 @@ class ExpertGroupEngine:
         want_res = res is not None and res.needs_grad
         # residual blocks: the reduce pass also stores the masked gradient (the residual branch needs it anyway), and the
         # apply pass then reads that instead of dy AND the saved output: one tensor pass less per block
-        gm = torch.empty_like(z.t) if (want_res and relu and ysrc is not None and self.bn_mask_in_reduce) else None
+        gm = torch.empty_like(z.t) if (want_res and relu and ysrc is not None) else None
         ops.set_meta(name=layer.name, bytes=nb * ((3 if ysrc is not None else 2) + (gm is not None)))
         ops.bn_bwd_reduce(dy, ysrc, z.t, mean, invstd, scale, shift, rpe, E, C_, relu, part, nparts, gmask=gm)
         part, nparts = self._fold_parts(part, nparts, 2 * C_, cap=2048)
@@ -986,7 +972,7 @@ class ExpertGroupEngine:
                                     layer.cinp, layer.dg_rows, layer.dg_red, self.dtype)
         Ho, Wo, o = self._conv_out(x, layer)
         stats = None
-        if self.training and self.fuse_conv_stats and self.dtype == torch.bfloat16:
+        if self._epilogue_stats:
             rows = ops.conv2d_stat_rows(N, h, w, Ho, Wo, layer.cinp, layer.cout_st, layer.coutp, 1, layer.ks, layer.stride,
                                         layer.pad, self.dtype, in_ld=x.t.shape[-1], out_ld=o.t.shape[-1])
             stats = torch.empty(rows, 2, layer.coutp, dtype=F32, device=self.dev)
@@ -1037,7 +1023,7 @@ class ExpertGroupEngine:
     def _act(self, x, act, drop_p):
         """y = dropout(act(x)) as its own pass (behind a BatchNorm1d, basics.py:34-39); backward from the saved output."""
         y = Var(torch.empty_like(x.t))
-        seed = (next(self._seed_counter) * 0x9E3779B1 + self.base_seed) & 0xFFFFFFFFFFFF if drop_p > 0 else 0
+        seed = self._next_seed() if drop_p > 0 else 0
         ops.act_fwd(x.t, y.t, act, drop_p, seed)
         y.needs_grad = x.needs_grad
         if self.taping and y.needs_grad:
@@ -1198,8 +1184,8 @@ class ExpertGroupEngine:
             z1, st = self._conv_stats(x0s, self.conv1, tape=False)
             z1.needs_grad = True
             # round 4: bn_c1's backward apply happens inside conv1's per-image filter gradient (dz1, 2.15 GB at the headline shape,
-            # is never written): possible because that launch is the only consumer of dz1 (PMOE_STEM_BN_FUSE=0: A/B switch)
-            z1.bn_defer = (self.stem_bn_fuse and self.training and self.bn_reduce_in_dgrad and self.dtype == torch.bfloat16
+            # is never written): possible because that launch is the only consumer of dz1
+            z1.bn_defer = (self.training and self.dtype == torch.bfloat16
                            and fold2 and ops.conv2d_wgrad_bn_served(z1.t.shape[0], H, W, z1.t.shape[1], z1.t.shape[2], self.conv1.cinp,
                                                                     self.conv1.cout_st, 64, 64, self.B, 3, 1, self.conv1.pad, self.dtype,
                                                                     x_ld=x0.t.shape[-1], dy_ld=z1.t.shape[-1], x_shared=True,
@@ -1325,10 +1311,14 @@ class ExpertGroupEngine:
         ops.nchw_to_nhwc(images.reshape(Bsz, cin, H, W).contiguous().float(), x0.t)
         return x0
 
+    @property
+    def _epilogue_stats(self):
+        """this pass takes BatchNorm statistics from the conv epilogue.  They are plain sums (no sample to centre on before the
+        conv has run): fine under bf16 storage noise, not for the exact-f32 parity mode, which takes the centred colstats pass"""
+        return self.training and self.fuse_conv_stats and self.dtype == torch.bfloat16
+
     def _conv_stats(self, x, layer, tape=True, in_bn=None):
-        # conv-epilogue statistics are plain sums (no sample to centre on before the conv has run): fine under
-        # bf16 storage noise, not for the exact-f32 parity mode, which takes the centred colstats pass instead
-        if self.training and self.fuse_conv_stats and self.dtype == torch.bfloat16:
+        if self._epilogue_stats:
             return self._conv(x, layer, bias=False, want_stats=True, tape=tape, in_bn=in_bn)
         return self._conv(x, layer, bias=False, tape=tape, in_bn=in_bn), None
 

@@ -1,19 +1,19 @@
-"""Engine for ``PUNetExpert`` (``PMoE/model/moe.py:268-323``): frozen PU-Net -> ResNet18-ECA backbone -> tanh head.
+"""Engines of the U-Net family, built from the same primitive launches as :class:`pmoe_amd.engine.ExpertGroupEngine` (groups of one):
 
-Built from the same primitive launches as :class:`pmoe_amd.engine.ExpertGroupEngine` (group of one):
-
-* the PU-Net (``model/punet.py:75-120``) is FORWARD ONLY -- ``freeze(self.punet)`` (moe.py:280) removes every one of
-  its parameters from training, so nothing is taped for it and the 138-channel stem needs no data gradient
-  (``eca1`` / ``conv1`` gradients come from the per-image filter-gradient fold, as in the MoE path);
-* train-mode BatchNorm inside the frozen U-Nets still uses batch statistics and updates its running buffers
-  (``model.train()`` in train_2.py:130 reaches them), exactly like the reference: the four past frames go through
-  ``unet`` one after the other, each with its own statistics;
-* ``ConvTranspose2d(k=2,s=2)`` is one 1x1 GEMM with 4*Cout rows + ``pmoe_pixel_shuffle2`` into the second half of
-  the skip-concatenation buffer; ``torch.cat`` / ``view`` of 23-class masks are ``pmoe_copy_window`` launches.
+* :class:`UNetOps` -- the U-Net primitives (``model/blocks/unet.py``): (conv -> BatchNorm -> ReLU) x 2 blocks, 2x2 max-pool, the
+  ``ConvTranspose2d(k=2,s=2)`` layers as one 1x1 GEMM with 4*Cout rows + ``pmoe_pixel_shuffle2`` into the second half of the
+  skip-concatenation buffer, BatchNorms over channel-padded rows, and the forward of one whole U-Net;
+* :class:`UNetEngine` -- the segmentation ``UNet`` on its own (stage 0);
+* :class:`RolloutEngine` -- the ``PredictiveUnet`` roll-out (``model/punet.py:75-120``): the past frames through ``unet`` one after
+  the other, each with its own train-mode statistics, then the autoregressive steps cat(masks) -> entry block -> ``pred_unet``;
+  ``torch.cat`` / ``view`` of 23-class masks are ``pmoe_copy_window`` launches;
+* :class:`PredictiveUnetEngine` -- the roll-out on its own (stage 1: ``entry_block`` and ``pred_unet`` train through time);
+* :class:`PUNetEngine` -- ``PUNetExpert`` (``PMoE/model/moe.py:268-323``): frozen PU-Net -> ResNet18-ECA backbone -> tanh head.
+  The PU-Net is FORWARD ONLY there -- ``freeze(self.punet)`` (moe.py:280) removes every one of its parameters from training, so
+  nothing is taped for it and the 138-channel stem needs no data gradient (``eca1`` / ``conv1`` gradients come from the per-image
+  filter-gradient fold, as in the MoE path); train-mode BatchNorm inside the frozen U-Nets still uses batch statistics and updates
+  its running buffers (``model.train()`` in train_2.py:130 reaches them), exactly like the reference.
 """
-import os
-import types
-
 import torch
 
 from . import hip, ops
@@ -22,7 +22,7 @@ from .engine import ExpertGroupEngine, GroupedBN, GroupedConv, Var, r16, F32
 
 class _UpConv(GroupedConv):
     """ConvTranspose2d(cin, cout, 2, 2) as a 1x1 layer with 4*cout rows (row (dy*2+dx)*cout + c)."""
-    route_bias = False        # the bias gradient is taken from the un-shuffled output gradient in PUNetEngine._up_bwd
+    route_bias = False        # the bias gradient is taken from the un-shuffled output gradient in UNetOps._up_bwd
 
     def __init__(self, eng, name, mod):
         super().__init__(eng, name, None, None, mod.in_channels, 4 * mod.out_channels, 1, 1, 0)
@@ -54,53 +54,22 @@ class _UpConv(GroupedConv):
         self._derived_version = ver
 
 
-class PUNetEngine(ExpertGroupEngine):
-    _punet_trains = False
+class UNetOps(ExpertGroupEngine):
+    """The U-Net primitives over a group of one.  ``module`` is what the engine serves; ``return_inter``: the forward also hands
+    out the bottleneck x_5 (``inter_repr``).  Nothing here knows of experts, roll-outs or heads."""
+    # Options (DESIGN.md section 6), all of the untaped forward except the first
+    fuse_bn_pool = True            # the down blocks' last BatchNorm + ReLU pass also writes MaxPool2d(2, 2) of its output
+    fuse_in_bn = True              # BatchNorm + ReLU between the two convolutions of a block applied ON LOAD by the second one
+    fuse_in_bn_1x1 = True          # ... and a block's last one by the 1x1 layer that is its one consumer (see _unet_fwd)
+    fuse_upconv_shuffle = True     # ConvTranspose2d = 1x1 GEMM whose store scatters the 2x2 blocks itself
 
-    def __init__(self, expert, return_inter=None):
-        self.return_inter = expert.return_inter if return_inter is None else return_inter
+    def __init__(self, module, return_inter):
+        self.return_inter = return_inter
+        self.up_layers, self.shadow_bns = [], []
         self._punet_built_for, self._punet_build_gen = None, 0
-        # tests/punet_parity.py (per-pass teacher forcing): ``debug_pass_out`` (a list) collects the mask tensor every U-Net
-        # pass wrote; ``debug_forced_masks`` (T + F tensors [B,classes,H,W]) REPLACES each pass's output by the given mask
-        # before the later passes read it, so that every pass runs on the checker's inputs and errors do not compound
-        self.debug_pass_out = self.debug_forced_masks = None
-        # (teacher forcing): ``debug_x0``, the predicted masks [B,F,classes,H,W], GIVEN: the frozen PU-Net is skipped -- the
-        # trainable half (138-channel stem, ResNet, heads) is then compared on identical inputs, without the chained train-mode
-        # U-Nets' sensitivity in the loop.  ``debug_keep_x0``: forward leaves the backbone's input tensor in ``debug_x0_kept``
-        self.debug_x0 = self.debug_x0_kept = None
-        self.debug_keep_x0 = False
-        super().__init__([expert], alt=False)
+        super().__init__([module])
 
     # ------------------------------------------------------------------ structure
-    def _collect_pre_backbone(self, ex):
-        pu = ex[0].punet
-        self.pu = pu
-        self.up_layers = []
-        self.shadow_bns = []
-        self.unet = self._collect_unet("punet.unet", pu.unet)
-        conv, bn, eca = self._mk["conv"], self._mk["bn"], self._mk["eca"]
-        eb = pu.entry_block
-        self.entry = dict(eca1=eca("punet.entry.eca1", [eb.layer1.eca1]),
-                          conv1=conv("punet.entry.conv1", [eb.layer1.conv1[0]]),
-                          bn1=bn("punet.entry.bn1", [eb.layer1.conv1[1]]),
-                          eca2=eca("punet.entry.eca2", [eb.layer2.eca2]),
-                          conv2=conv("punet.entry.conv2", [eb.layer2.conv2[0]]),
-                          bn2=self._padded_bn("punet.entry.bn2", eb.layer2.conv2[1]))
-        self.pred_unet = self._collect_unet("punet.pred_unet", pu.pred_unet)
-        for layer in self._punet_convs():
-            layer.need_dgrad = self._punet_trains        # stage 2 freezes the PU-Net: no data gradients at all
-        for U in (self.unet, self.pred_unet):
-            for up in U["up"]:
-                up.need_dgrad = self._punet_trains
-
-    def _punet_convs(self):
-        out = []
-        for U in (self.unet, self.pred_unet):
-            for blk in U["dwn"] + U["up_forw"]:
-                out += [blk["c1"], blk["c2"]]
-            out.append(U["out"])
-        return out + [self.entry["conv1"], self.entry["conv2"]]
-
     def _padded_bn(self, name, mod):
         """BatchNorm over C channels stored in r16(C)-wide rows (C = 3 after the entry block): the kernels index
         whole rows, so gamma/beta/running stats are mirrored in zero-padded device buffers around each forward."""
@@ -128,7 +97,9 @@ class PUNetEngine(ExpertGroupEngine):
             self._grad_slot("beta_real", layer).copy_(db[0, :creal])
         return dg, db, store
 
-    def _collect_unet(self, name, U):
+    def _collect_unet(self, name, U, need_dgrad):
+        """the layers of U-Net ``U`` in forward order.  ``need_dgrad``: its convolutions run data gradients (False: never taped, or
+        frozen and fed by images)"""
         conv, bn = self._mk["conv"], self._mk["bn"]
 
         def block(nm, seq):
@@ -138,45 +109,21 @@ class PUNetEngine(ExpertGroupEngine):
         d = dict(mod=U, dwn=[block(f"{name}.dwn_{i}", getattr(U, f"dwn_{i}")) for i in range(1, 6)], up=[], up_forw=[])
         for i in range(1, 5):
             up = _UpConv(self, f"{name}.up_{i}", getattr(U, f"up_{i}"))
+            up.need_dgrad = need_dgrad
             self.params.append(("wT", up, [up.mod.weight]))
             self.params.append(("bT", up, [up.mod.bias]))
             self.up_layers.append(up)
             d["up"].append(up)
             d["up_forw"].append(block(f"{name}.up_forw_{i}", getattr(U, f"up_forw_{i}")))
         d["out"] = conv(f"{name}.out", [U.out])
+        for blk in d["dwn"] + d["up_forw"]:
+            blk["c1"].need_dgrad = blk["c2"].need_dgrad = need_dgrad
+        d["out"].need_dgrad = need_dgrad
         return d
-
-    def _collect_backbone(self, bbs):
-        if self.return_inter:          # punet_inter: the PU-Net bottleneck vector is the image feature (moe.py:282-284)
-            self.blocks = []
-            self.conv1 = self.eca1 = None
-            return
-        super()._collect_backbone(bbs)
-        c1 = self.conv1
-        if self.pad_stem_input and c1.ks == 3 and c1.stride == 1 and c1.coutp == 64 and c1.cin > 64 and c1.cinp % 64:
-            # round 4: the 138-channel stem input (F predicted masks x 23 classes) stored in rows of 192 channels instead of 144, zero
-            # filled -- whole 64-channel chunks, so the convolution (667 GFLOP at the C4 shape) runs on the persistent LDS-DMA kernel's
-            # 64-output-channel tiles (plan 5067) instead of the generic register-staged kernel's 16-channel chunks (273 TFLOP/s)
-            c1.cinp = (c1.cin + 63) // 64 * 64
-
-    pad_stem_input = True
-
-    def _x0_width(self, channels):
-        """row width of the backbone's input tensor: the stem convolution's (possibly 64-padded) input-channel count"""
-        return self.conv1.cinp if self.conv1 is not None and self.conv1.cin == channels else r16(channels)
-
-    def _collect_heads(self, ex):
-        conv, mlp = self._mk["conv"], self._mk["mlp"]
-        e = ex[0]
-        self.speed_pred = mlp("speed_pred", [e.speed_pred])
-        # action_pred = Sequential(make_mlp(action_head), Linear(512, 2))  (moe.py:296-301)
-        self.action_feat = mlp("action_pred.0", [e.action_pred[0]])
-        self.head = conv("action_pred.1", [e.action_pred[1]])
 
     def _ensure_built(self, dev, dtype):
         # (its own key: the base class stores a longer tuple in _built_for -- compared against that one, this branch ran on EVERY
-        #  call, the fresh shadow tensors changed the pointer table, and all 79 weight packs of a PUNetExpert were redone every step:
-        #  1.2 ms of pack launches + the derived ConvTranspose2d packs per step until round 4)
+        #  call, the fresh shadow tensors changed the pointer table, and all 79 weight packs of a PUNetExpert were redone every step)
         key = (str(dev), dtype)
         if self._punet_built_for != key:
             for up in self.up_layers:
@@ -220,10 +167,12 @@ class PUNetEngine(ExpertGroupEngine):
                 m.running_mean.copy_(l.shadow["rm"][:c])
                 m.running_var.copy_(l.shadow["rv"][:c])
 
-    # ------------------------------------------------------------------ PU-Net forward
-    fuse_bn_pool = True            # round 4: the down blocks' last BatchNorm + ReLU pass also writes MaxPool2d(2, 2) of its output
-
-    fuse_in_bn = True      # round 4: BatchNorm + ReLU between the two convolutions of a block applied ON LOAD by the second one
+    # ------------------------------------------------------------------ U-Net forward
+    def _bn_on_load(self, consumer):
+        """an untaped train-mode bf16 forward, whose BatchNorm + ReLU in front of ``consumer`` may be applied on load by it: the
+        activation has that one consumer and nothing is saved for a backward pass (the statistics come from the conv epilogue)"""
+        return (self.fuse_in_bn and not self.taping and self._epilogue_stats and self.debug_acts is None
+                and consumer.w_f8 is None)
 
     def _conv3(self, x, blk, out=None, pool_to=None, defer=False):
         """blocks/unet.py:14-24: (conv -> BatchNorm -> ReLU) x 2.  Untaped train-mode forward (the frozen U-Nets inside a training
@@ -231,8 +180,8 @@ class PUNetEngine(ExpertGroupEngine):
         where the second convolution's kernel can evaluate relu(bn1(z1)) on its halo patch (PMOE_RES_INBN: the 64-channel blocks)
         the pass that would write it -- and the tensor -- do not exist."""
         c1, bn1, c2 = blk["c1"], blk["bn1"], blk["c2"]
-        if (self.fuse_in_bn and not self.taping and self.training and self.dtype == torch.bfloat16 and self.fuse_conv_stats
-                and self.debug_acts is None and c2.w_f8 is None and c1.cout_st == c2.cinp == bn1.C):
+        on_load = self._bn_on_load(c2)
+        if on_load and c1.cout_st == c2.cinp == bn1.C:
             n, h, w, _ = x.t.shape
             ho, wo = ops.conv_out_size(h, c2.ks, c2.stride, c2.pad), ops.conv_out_size(w, c2.ks, c2.stride, c2.pad)
             # asked on every pass (the answer is needed before c1 runs): the library reads its switches per launch
@@ -243,8 +192,7 @@ class PUNetEngine(ExpertGroupEngine):
                 z2, st2 = self._conv_stats(z1, c2, in_bn=self._last_coef)
                 return self._last_bn(z2, st2, blk["bn2"], out, pool_to, defer)
         a = self._conv_bn(x, c1, bn1, relu=True)
-        if (defer and self.fuse_in_bn and not self.taping and self.training and self.dtype == torch.bfloat16 and self.fuse_conv_stats
-                and self.debug_acts is None and c2.w_f8 is None):
+        if defer and on_load:
             z2, st2 = self._conv_stats(a, c2)
             return self._last_bn(z2, st2, blk["bn2"], out, pool_to, defer)
         return self._conv_bn(a, c2, blk["bn2"], relu=True, out=out, pool_to=pool_to)
@@ -360,15 +308,8 @@ class PUNetEngine(ExpertGroupEngine):
         return self._conv1x1_after_bn(h, U["out"]), (None if x5.pending_bn is not None else x5)
 
     def _skip_dropout(self, U, a, pooled):
-        """hook: nn.Dropout2d on a skip activation x_1..x_4 (unet.py:53-65) -> its scale table, or None where there is none
-        (the U-Nets inside a PU-Net are built with dropout = 0: no launch; one built with dropout > 0 is refused, not ignored)."""
-        if U["mod"].dropout.p > 0:
-            raise NotImplementedError("a U-Net inside a PU-Net runs without Dropout2d (punet.py:33-39,62-68 never configure it); "
-                                      "UNet(dropout>0) is supported on its own (UNetEngine)")
-        return None
-
-    fuse_in_bn_1x1 = os.environ.get("PMOE_PUNET_BN_1X1", "1") != "0"      # round 4 (late): see _unet_fwd (the variable: A/B runs)
-    fuse_upconv_shuffle = True     # round 4: ConvTranspose2d = 1x1 GEMM whose store scatters the 2x2 blocks itself (frozen / untaped path)
+        """hook: nn.Dropout2d on a skip activation x_1..x_4 (unet.py:53-65) -> its [N,C] scale table, or None where there is none"""
+        raise NotImplementedError
 
     def _upconv_fused(self, h, up, cat):
         """ConvTranspose2d(k2, s2) + its half of torch.cat in ONE launch: the 1x1 direct kernel writes channel (2 dy + dx) c_up + c
@@ -387,7 +328,45 @@ class PUNetEngine(ExpertGroupEngine):
         run.launch()
         return True
 
-    fold_entry_eca = True  # round 4: the entry block's two ECA gates folded into per-image weights of the convolutions they feed
+
+class RolloutEngine(UNetOps):
+    """The ``PredictiveUnet`` roll-out (``model/punet.py:75-120``) over the U-Net primitives: what PredictiveUnetEngine and
+    PUNetEngine share."""
+    fold_entry_eca = True  # the entry block's two ECA gates folded into per-image weights of the convolutions they feed
+
+    def __init__(self, module, return_inter):
+        # tests/punet_parity.py (per-pass teacher forcing): ``debug_pass_out`` (a list) collects the mask tensor every U-Net
+        # pass wrote; ``debug_forced_masks`` (T + F tensors [B,classes,H,W]) REPLACES each pass's output by the given mask
+        # before the later passes read it, so that every pass runs on the checker's inputs and errors do not compound
+        self.debug_pass_out = self.debug_forced_masks = None
+        super().__init__(module, return_inter)
+
+    def _collect_punet(self, pu, need_dgrad):
+        """``unet`` is frozen and fed by images: no data gradients.  ``need_dgrad``: the entry block and ``pred_unet`` run them"""
+        self.pu = pu
+        self.unet = self._collect_unet("punet.unet", pu.unet, need_dgrad=False)
+        conv, bn, eca = self._mk["conv"], self._mk["bn"], self._mk["eca"]
+        eb = pu.entry_block
+        self.entry = dict(eca1=eca("punet.entry.eca1", [eb.layer1.eca1]),
+                          conv1=conv("punet.entry.conv1", [eb.layer1.conv1[0]]),
+                          bn1=bn("punet.entry.bn1", [eb.layer1.conv1[1]]),
+                          eca2=eca("punet.entry.eca2", [eb.layer2.eca2]),
+                          conv2=conv("punet.entry.conv2", [eb.layer2.conv2[0]]),
+                          bn2=self._padded_bn("punet.entry.bn2", eb.layer2.conv2[1]))
+        self.entry["conv1"].need_dgrad = self.entry["conv2"].need_dgrad = need_dgrad
+        self.pred_unet = self._collect_unet("punet.pred_unet", pu.pred_unet, need_dgrad)
+
+    def _x0_width(self, channels):
+        """row width of the tensor that gathers the predicted masks"""
+        return r16(channels)
+
+    def _skip_dropout(self, U, a, pooled):
+        """hook: nn.Dropout2d on a skip activation x_1..x_4 (unet.py:53-65) -> its scale table, or None where there is none
+        (the U-Nets inside a PU-Net are built with dropout = 0: no launch; one built with dropout > 0 is refused, not ignored)."""
+        if U["mod"].dropout.p > 0:
+            raise NotImplementedError("a U-Net inside a PU-Net runs without Dropout2d (punet.py:33-39,62-68 never configure it); "
+                                      "UNet(dropout>0) is supported on its own (UNetEngine)")
+        return None
 
     def _entry_fwd(self, masks):
         eb = self.entry
@@ -423,8 +402,6 @@ class PUNetEngine(ExpertGroupEngine):
         Bsz, T = images.shape[0], images.shape[1]
         if T != pu.n_past_frames:
             raise AssertionError("Number of images should match number of past frames")      # punet.py:84-86
-        if pu.n_future_frames == 0 and not self._punet_trains:
-            raise NotImplementedError("PUNetExpert needs future_frames > 0 (moe.py:286-289 sizes its stem from it)")
         H, W = images.shape[-2:]
         cpad = r16(pu.in_features)
         masks = []
@@ -486,6 +463,47 @@ class PUNetEngine(ExpertGroupEngine):
     def _step_begin(self, f):
         """hook: start of autoregressive step ``f`` while taping (the stage-1 engine accumulates shared-weight gradients)."""
 
+
+class PUNetEngine(RolloutEngine):
+    """``PUNetExpert``: the frozen roll-out, then backbone (or the PU-Net bottleneck), measurement encoders and the tanh head."""
+
+    def __init__(self, expert, return_inter=None):
+        # (teacher forcing): ``debug_x0``, the predicted masks [B,F,classes,H,W], GIVEN: the frozen PU-Net is skipped -- the
+        # trainable half (138-channel stem, ResNet, heads) is then compared on identical inputs, without the chained train-mode
+        # U-Nets' sensitivity in the loop.  ``debug_keep_x0``: forward leaves the backbone's input tensor in ``debug_x0_kept``
+        self.debug_x0 = self.debug_x0_kept = None
+        self.debug_keep_x0 = False
+        super().__init__(expert, expert.return_inter if return_inter is None else return_inter)
+
+    # ------------------------------------------------------------------ structure
+    def _collect_pre_backbone(self, ex):
+        self._collect_punet(ex[0].punet, need_dgrad=False)        # stage 2 freezes the PU-Net: no data gradients at all
+
+    def _collect_backbone(self, bbs):
+        if self.return_inter:          # punet_inter: the PU-Net bottleneck vector is the image feature (moe.py:282-284)
+            self.blocks = []
+            self.conv1 = self.eca1 = None
+            return
+        super()._collect_backbone(bbs)
+        c1 = self.conv1
+        if c1.ks == 3 and c1.stride == 1 and c1.coutp == 64 and c1.cin > 64 and c1.cinp % 64:
+            # the 138-channel stem input (F predicted masks x 23 classes) stored in rows of 192 channels instead of 144, zero
+            # filled -- whole 64-channel chunks, so the convolution (667 GFLOP at the C4 shape) runs on the persistent LDS-DMA kernel's
+            # 64-output-channel tiles (plan 5067) instead of the generic register-staged kernel's 16-channel chunks (273 TFLOP/s)
+            c1.cinp = (c1.cin + 63) // 64 * 64
+
+    def _x0_width(self, channels):
+        """row width of the backbone's input tensor: the stem convolution's (possibly 64-padded) input-channel count"""
+        return self.conv1.cinp if self.conv1 is not None and self.conv1.cin == channels else r16(channels)
+
+    def _collect_heads(self, ex):
+        conv, mlp = self._mk["conv"], self._mk["mlp"]
+        e = ex[0]
+        self.speed_pred = mlp("speed_pred", [e.speed_pred])
+        # action_pred = Sequential(make_mlp(action_head), Linear(512, 2))  (moe.py:296-301)
+        self.action_feat = mlp("action_pred.0", [e.action_pred[0]])
+        self.head = conv("action_pred.1", [e.action_pred[1]])
+
     # ------------------------------------------------------------------ network
     def forward(self, images, speed, command, training, taping, dtype, base_seed=0):
         """-> actions [B,2] (tanh), pred_speed [B,1], state."""
@@ -506,6 +524,8 @@ class PUNetEngine(ExpertGroupEngine):
             ops.nchw_to_nhwc(mk.reshape(Bsz, -1, Hm, Wm).contiguous().float(), x0.t)
             inter = None
         else:
+            if self.pu.n_future_frames == 0:
+                raise NotImplementedError("PUNetExpert needs future_frames > 0 (moe.py:286-289 sizes its stem from it)")
             x0, inter = self._punet_fwd(images)
         if self.debug_keep_x0:
             self.debug_x0_kept = x0.t if x0 is not None else None
@@ -606,7 +626,7 @@ class PUNetEngine(ExpertGroupEngine):
             sp.set_grad(dspd)
 
 
-class PredictiveUnetEngine(PUNetEngine):
+class PredictiveUnetEngine(RolloutEngine):
     """``PredictiveUnet`` on its own (``model/punet.py:75-120``): stage-1 training (``trainer/train_1.py:129-141``,
     SURVEY.md section 8f N4) and plain segmentation-forecast inference.
 
@@ -616,20 +636,12 @@ class PredictiveUnetEngine(PUNetEngine):
     (the last one to run adds the accumulator back), so the layer backward code stays "write, don't accumulate".
     A predicted mask receives gradient from the loss and from up to ``past_frames`` later steps through the channel
     concatenation (``add_window``)."""
-    _punet_trains = True
 
     def __init__(self, punet):
-        super().__init__(types.SimpleNamespace(punet=punet), bool(punet.inter_repr))
+        super().__init__(punet, bool(punet.inter_repr))
 
     def _collect_network(self, ex):
-        self._collect_pre_backbone(ex)
-        self.conv1 = self.eca1 = self.head = None
-        self.blocks = []
-        for blk in self.unet["dwn"] + self.unet["up_forw"]:          # frozen, fed by images: no data gradients
-            blk["c1"].need_dgrad = blk["c2"].need_dgrad = False
-        self.unet["out"].need_dgrad = False
-        for up in self.unet["up"]:
-            up.need_dgrad = False
+        self._collect_punet(ex[0], need_dgrad=True)       # the entry block and pred_unet train, every step feeds the next
 
     def _step_begin(self, f):
         first = f == 0
@@ -701,7 +713,7 @@ class PredictiveUnetEngine(PUNetEngine):
         return super().backward(tape_state, *douts)
 
 
-class UNetEngine(PUNetEngine):
+class UNetEngine(UNetOps):
     """The segmentation ``UNet`` on its own (``model/blocks/unet.py:50-95``): stage-0 training (``trainer/train_0.py:130-140``)
     and plain segmentation inference.  A group of one running the same taped primitives as ``pred_unet`` in stage 1: every layer
     gets a weight gradient, every layer but the first convolution (its input is the image) a data gradient.
@@ -712,20 +724,13 @@ class UNetEngine(PUNetEngine):
     pass stays.  Nothing in backward reads the un-dropped activation: the BatchNorm backward recomputes the ReLU decision from
     its pre-activation, the max-pool backward finds the same winners in the scaled window (an all-zero window's gradient is
     multiplied by zero afterwards), and the convolutions that read the dropped tensors are the ones whose input they are."""
-    _punet_trains = True
 
     def __init__(self, unet):
         self.debug_drop_tables = []        # the [N,C] scale table of every Dropout2d site of the LAST forward (tests replay them)
-        super().__init__(types.SimpleNamespace(unet=unet), bool(unet.inter_repr))
+        super().__init__(unet, bool(unet.inter_repr))
 
     def _collect_network(self, ex):
-        self.pu = None
-        self.up_layers, self.shadow_bns = [], []
-        self.unet = self._collect_unet("unet", ex[0].unet)
-        self.conv1 = self.eca1 = self.head = None
-        self.blocks = []
-        for up in self.unet["up"]:
-            up.need_dgrad = True
+        self.unet = self._collect_unet("unet", ex[0], need_dgrad=True)
         self.unet["dwn"][0]["c1"].need_dgrad = False          # fed by the image
 
     def _skip_dropout(self, U, a, pooled):
@@ -733,8 +738,7 @@ class UNetEngine(PUNetEngine):
         if p <= 0.0 or not self.training:
             return None
         table = torch.empty(a.t.shape[0], a.c, dtype=F32, device=self.dev)
-        seed = (next(self._seed_counter) * 0x9E3779B1 + self.base_seed) & 0xFFFFFFFFFFFF
-        ops.dropout2d_table(table, p, seed)
+        ops.dropout2d_table(table, p, self._next_seed())
         ops.channel_scale(a.t, table, c=a.c, coff=a.coff)
         if pooled is not None:
             ops.channel_scale(pooled, table)

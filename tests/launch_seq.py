@@ -40,38 +40,40 @@ def field(rec, name):
     return rec[1][[f for f, _ in desc._fields_].index(name)]
 
 
-def _mixture(fp8):
+def _mixture(fp8, kind="moe", dtype=torch.bfloat16, train=True):
     from oracle import weights as W
     from pmoe_amd.loss import moe_loss
     from pmoe_amd.model.moe import get_model
     from pmoe_amd.utils import stage2_model_cfg
-    model = W.fill_state_dict(get_model(stage2_model_cfg("moe", 2, dropout=0.0)), seed=3).to("cuda")
-    model.compute_dtype, model.fp8_weights = torch.bfloat16, fp8
-    model.train()
+    model = W.fill_state_dict(get_model(stage2_model_cfg(kind, 2, dropout=0.0)), seed=3).to("cuda")
+    model.compute_dtype, model.fp8_weights = dtype, fp8
+    model.train(train)
     # fp8: layer2 has 4 * 32 * 32 = 4096 pixels per expert (the block-scaled kernel's floor), layer3 / layer4 fewer
     inp = {k: v.cuda() for k, v in W.make_inputs(4 if fp8 else 2, *((128, 128) if fp8 else (64, 64)), seed=5).items()}
 
     def run():
-        with torch.set_grad_enabled(not fp8):
+        with torch.set_grad_enabled(train and not fp8):
             dist, speeds = model(inp["images"], inp["speed"], inp["command"])
-            if not fp8:
+            if train and not fp8:
                 moe_loss(dist, speeds, inp["control"], inp["target_speed"], [0.7, 0.3]).backward()
         return [t.detach() for t in dist.hip_params] + [speeds.detach()]
     return model, run
 
 
-def _punet(tmp, batch, side):
+def _punet(tmp, batch, side, taped=False, future=2):
     from oracle import weights as W
     from pmoe_amd.utils import build_product
-    model = W.fill_state_dict(build_product(Path(tmp), dict(type="punet", n_experts=1, future_frames=2)), seed=3).to("cuda")
+    model = W.fill_state_dict(build_product(Path(tmp), dict(type="punet", n_experts=1, future_frames=future)), seed=3).to("cuda")
     model.compute_dtype = torch.bfloat16
     model.train()
     inp = {k: v.cuda() for k, v in W.make_inputs(batch, side, side, seed=5).items()}
 
     def run():
-        with torch.no_grad():
+        with torch.set_grad_enabled(taped):
             act, sp = model(inp["images"], inp["speed"], inp["command"])
-        return [act, sp]
+            if taped:                   # (the trainable half: 138-channel stem, ResNet, heads; the PU-Net is frozen)
+                (act.square().mean() + sp.square().mean()).backward()
+        return [act.detach(), sp.detach()]
     return model, run
 
 
@@ -87,6 +89,42 @@ def _unet():
         model(img).float().square().mean().backward()
         return []
     return model, run
+
+
+def _stage1(tmp):
+    """PredictiveUnet as tests/test_stage1_gpu.py builds it: ``unet`` frozen, entry block and ``pred_unet`` trained through time"""
+    from oracle import weights as W
+    from pmoe_amd.loss import AutoregressiveCriterion
+    from pmoe_amd.model.blocks import UNet
+    from pmoe_amd.model.punet import PredictiveUnet
+    Path(tmp).mkdir(parents=True, exist_ok=True)
+    torch.save({"unet": UNet().state_dict()}, Path(tmp) / "unet.pth")
+    model = PredictiveUnet(past_frames=4, future_frames=3, model_name="unet", model_path=str(Path(tmp) / "unet.pth"))
+    model = W.fill_state_dict(model, seed=3).to("cuda")
+    model.compute_dtype = torch.bfloat16
+    model.train()
+    images = W.make_inputs(2, 32, 32, seed=5)["images"].cuda()
+    target = W.make_seg_targets(2, 3, 32, 32, 23, seed=7).cuda()
+
+    def run():
+        out = model(images)
+        AutoregressiveCriterion(3, "tversky")(out, target).backward()
+        return [out.detach()]
+    return model, run
+
+
+def engine_cases(tmp):
+    """name -> () -> (model, run): the passes of tests/golden/launch_sequences_engines.json -- where the fallbacks behind the
+    engines' fused paths run (eval mode, f32, the alpha MLP of ``moe_alt``) and the taped PU-Net classes (the expert's trainable
+    half, stage-1 back-propagation through time).  Two predicted frames give the expert a 46-channel stem in 48-wide rows; six
+    give the 138 channels that are stored in rows of 192 (``_f6``).  Recorded from the revision before the engines' options were
+    reduced to the tested ones and the U-Net primitives moved under a base class of their own."""
+    return {"mixture_eval_bf16": lambda: _mixture(False, train=False),
+            "mixture_train_f32": lambda: _mixture(False, dtype=torch.float32),
+            "moealt_train_bf16": lambda: _mixture(False, kind="moe_alt"),
+            "punet_expert_train_taped": lambda: _punet(tmp, 2, 64, taped=True),
+            "punet_expert_train_taped_f6": lambda: _punet(tmp, 2, 64, taped=True, future=6),
+            "stage1_train_taped": lambda: _stage1(tmp)}
 
 
 def cases(tmp):
@@ -113,8 +151,10 @@ def record(make):
 
 if __name__ == "__main__":
     import tempfile
+    which = engine_cases if Path(sys.argv[1]).name == "launch_sequences_engines.json" else cases
     with tempfile.TemporaryDirectory() as tmp:
-        seqs = {name: record(make)[2] for name, make in cases(tmp).items()}
+        seqs = {name: record(make)[2] for name, make in which(tmp).items()}
     body = ",\n".join(json.dumps(k) + ":[\n" + ",\n".join(json.dumps(r, separators=(",", ":")) for r in v) + "\n]" for k, v in seqs.items())
     Path(sys.argv[1]).write_text("{" + body + "}\n")
-    print({k: len(v) for k, v in seqs.items()})
+    import pmoe_amd
+    print("recorded from", Path(pmoe_amd.__file__).parent, {k: len(v) for k, v in seqs.items()})

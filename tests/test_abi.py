@@ -369,6 +369,32 @@ def test_switch_table_is_what_the_sources_read():
     assert not unnamed, unnamed
 
 
+def _option_table():
+    """the attribute names in the table of DESIGN.md's section "Options of the Python engines" """
+    text = (REPO / "DESIGN.md").read_text()
+    section = text.split("### Options of the Python engines", 1)[1].split("\n#", 1)[0]
+    return set(re.findall(r"^\| `([a-z_0-9]+)` \|", section, flags=re.M))
+
+
+def test_option_table_is_what_the_engines_declare():
+    """The Python engines keep the library's rule: the boolean class attributes of the engine classes are exactly DESIGN.md's
+    option table, every one is named by a file under tests/, and the package reads three environment names."""
+    import inspect
+    from pmoe_amd import engine, engine_punet
+    classes = [c for m in (engine, engine_punet) for _, c in inspect.getmembers(m, inspect.isclass)
+               if issubclass(c, engine.ExpertGroupEngine) and c.__module__ == m.__name__]
+    assert {c.__name__ for c in classes} >= {"ExpertGroupEngine", "UNetEngine", "PredictiveUnetEngine", "PUNetEngine"}
+    declared = {k for c in classes for k, v in vars(c).items() if isinstance(v, bool)}
+    assert declared and declared == _option_table(), declared ^ _option_table()
+    tests = "".join(f.read_text() for f in sorted((REPO / "tests").rglob("*.py")) if f.name != "test_abi.py")
+    tests += (REPO / "tests" / "test_abi.py").read_text().split("def _switch_table", 1)[0]
+    unnamed = sorted(name for name in declared if not re.search(r"\b" + name + r"\b", tests))
+    assert not unnamed, unnamed
+    py = "".join(f.read_text() for f in sorted((REPO / "pmoe_amd").rglob("*.py")))
+    assert "getenv" not in py and len(re.findall(r"\benviron\b", py)) == len(re.findall(r"\benviron\.get\(\s*\"", py))      # (no computed names)
+    assert set(re.findall(r"\benviron\.get\(\s*\"(\w+)\"", py)) == {"PMOE_OVERLAP_WGRAD", "PMOE_DP_COLLECTIVE", "PMOE_HIP_LIB"}
+
+
 def test_wgrad_queries_answer_what_the_launch_does(lib):
     """Plan, size and fold go through the launch's own selection.  Three places where they once answered differently:"""
     import ctypes as C

@@ -112,3 +112,35 @@ def test_conv3_asks_on_every_pass(tmp_path, monkeypatch):
     seq2 = reduce_calls(rec.calls)
     assert not [f for f in _fused(seq2) if f[:2] == (hip.RES_INBN, 3)]
     assert sum(r[0] == "pmoe_bn_apply" for r in seq2) == applies + len(on_load)          # one BatchNorm + ReLU pass per block instead
+
+
+# ---- the passes of tests/launch_seq.py engine_cases: recorded from the revision before the engines' untested options were retired and
+# the U-Net primitives got a base class of their own (python tests/launch_seq.py tests/golden/launch_sequences_engines.json)
+ENGINES = json.loads((Path(__file__).resolve().parent / "golden" / "launch_sequences_engines.json").read_text())
+
+# entry points (or a descriptor field) that show the branch a case is there for, and ones it must not contain
+TAKES = {
+    "mixture_eval_bf16": ({"pmoe_pack_conv_weights_scaled"}, {"pmoe_bn_apply", "pmoe_colstats"}),            # folded BatchNorms
+    "mixture_train_f32": ({"pmoe_colstats", "pmoe_unpack_conv_wgrad"}, {"pmoe_mlp_wgrad"}),                   # no epilogue statistics
+    "moealt_train_bf16": ({"pmoe_copy_window", "pmoe_mlp_wgrad"}, set()),                                     # _merge_alt_head
+    "punet_expert_train_taped": ({"pmoe_eca_stem_fold", "pmoe_pixel_shuffle2"}, {"pmoe_pixel_unshuffle2"}),   # frozen PU-Net
+    "punet_expert_train_taped_f6": ({"pmoe_eca_stem_fold"}, {"pmoe_pixel_unshuffle2"}),
+    "stage1_train_taped": ({"pmoe_add_window", "pmoe_pixel_unshuffle2", "pmoe_unpack_conv_wgrad"}, set()),    # through time
+}
+
+
+@pytest.mark.parametrize("name", list(TAKES))
+def test_engine_passes_issue_the_recorded_launches(tmp_path, name):
+    """eval mode, f32, ``moe_alt``, the taped PU-Net expert and stage-1 back-propagation through time: call for call and
+    descriptor field for descriptor field what the engines issued before."""
+    from tests.launch_seq import engine_cases
+    _, _, seq, _ = record(engine_cases(tmp_path)[name])
+    want = ENGINES[name]
+    names = {r[0] for r in seq}
+    has, has_not = TAKES[name]
+    assert has <= names and not (has_not & names), (sorted(has - names), sorted(has_not & names))
+    if name.endswith("_f6"):            # the 138-channel stem input lives in rows of 192 channels
+        assert any(r[0] == "pmoe_conv2d_igemm" and field(r, "cin") == 192 and field(r, "ks") == 3 for r in seq)
+    assert len(seq) == len(want), (len(seq), len(want))
+    for i, (a, b) in enumerate(zip(seq, want)):
+        assert a == b, (name, i, a, b)
