@@ -529,9 +529,9 @@ int pmoe_channel_scale(void* x, int32_t ld, int32_t coff, const float* table, in
 typedef struct pmoe_opt_tensor {
     float* param;
     const float* grad;
-    float* exp_avg;
-    float* exp_avg_sq;
-    float* max_exp_avg_sq; /* amsgrad only */
+    float* exp_avg;        /* pmoe_mt_rmsprop*: momentum_buffer (momentum > 0 only) */
+    float* exp_avg_sq;     /* pmoe_mt_rmsprop*: square_avg */
+    float* max_exp_avg_sq; /* amsgrad only; pmoe_mt_rmsprop*: grad_avg (centered only) */
     float* swa;            /* averaged copy (pmoe_mt_swa_update only) */
     int64_t numel;
     float bc1;             /* 1 - beta1^step of THIS tensor */
@@ -574,6 +574,31 @@ int pmoe_mt_adam_packs(const pmoe_opt_tensor* table, const pmoe_opt_pack* packs,
                        const int32_t* tile_co0, const int32_t* tile_ci0, int32_t n_tiles, float lr, float beta1, float beta2,
                        float eps, float weight_decay, int32_t amsgrad, float bc1_all, float bc2_sqrt_all, const float* norm,
                        void* stream);
+/* torch.optim.RMSprop (torch/optim/rmsprop.py:_single_tensor_rmsprop, maximize=False), the trainers' second optimizer
+ * (trainer/train_2.py:62-73, conf/stage_*.yaml `rmsprop:`), over the same chunk table.  Per element, one rounding per line
+ * (fma = one fused multiply-add), clip = norm[1] or 1 where norm == NULL:
+ *   g  = clip * g
+ *   g  = fma(weight_decay, p, g)                       weight_decay != 0 only
+ *   sa = fma(sa, alpha, ((1 - alpha) * g) * g)
+ *   ga = fma(1 - alpha, g - ga, ga);  d = sqrtf(fma(-ga, ga, sa)) + eps          centered
+ *                                     d = sqrtf(sa) + eps                        otherwise
+ *   buf = fma(buf, momentum, g / d);  p = fma(-lr, buf, p)                       momentum > 0
+ *                                     p = fma(-lr, g / d, p)                     otherwise
+ * The state lives in the slots of pmoe_opt_tensor under other names: exp_avg_sq = square_avg (sa), max_exp_avg_sq = grad_avg
+ * (ga, centered only), exp_avg = momentum_buffer (buf, momentum > 0 only); a slot that the mode does not use is never
+ * dereferenced and may be NULL; `momentum > 0` is decided on the float passed here, so a caller that keeps a momentum_buffer passes a
+ * momentum that is positive in float32.  bc1 / bc2_sqrt are not read.  1 - alpha is formed in float32 (0.0099999905 for alpha = 0.99;
+ * torch forms it in double and casts, 0.0099999998): the weights of sa and ga differ from torch's float32 path by 9e-7 relative, so
+ * the result follows torch's formula but is not bit-equal to its float32 kernels.  There is no clamp that torch does not have: a centered sa - ga^2
+ * that rounds below zero gives NaN here as it does there. */
+int pmoe_mt_rmsprop(const pmoe_opt_tensor* table, const int32_t* chunk_tensor, const int32_t* chunk_index, int32_t n_chunks,
+                    float lr, float alpha, float eps, float weight_decay, float momentum, int32_t centered, const float* norm,
+                    void* stream);
+/* The same update through the tile table of pmoe_mt_adam_packs, leaving the packed operands current.  Parameters and state come
+ * out bit-identical to pmoe_mt_rmsprop. */
+int pmoe_mt_rmsprop_packs(const pmoe_opt_tensor* table, const pmoe_opt_pack* packs, const int32_t* tile_tensor,
+                          const int32_t* tile_co0, const int32_t* tile_ci0, int32_t n_tiles, float lr, float alpha, float eps,
+                          float weight_decay, float momentum, int32_t centered, const float* norm, void* stream);
 /* swa = param (n_averaged == 0) or swa + (param - swa) / (n_averaged + 1) */
 int pmoe_mt_swa_update(const pmoe_opt_tensor* table, const int32_t* chunk_tensor, const int32_t* chunk_index,
                        int32_t n_chunks, int64_t n_averaged, void* stream);

@@ -1,6 +1,7 @@
 // Fused optimizer tail of the stage-2 step (reference trainer/train_2.py:157-165,184):
 //   clip_grad_norm_(params, max_norm)  ->  global L2 norm over ~620 gradient tensors + one scale
 //   Adam(amsgrad=True).step()          ->  one multi-tensor update (optionally also writing the engine's packed operands)
+//   RMSprop(centered=True).step()      ->  the same launch with the other update rule (train_2.py:62-73 `optimizer: rmsprop`)
 //   AveragedModel.update_parameters()  ->  one multi-tensor running mean
 // The reference issues a handful of launches (and a .item() sync) PER parameter tensor; here each stage is one launch
 // over a chunk table: tensor t is cut into chunks of PMOE_OPT_CHUNK elements, workgroup i handles chunk
@@ -84,9 +85,18 @@ __global__ void __launch_bounds__(256) mt_scale_kernel(const pmoe_opt_tensor* __
 // torch.optim.Adam (single-tensor formulas of torch/optim/adam.py, maximize=False, capturable=False):
 //   g' = clip * g (+ wd * p);  m = m + (1-b1)(g' - m);  v = b2 v + (1-b2) g'^2;  vmax = max(vmax, v)
 //   p -= (lr / bc1) * m / (sqrt(vmax or v) / sqrt(bc2) + eps)
+//
+// An update rule (AdamCoef, RmspropCoef) is the coefficients of one launch plus three members: upd(g, p, a, b, x) -> the new
+// parameter, with a / b / x the values of the row's exp_avg / exp_avg_sq / max_exp_avg_sq slots, and has_a() / has_x(): whether
+// the rule keeps state in the first and the third slot (the second is always live).  A slot that is not live is never
+// dereferenced.  Everything below the rules -- the 16-byte run, the chunk walk, the tile walk and the pack stores -- is written
+// once, over the rule.
 struct AdamCoef {
     float clip, weight_decay, beta1, beta2, eps, step_size, inv_bc2s;
     int amsgrad;
+    __device__ __forceinline__ bool has_a() const { return true; }
+    __device__ __forceinline__ bool has_x() const { return amsgrad != 0; }
+    __device__ __forceinline__ float upd(float gi, float pi, float& mi, float& vi, float& mx) const;
 };
 
 // The one place the update is written: mt_adam_kernel and mt_adam_pack_kernel both call it, so that a parameter comes out with
@@ -107,6 +117,10 @@ __device__ __forceinline__ float adam_upd(const AdamCoef& c, float gi, float pi,
     return __builtin_fmaf(-c.step_size, mi / __builtin_fmaf(sqrtf(d), c.inv_bc2s, c.eps), pi);
 }
 
+__device__ __forceinline__ float AdamCoef::upd(float gi, float pi, float& mi, float& vi, float& mx) const {
+    return adam_upd(*this, gi, pi, mi, vi, mx);
+}
+
 // bias corrections: one value for all tensors (kernel argument, > 0) or the per-tensor entries of the table
 __device__ __forceinline__ AdamCoef adam_coef(const pmoe_opt_tensor& t, float lr, float beta1, float beta2, float eps,
                                               float weight_decay, int amsgrad, float bc1_all, float bc2s_all,
@@ -123,25 +137,77 @@ __device__ __forceinline__ AdamCoef adam_coef(const pmoe_opt_tensor& t, float lr
     return c;
 }
 
+// torch.optim.RMSprop (torch/optim/rmsprop.py:_single_tensor_rmsprop, maximize=False); the formula, line by line, is in the
+// header at pmoe_mt_rmsprop.  Slots: a = momentum_buffer (momentum > 0), b = square_avg, x = grad_avg (centered).
+struct RmspropCoef {
+    float clip, weight_decay, alpha, eps, lr, momentum;
+    int centered;
+    __device__ __forceinline__ bool has_a() const { return momentum > 0.f; }
+    __device__ __forceinline__ bool has_x() const { return centered != 0; }
+    __device__ __forceinline__ float upd(float gi, float pi, float& buf, float& sa, float& ga) const;
+};
+
+// The one place this update is written, like adam_upd and for the same reason: one rounding per line, no contraction.  No
+// clamp under the square root: torch has none, and a centered sa - ga^2 that rounds below zero is NaN in both.
+__device__ __forceinline__ float rmsprop_upd(const RmspropCoef& c, float gi, float pi, float& buf, float& sa, float& ga) {
+#pragma clang fp contract(off)
+    gi *= c.clip;
+    if (c.weight_decay != 0.f) gi = __builtin_fmaf(c.weight_decay, pi, gi);
+    sa = __builtin_fmaf(sa, c.alpha, ((1.f - c.alpha) * gi) * gi);
+    float d;
+    if (c.centered) {
+        ga = __builtin_fmaf(1.f - c.alpha, gi - ga, ga);
+        d = sqrtf(__builtin_fmaf(-ga, ga, sa)) + c.eps;
+    } else {
+        d = sqrtf(sa) + c.eps;
+    }
+    const float q = gi / d;
+    if (c.momentum > 0.f) {
+        buf = __builtin_fmaf(buf, c.momentum, q);
+        return __builtin_fmaf(-c.lr, buf, pi);
+    }
+    return __builtin_fmaf(-c.lr, q, pi);
+}
+
+__device__ __forceinline__ float RmspropCoef::upd(float gi, float pi, float& buf, float& sa, float& ga) const {
+    return rmsprop_upd(*this, gi, pi, buf, sa, ga);
+}
+
+__device__ __forceinline__ RmspropCoef rmsprop_coef(float lr, float alpha, float eps, float weight_decay, float momentum,
+                                                    int centered, const float* norm) {
+    RmspropCoef c;
+    c.clip = norm ? norm[1] : 1.f;
+    c.weight_decay = weight_decay;
+    c.alpha = alpha;
+    c.eps = eps;
+    c.lr = lr;
+    c.momentum = momentum;
+    c.centered = centered;
+    return c;
+}
+
 // n consecutive elements, one thread: 4 as 16-byte accesses (vec: the caller has checked the alignment), fewer one by one.
-// stage != nullptr also leaves the updated parameters there.
-__device__ __forceinline__ void adam_run(const AdamCoef& c, float* p, const float* g, float* m, float* v, float* vm, int n,
-                                         bool vec, float* stage) {
+// a / x are read and written only where the rule has them.  stage != nullptr also leaves the updated parameters there.
+template <class R>
+__device__ __forceinline__ void opt_run(const R& c, float* p, const float* g, float* a, float* b, float* x, int n, bool vec,
+                                        float* stage) {
+    const bool ha = c.has_a(), hx = c.has_x();
     if (vec) {
-        f32x4 pv = *reinterpret_cast<f32x4*>(p), mv = *reinterpret_cast<f32x4*>(m);
-        f32x4 vv = *reinterpret_cast<f32x4*>(v);
+        f32x4 pv = *reinterpret_cast<f32x4*>(p);
+        f32x4 bv = *reinterpret_cast<f32x4*>(b);
+        f32x4 av = ha ? *reinterpret_cast<f32x4*>(a) : bv;
         const f32x4 gv = *reinterpret_cast<const f32x4*>(g);
-        f32x4 xv = c.amsgrad ? *reinterpret_cast<f32x4*>(vm) : vv;
+        f32x4 xv = hx ? *reinterpret_cast<f32x4*>(x) : bv;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            float mi = mv[k], vi = vv[k], mx = xv[k];
-            pv[k] = adam_upd(c, gv[k], pv[k], mi, vi, mx);
-            mv[k] = mi; vv[k] = vi; xv[k] = mx;
+            float ai = av[k], bi = bv[k], xi = xv[k];
+            pv[k] = c.upd(gv[k], pv[k], ai, bi, xi);
+            av[k] = ai; bv[k] = bi; xv[k] = xi;
         }
         *reinterpret_cast<f32x4*>(p) = pv;
-        *reinterpret_cast<f32x4*>(m) = mv;
-        *reinterpret_cast<f32x4*>(v) = vv;
-        if (c.amsgrad) *reinterpret_cast<f32x4*>(vm) = xv;
+        if (ha) *reinterpret_cast<f32x4*>(a) = av;
+        *reinterpret_cast<f32x4*>(b) = bv;
+        if (hx) *reinterpret_cast<f32x4*>(x) = xv;
         if (stage) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) stage[k] = pv[k];
@@ -149,14 +215,39 @@ __device__ __forceinline__ void adam_run(const AdamCoef& c, float* p, const floa
         return;
     }
     for (int i = 0; i < n; ++i) {
-        float mi = m[i], vi = v[i], mx = c.amsgrad ? vm[i] : 0.f;
-        const float pn = adam_upd(c, g[i], p[i], mi, vi, mx);
+        float ai = ha ? a[i] : 0.f, bi = b[i], xi = hx ? x[i] : 0.f;
+        const float pn = c.upd(g[i], p[i], ai, bi, xi);
         p[i] = pn;
-        m[i] = mi;
-        v[i] = vi;
-        if (c.amsgrad) vm[i] = mx;
+        if (ha) a[i] = ai;
+        b[i] = bi;
+        if (hx) x[i] = xi;
         if (stage) stage[i] = pn;
     }
+}
+
+// chunk `chunk` of tensor t: 16-byte accesses where param, grad and the live state pointers are all 16-byte aligned, with a
+// scalar tail after them; scalar throughout when they are not
+template <class R>
+__device__ __forceinline__ void opt_chunk(const R& c, const pmoe_opt_tensor& t, int chunk) {
+    const long long base = (long long)chunk * CHUNK;
+    long long n = t.numel - base;
+    if (n > CHUNK) n = CHUNK;
+    float* p = t.param + base;
+    const float* g = t.grad + base;
+    float* a = c.has_a() ? t.exp_avg + base : nullptr;
+    float* b = t.exp_avg_sq + base;
+    float* x = c.has_x() ? t.max_exp_avg_sq + base : nullptr;
+    const bool aligned = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(a) |
+                           reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(x)) & 15) == 0;
+    long long done = 0;
+    if (aligned) {
+        const long long nv = n >> 2;
+        for (long long i = threadIdx.x; i < nv; i += 256)
+            opt_run(c, p + 4 * i, g + 4 * i, a ? a + 4 * i : nullptr, b + 4 * i, x ? x + 4 * i : nullptr, 4, true, nullptr);
+        done = nv << 2;
+    }
+    for (long long i = done + threadIdx.x; i < n; i += 256)
+        opt_run(c, p + i, g + i, a ? a + i : nullptr, b + i, x ? x + i : nullptr, 1, false, nullptr);
 }
 
 __global__ void __launch_bounds__(256) mt_adam_kernel(const pmoe_opt_tensor* __restrict__ tab,
@@ -165,31 +256,22 @@ __global__ void __launch_bounds__(256) mt_adam_kernel(const pmoe_opt_tensor* __r
                                                      float beta2, float eps, float weight_decay, int amsgrad,
                                                      float bc1_all, float bc2s_all, const float* __restrict__ norm) {
     const pmoe_opt_tensor t = tab[chunk_tensor[blockIdx.x]];
-    const long long base = (long long)chunk_index[blockIdx.x] * CHUNK;
-    long long n = t.numel - base;
-    if (n > CHUNK) n = CHUNK;
-    const AdamCoef c = adam_coef(t, lr, beta1, beta2, eps, weight_decay, amsgrad, bc1_all, bc2s_all, norm);
-    float* p = t.param + base;
-    const float* g = t.grad + base;
-    float* m = t.exp_avg + base;
-    float* v = t.exp_avg_sq + base;
-    float* vm = amsgrad ? t.max_exp_avg_sq + base : nullptr;
-    const bool aligned = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
-                           reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(vm)) & 15) == 0;
-    long long done = 0;
-    if (aligned) {
-        const long long nv = n >> 2;
-        for (long long i = threadIdx.x; i < nv; i += 256)
-            adam_run(c, p + 4 * i, g + 4 * i, m + 4 * i, v + 4 * i, vm ? vm + 4 * i : nullptr, 4, true, nullptr);
-        done = nv << 2;
-    }
-    for (long long i = done + threadIdx.x; i < n; i += 256)
-        adam_run(c, p + i, g + i, m + i, v + i, vm ? vm + i : nullptr, 1, false, nullptr);
+    opt_chunk(adam_coef(t, lr, beta1, beta2, eps, weight_decay, amsgrad, bc1_all, bc2s_all, norm), t,
+              chunk_index[blockIdx.x]);
 }
 
-// ---- the same update, leaving the engine's packed operands current (include/pmoe_hip.h: pmoe_mt_adam_packs) -----------------
+__global__ void __launch_bounds__(256) mt_rmsprop_kernel(const pmoe_opt_tensor* __restrict__ tab,
+                                                        const int32_t* __restrict__ chunk_tensor,
+                                                        const int32_t* __restrict__ chunk_index, float lr, float alpha,
+                                                        float eps, float weight_decay, float momentum, int centered,
+                                                        const float* __restrict__ norm) {
+    const pmoe_opt_tensor t = tab[chunk_tensor[blockIdx.x]];
+    opt_chunk(rmsprop_coef(lr, alpha, eps, weight_decay, momentum, centered, norm), t, chunk_index[blockIdx.x]);
+}
+
+// ---- the same updates, leaving the engine's packed operands current (include/pmoe_hip.h: pmoe_mt_adam_packs) ---------------
 // A workgroup owns one (co block) x (ci block) x (all taps) tile of one tensor.  In the parameter W[co][ci][tp] a tile row is one
-// contiguous run of cols * taps floats, so the update streams it exactly like mt_adam_kernel (16-byte accesses from the first
+// contiguous run of cols * taps floats, so the update streams it exactly like the chunk walk (16-byte accesses from the first
 // 16-byte boundary of each row on) and leaves the new values in LDS; the two operands are then written from LDS in THEIR
 // order: fwd [co][tp][ci] with ci across the lanes (runs of cols elements), dgrd [ci][taps-1-tp][co] with co across the lanes
 // (runs of rows elements) -- tiles of >= 16 x 16 channels make both runs >= 32 bytes in bf16.  A flat chunk of the parameter
@@ -222,28 +304,20 @@ __device__ __forceinline__ void pack_store_tile(const pmoe_opt_pack& k, const fl
     }
 }
 
-__global__ void __launch_bounds__(256) mt_adam_pack_kernel(const pmoe_opt_tensor* __restrict__ tab,
-                                                          const pmoe_opt_pack* __restrict__ packs,
-                                                          const int32_t* __restrict__ tile_tensor,
-                                                          const int32_t* __restrict__ tile_co0,
-                                                          const int32_t* __restrict__ tile_ci0, float lr, float beta1,
-                                                          float beta2, float eps, float weight_decay, int amsgrad,
-                                                          float bc1_all, float bc2s_all, const float* __restrict__ norm) {
-    __shared__ float stage[PMOE_OPT_PACK_STAGE];
-    const int ti = tile_tensor[blockIdx.x];
-    const pmoe_opt_tensor t = tab[ti];
-    const pmoe_opt_pack k = packs[ti];
-    const int co0 = tile_co0[blockIdx.x], ci0 = tile_ci0[blockIdx.x];
+// the tile (co0, ci0) of tensor t with sink k: update through `stage` (PMOE_OPT_PACK_STAGE floats of LDS), then the pack stores
+template <class R>
+__device__ __forceinline__ void opt_pack_tile(const R& c, const pmoe_opt_tensor& t, const pmoe_opt_pack& k, int co0, int ci0,
+                                              float* stage) {
     if (co0 < 0 || ci0 < 0 || co0 >= k.cout || ci0 >= k.cin || k.taps < 1 || k.tco < 1 || k.tci < 1) return;
     const unsigned rows = (unsigned)min(k.tco, k.cout - co0), cols = (unsigned)min(k.tci, k.cin - ci0);
     const unsigned len = cols * (unsigned)k.taps;              // one tile row: contiguous in the parameter
     const unsigned rs = len | 1u;
     if (rows * rs > (unsigned)PMOE_OPT_PACK_STAGE || (long long)k.cout * k.cin * k.taps != t.numel) return;
-    const AdamCoef c = adam_coef(t, lr, beta1, beta2, eps, weight_decay, amsgrad, bc1_all, bc2s_all, norm);
-    float* vm = amsgrad ? t.max_exp_avg_sq : nullptr;
+    float* a = c.has_a() ? t.exp_avg : nullptr;
+    float* x = c.has_x() ? t.max_exp_avg_sq : nullptr;
     const bool aligned = ((reinterpret_cast<uintptr_t>(t.param) | reinterpret_cast<uintptr_t>(t.grad) |
-                           reinterpret_cast<uintptr_t>(t.exp_avg) | reinterpret_cast<uintptr_t>(t.exp_avg_sq) |
-                           reinterpret_cast<uintptr_t>(vm)) & 15) == 0;
+                           reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(t.exp_avg_sq) |
+                           reinterpret_cast<uintptr_t>(x)) & 15) == 0;
     const unsigned row_stride = (unsigned)k.cin * (unsigned)k.taps;
     const unsigned s0 = ((unsigned)co0 * (unsigned)k.cin + (unsigned)ci0) * (unsigned)k.taps;
     // work units of a row: unit 0 = the elements before the row's first 16-byte boundary, units 1.. = one 16-byte group each,
@@ -267,14 +341,41 @@ __global__ void __launch_bounds__(256) mt_adam_pack_kernel(const pmoe_opt_tensor
             continue;
         }
         const unsigned o = s + lo;
-        adam_run(c, t.param + o, t.grad + o, t.exp_avg + o, t.exp_avg_sq + o, vm ? vm + o : nullptr, (int)n, vec,
-                 stage + r * rs + lo);
+        opt_run(c, t.param + o, t.grad + o, a ? a + o : nullptr, t.exp_avg_sq + o, x ? x + o : nullptr, (int)n, vec,
+                stage + r * rs + lo);
     }
     __syncthreads();
     if (k.dtype == PMOE_DT_BF16)
         pack_store_tile<bf16>(k, stage, rs, (unsigned)co0, (unsigned)ci0, rows, cols);
     else if (k.dtype == PMOE_DT_F32)
         pack_store_tile<float>(k, stage, rs, (unsigned)co0, (unsigned)ci0, rows, cols);
+}
+
+__global__ void __launch_bounds__(256) mt_adam_pack_kernel(const pmoe_opt_tensor* __restrict__ tab,
+                                                          const pmoe_opt_pack* __restrict__ packs,
+                                                          const int32_t* __restrict__ tile_tensor,
+                                                          const int32_t* __restrict__ tile_co0,
+                                                          const int32_t* __restrict__ tile_ci0, float lr, float beta1,
+                                                          float beta2, float eps, float weight_decay, int amsgrad,
+                                                          float bc1_all, float bc2s_all, const float* __restrict__ norm) {
+    __shared__ float stage[PMOE_OPT_PACK_STAGE];
+    const int ti = tile_tensor[blockIdx.x];
+    const pmoe_opt_tensor t = tab[ti];
+    opt_pack_tile(adam_coef(t, lr, beta1, beta2, eps, weight_decay, amsgrad, bc1_all, bc2s_all, norm), t, packs[ti],
+                  tile_co0[blockIdx.x], tile_ci0[blockIdx.x], stage);
+}
+
+__global__ void __launch_bounds__(256) mt_rmsprop_pack_kernel(const pmoe_opt_tensor* __restrict__ tab,
+                                                             const pmoe_opt_pack* __restrict__ packs,
+                                                             const int32_t* __restrict__ tile_tensor,
+                                                             const int32_t* __restrict__ tile_co0,
+                                                             const int32_t* __restrict__ tile_ci0, float lr, float alpha,
+                                                             float eps, float weight_decay, float momentum, int centered,
+                                                             const float* __restrict__ norm) {
+    __shared__ float stage[PMOE_OPT_PACK_STAGE];
+    const int ti = tile_tensor[blockIdx.x];
+    opt_pack_tile(rmsprop_coef(lr, alpha, eps, weight_decay, momentum, centered, norm), tab[ti], packs[ti],
+                  tile_co0[blockIdx.x], tile_ci0[blockIdx.x], stage);
 }
 
 // AveragedModel.update_parameters (torch/optim/swa_utils.py): first call copies, later p_avg += (p - p_avg) / (n + 1)
@@ -323,6 +424,24 @@ int pmoe_mt_adam_packs(const pmoe_opt_tensor* table, const pmoe_opt_pack* packs,
     if (n_tiles < 1 || !table || !packs || !tile_tensor || !tile_co0 || !tile_ci0) return PMOE_ERR_ARG;
     hipLaunchKernelGGL(mt_adam_pack_kernel, dim3(n_tiles), dim3(256), 0, (hipStream_t)stream, table, packs, tile_tensor,
                        tile_co0, tile_ci0, lr, beta1, beta2, eps, weight_decay, amsgrad, bc1_all, bc2_sqrt_all, norm);
+    return (int)hipGetLastError();
+}
+
+int pmoe_mt_rmsprop(const pmoe_opt_tensor* table, const int32_t* chunk_tensor, const int32_t* chunk_index, int32_t n_chunks,
+                    float lr, float alpha, float eps, float weight_decay, float momentum, int32_t centered, const float* norm,
+                    void* stream) {
+    if (n_chunks < 1 || !table || !chunk_tensor || !chunk_index) return PMOE_ERR_ARG;
+    hipLaunchKernelGGL(mt_rmsprop_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, table, chunk_tensor, chunk_index,
+                       lr, alpha, eps, weight_decay, momentum, centered, norm);
+    return (int)hipGetLastError();
+}
+
+int pmoe_mt_rmsprop_packs(const pmoe_opt_tensor* table, const pmoe_opt_pack* packs, const int32_t* tile_tensor,
+                          const int32_t* tile_co0, const int32_t* tile_ci0, int32_t n_tiles, float lr, float alpha, float eps,
+                          float weight_decay, float momentum, int32_t centered, const float* norm, void* stream) {
+    if (n_tiles < 1 || !table || !packs || !tile_tensor || !tile_co0 || !tile_ci0) return PMOE_ERR_ARG;
+    hipLaunchKernelGGL(mt_rmsprop_pack_kernel, dim3(n_tiles), dim3(256), 0, (hipStream_t)stream, table, packs, tile_tensor,
+                       tile_co0, tile_ci0, lr, alpha, eps, weight_decay, momentum, centered, norm);
     return (int)hipGetLastError();
 }
 

@@ -149,6 +149,8 @@ SIGNATURES = {
     "pmoe_mt_grad_norm": [_P, _P, _P, _I, _F, _P, _P, _I, _P],
     "pmoe_mt_adam": [_P, _P, _P, _I, _F, _F, _F, _F, _F, _I, _F, _F, _P, _P],
     "pmoe_mt_adam_packs": [_P, _P, _P, _P, _P, _I, _F, _F, _F, _F, _F, _I, _F, _F, _P, _P],
+    "pmoe_mt_rmsprop": [_P, _P, _P, _I, _F, _F, _F, _F, _F, _I, _P, _P],
+    "pmoe_mt_rmsprop_packs": [_P, _P, _P, _P, _P, _I, _F, _F, _F, _F, _F, _I, _P, _P],
     "pmoe_mt_swa_update": [_P, _P, _P, _I, _L, _P],
 }
 _RESTYPES = {"pmoe_error_string": C.c_char_p, "pmoe_conv2d_wgrad_ws_floats": C.c_int64}

@@ -3,6 +3,7 @@ reference trainer (``trainer/train_2.py:157-165,184``; hyper-parameters ``conf/s
 
     torch.nn.utils.clip_grad_norm_(model.parameters(), 1.0)   ->  pmoe_amd.optim.clip_grad_norm_
     torch.optim.Adam(params, lr, betas, eps, wd, amsgrad=True) ->  pmoe_amd.optim.FusedAdam   (same constructor)
+    torch.optim.RMSprop(params, **cfg.rmsprop)                 ->  pmoe_amd.optim.FusedRMSprop (same constructor)
     torch.optim.swa_utils.AveragedModel(model)                 ->  pmoe_amd.optim.FusedAveragedModel
 
 Each call is one or two HIP launches over a chunk table (``csrc/optim.hip``) instead of several launches -- and, in
@@ -12,7 +13,8 @@ consumes the clip coefficient straight from device memory, so clip + step is: 2 
 
 ``FusedAdam(..., packs=model)`` (opt-in): the update of a parameter that the model's engine keeps packed also writes the
 packed operands (``mt_adam_pack_kernel``), and the next forward does not pack again (DESIGN.md "Packs kept current by the
-optimizer").
+optimizer").  ``FusedRMSprop`` -- the trainers' other optimizer (train_2.py:62-73) -- takes the same ``clip`` and ``packs``;
+``get_optimizer(name, params, cfg)`` is the trainers' dispatch between the two.
 """
 import ctypes as C
 
@@ -189,7 +191,7 @@ def clip_grad_norm_(parameters, max_norm, norm_type=2.0, scale=True):
     return total
 
 
-def _pack_engines(packs):
+def _pack_engines(packs, who="FusedAdam"):
     """``packs`` -> the engine hosts (pmoe_amd.model.host.EngineHost) among the given modules and their submodules; an object
     that has ``pack_sinks`` itself (an engine) is taken as it is"""
     from .model.host import EngineHost
@@ -200,30 +202,41 @@ def _pack_engines(packs):
         elif isinstance(m, torch.nn.Module):
             hosts = [h for h in m.modules() if isinstance(h, EngineHost)]
             if not hosts:
-                raise ValueError(f"FusedAdam(packs=...): {type(m).__name__} hosts no engine")
+                raise ValueError(f"{who}(packs=...): {type(m).__name__} hosts no engine")
             out.extend(hosts)
         else:
-            raise TypeError("FusedAdam(packs=...): a module that hosts an engine, or a list of them")
+            raise TypeError(f"{who}(packs=...): a module that hosts an engine, or a list of them")
     return out
 
 
-class FusedAdam(torch.optim.Optimizer):
-    """``torch.optim.Adam`` semantics (same arguments, same per-parameter ``state`` keys ``step`` / ``exp_avg`` /
-    ``exp_avg_sq`` / ``max_exp_avg_sq``, so ``state_dict()`` checkpoints interchange with the reference's optimizer,
-    train_2.py:300-310), updated by one multi-tensor HIP launch per parameter group.
+class _FusedOptimizer(torch.optim.Optimizer):
+    """What the fused optimizers share -- everything but the update rule: state creation, the step loop (one launch per
+    parameter group, or two where an engine's packs take part), the table of a launch with its cache key, the ``packs=`` rule
+    and the version / ``packs_written`` tail.  A subclass names its two entry points and says which table column holds which
+    state tensor (``_slots``), which arguments the launch takes (``_hyper``) and what else a table row carries (``_fill``)."""
 
-    ``packs``: a module that runs on an engine (or a list of them).  The parameters that the engine keeps packed -- conv /
-    linear weights and biases -- are then updated by a second launch per group that also stores the new values into the engine's
-    packed operands, and the engine is told that its packs hold the new parameter versions: the next forward packs nothing.
-    An engine takes part in a step only if its packs were current when the step began, the optimizer holds every parameter
-    the engine packs, and the engine is not on its fp8 policy; otherwise its parameters take the ordinary launch and the
-    engine packs as usual.  ``packs=None``: exactly the launches of before.  ``state_dict()`` does not change."""
+    _NAME = None           # in error texts
+    _TAG = None            # of the table cache keys
+    _ENTRY = None          # (entry point over a chunk table, entry point over a tile table)
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False, packs=None):
-        if lr < 0 or eps < 0 or not (0 <= betas[0] < 1) or not (0 <= betas[1] < 1) or weight_decay < 0:
-            raise ValueError("FusedAdam: invalid hyper-parameter")
-        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=amsgrad))
-        self._pack_hosts = _pack_engines(packs) if packs is not None else []
+    def __init__(self, params, defaults, packs):
+        super().__init__(params, defaults)
+        self._pack_hosts = _pack_engines(packs, self._NAME) if packs is not None else []
+
+    def _slots(self, group):
+        """-> ((table column, state key), ...): the state tensors of a parameter of ``group``, in torch's order of creation"""
+        raise NotImplementedError
+
+    def _fill(self, rows, group, steps):
+        """per-tensor values of a freshly built table other than pointers and sizes"""
+
+    def _key_steps(self, steps):
+        """what of the step counts a cached table depends on"""
+        return ()
+
+    def _hyper(self, group, steps):
+        """-> the arguments of the launch between the table and the clip state"""
+        raise NotImplementedError
 
     def _open_packs(self):
         """-> (sink of every parameter whose update goes through the pack launch, key of the banks they point into, the engines
@@ -259,29 +272,28 @@ class FusedAdam(torch.optim.Optimizer):
                 loss = closure()
         clip_state = getattr(clip, "clip_state", None) if clip is not None else None
         if clip is not None and clip_state is None:
-            raise ValueError("FusedAdam.step(clip=...): pass the tensor returned by pmoe_amd.optim.clip_grad_norm_")
+            raise ValueError(f"{self._NAME}.step(clip=...): pass the tensor returned by pmoe_amd.optim.clip_grad_norm_")
         sinks, bank_key, claims = self._open_packs() if self._pack_hosts else ({}, (), [])
         for group in self.param_groups:
             ps = [p for p in group["params"] if p.grad is not None]
             if not ps:
                 continue
-            ams = bool(group["amsgrad"])
-            keys = ("exp_avg", "exp_avg_sq") + (("max_exp_avg_sq",) if ams else ())
+            slots = self._slots(group)
             for p in ps:
                 if p.grad.is_sparse:
-                    raise RuntimeError("FusedAdam does not support sparse gradients")
+                    raise RuntimeError(f"{self._NAME} does not support sparse gradients")
                 st = self.state[p]
                 if not st:
                     st["step"] = torch.tensor(0.0, dtype=F32)      # torch keeps `step` as a CPU f32 scalar tensor
-                    for k in keys:
+                    for _, k in slots:
                         st[k] = torch.zeros_like(p, memory_format=torch.preserve_format)
                 st["step"] += 1
             if sinks:
                 packed = [p for p in ps if id(p) in sinks]
-                self._launch(group, [p for p in ps if id(p) not in sinks], keys, clip_state)
-                self._launch(group, packed, keys, clip_state, [sinks[id(p)] for p in packed], bank_key)
+                self._launch(group, [p for p in ps if id(p) not in sinks], slots, clip_state)
+                self._launch(group, packed, slots, clip_state, [sinks[id(p)] for p in packed], bank_key)
             else:
-                self._launch(group, ps, keys, clip_state)
+                self._launch(group, ps, slots, clip_state)
             # the kernel wrote through raw pointers: tell autograd (and the engine's packed-weight cache, which keys
             # on the version counters) that these tensors changed in place
             torch.autograd.graph.increment_version(ps)
@@ -289,49 +301,137 @@ class FusedAdam(torch.optim.Optimizer):
             eng.packs_written(before)
         return loss
 
-    def _launch(self, group, ps, keys, clip_state, sinks=None, bank_key=()):
-        """one launch over ``ps``: pmoe_mt_adam, or with ``sinks`` (one per tensor) pmoe_mt_adam_packs"""
+    def _launch(self, group, ps, slots, clip_state, sinks=None, bank_key=()):
+        """one launch over ``ps``: the chunk-table entry point, or with ``sinks`` (one per tensor) the tile-table one"""
         if not ps:
             return
-        b1, b2 = group["betas"]
         steps = [float(self.state[p]["step"]) for p in ps]
         cols = {"param": tuple(_f32_cuda(p, "parameter") for p in ps),
                 "grad": tuple(_f32_cuda(p.grad, "gradient") for p in ps)}
-        for k in keys:
-            cols[k] = tuple(_f32_cuda(self.state[p][k], k) for p in ps)
-        uniform = min(steps) == max(steps)
+        for col, k in slots:
+            cols[col] = tuple(_f32_cuda(self.state[p][k], k) for p in ps)
 
         def build():
             rows = _rows(len(ps))
             for k, v in cols.items():
                 rows[k] = v
             rows["numel"] = [p.numel() for p in ps]
-            rows["bc1"] = [1.0 - b1 ** k for k in steps]
-            rows["bc2_sqrt"] = [(1.0 - b2 ** k) ** 0.5 for k in steps]
+            self._fill(rows, group, steps)
             if sinks is None:
                 return rows
             packs = np.zeros(len(ps), dtype=_PACK_ROW)
             for i, k in enumerate(_PACK_FIELDS):
                 packs[k] = [s[i] for s in sinks]
             if max(int(p.numel()) for p in ps) >= 2 ** 31:
-                raise RuntimeError("FusedAdam(packs=...): a packed parameter has 2^31 or more elements")
+                raise RuntimeError(f"{self._NAME}(packs=...): a packed parameter has 2^31 or more elements")
             return rows, packs
         # a pack table also holds pointers into the engine's banks: its key carries them, the layout they are written in and the
         # engines' build counters -- banks built again (another compute dtype or device) never meet a table of the old ones
-        key = (("a",) if sinks is None else ("ap", bank_key, tuple(sinks))) + tuple(v for c in cols.values() for v in c) + (
-            () if uniform else tuple(steps))
+        # and every key names the columns its pointers went into: two modes of one optimizer can fill equally many columns (RMSprop
+        # with momentum only and centered only), and a table of the one must never serve the other
+        key = ((self._TAG,) if sinks is None else (self._TAG + "p", bank_key, tuple(sinks))) + (tuple(cols),) + tuple(
+            v for c in cols.values() for v in c) + self._key_steps(steps)
         tab = _Table.get(key, ps[0].device, build, [p.numel() for p in ps])
+        tail = (C.c_void_p(clip_state.data_ptr()) if clip_state is not None else None, stream_ptr())
+        plain, tiled = self._ENTRY
+        if sinks is None:
+            check(getattr(load(), plain)(*tab.args(), *self._hyper(group, steps), *tail), plain)
+        else:
+            check(getattr(load(), tiled)(*tab.pack_args(), *self._hyper(group, steps), *tail), tiled)
+
+
+class FusedAdam(_FusedOptimizer):
+    """``torch.optim.Adam`` semantics (same arguments, same per-parameter ``state`` keys ``step`` / ``exp_avg`` /
+    ``exp_avg_sq`` / ``max_exp_avg_sq``, so ``state_dict()`` checkpoints interchange with the reference's optimizer,
+    train_2.py:300-310), updated by one multi-tensor HIP launch per parameter group.
+
+    ``packs``: a module that runs on an engine (or a list of them).  The parameters that the engine keeps packed -- conv /
+    linear weights and biases -- are then updated by a second launch per group that also stores the new values into the engine's
+    packed operands, and the engine is told that its packs hold the new parameter versions: the next forward packs nothing.
+    An engine takes part in a step only if its packs were current when the step began, the optimizer holds every parameter
+    the engine packs, and the engine is not on its fp8 policy; otherwise its parameters take the ordinary launch and the
+    engine packs as usual.  ``packs=None``: exactly the launches of before.  ``state_dict()`` does not change."""
+
+    _NAME, _TAG, _ENTRY = "FusedAdam", "a", ("pmoe_mt_adam", "pmoe_mt_adam_packs")
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False, packs=None):
+        if lr < 0 or eps < 0 or not (0 <= betas[0] < 1) or not (0 <= betas[1] < 1) or weight_decay < 0:
+            raise ValueError("FusedAdam: invalid hyper-parameter")
+        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=amsgrad), packs)
+
+    def _slots(self, group):
+        return (("exp_avg", "exp_avg"), ("exp_avg_sq", "exp_avg_sq")) + (
+            (("max_exp_avg_sq", "max_exp_avg_sq"),) if group["amsgrad"] else ())
+
+    def _fill(self, rows, group, steps):
+        b1, b2 = group["betas"]
+        rows["bc1"] = [1.0 - b1 ** k for k in steps]
+        rows["bc2_sqrt"] = [(1.0 - b2 ** k) ** 0.5 for k in steps]
+
+    def _key_steps(self, steps):
+        return () if min(steps) == max(steps) else tuple(steps)
+
+    def _hyper(self, group, steps):
         # all tensors at the same step (the normal case): bias corrections travel as kernel arguments and the cached
         # table is reused; otherwise the per-tensor values of a freshly built table are used (argument < 0)
+        b1, b2 = group["betas"]
+        uniform = min(steps) == max(steps)
         bc1 = 1.0 - b1 ** steps[0] if uniform else -1.0
         bc2s = (1.0 - b2 ** steps[0]) ** 0.5 if uniform else -1.0
-        hyper = (float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]),
-                 int(bool(group["amsgrad"])), float(bc1), float(bc2s),
-                 C.c_void_p(clip_state.data_ptr()) if clip_state is not None else None, stream_ptr())
-        if sinks is None:
-            check(load().pmoe_mt_adam(*tab.args(), *hyper), "pmoe_mt_adam")
-        else:
-            check(load().pmoe_mt_adam_packs(*tab.pack_args(), *hyper), "pmoe_mt_adam_packs")
+        return (float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]),
+                int(bool(group["amsgrad"])), float(bc1), float(bc2s))
+
+
+class FusedRMSprop(_FusedOptimizer):
+    """``torch.optim.RMSprop`` semantics -- the trainers' ``optimizer: rmsprop`` (train_2.py:62-73; ``conf/stage_*.yaml``
+    ``rmsprop:`` = lr, momentum 0, alpha 0.99, eps 1e-8, centered, weight_decay 0): torch's arguments, defaults and
+    ``ValueError``s, and torch's per-parameter ``state`` (``step``, ``square_avg``, ``momentum_buffer`` where momentum > 0,
+    ``grad_avg`` where centered), so ``state_dict()`` checkpoints interchange with ``torch.optim.RMSprop``.  One multi-tensor
+    HIP launch per parameter group (``csrc/optim.hip``: ``rmsprop_upd``; the formula is in ``include/pmoe_hip.h`` at
+    ``pmoe_mt_rmsprop``).  Like torch there is no clamp under the square root: a centered ``square_avg - grad_avg^2`` that
+    rounds below zero gives NaN in both.  ``step(clip=...)`` and ``packs=`` are FusedAdam's."""
+
+    _NAME, _TAG, _ENTRY = "FusedRMSprop", "r", ("pmoe_mt_rmsprop", "pmoe_mt_rmsprop_packs")
+
+    def __init__(self, params, lr=1e-2, alpha=0.99, eps=1e-8, weight_decay=0, momentum=0, centered=False, packs=None):
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if not 0.0 <= momentum:
+            raise ValueError(f"Invalid momentum value: {momentum}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if not 0.0 <= alpha:
+            raise ValueError(f"Invalid alpha value: {alpha}")
+        super().__init__(params, dict(lr=lr, momentum=momentum, alpha=alpha, eps=eps, centered=centered,
+                                      weight_decay=weight_decay), packs)
+
+    def _slots(self, group):
+        # the rows of the table are pmoe_opt_tensor's: square_avg travels in exp_avg_sq, momentum_buffer in exp_avg and
+        # grad_avg in max_exp_avg_sq; a slot the mode does not use stays NULL and the kernel never looks at it
+        return ((("exp_avg_sq", "square_avg"),) + ((("exp_avg", "momentum_buffer"),) if group["momentum"] > 0 else ())
+                + ((("max_exp_avg_sq", "grad_avg"),) if group["centered"] else ()))
+
+    def _hyper(self, group, steps):
+        # the kernel takes `momentum > 0` in float32 as "there is a momentum_buffer", _slots takes it from the double like torch: a
+        # positive momentum below float32's normal range travels as the smallest normal one (buf * momentum rounds away either way)
+        momentum = float(group["momentum"])
+        if momentum > 0:
+            momentum = max(momentum, float(np.finfo(np.float32).tiny))
+        return (float(group["lr"]), float(group["alpha"]), float(group["eps"]), float(group["weight_decay"]),
+                momentum, int(bool(group["centered"])))
+
+
+def get_optimizer(name, params, cfg, packs=None):
+    """The trainers' dispatch on ``train_params.optimizer`` (train_2.py:62-73, train_1.py:64, train_0.py:61) onto the fused
+    optimizers: ``cfg.adam`` / ``cfg.rmsprop`` are the keyword blocks of the stage's configuration."""
+    name = str(name)
+    if name.lower() == "adam":
+        return FusedAdam(params, **cfg.adam, packs=packs)
+    if name.lower() == "rmsprop":
+        return FusedRMSprop(params, **cfg.rmsprop, packs=packs)
+    raise ValueError(f"Unknown optimizer {name}")
 
 
 class FusedAveragedModel(torch.optim.swa_utils.AveragedModel):
