@@ -235,11 +235,8 @@ static int launch_point(const uint8_t* src, OUT* dst, const pmoe_aug_plan* plan,
                         int32_t phase, void* stream) {
     if (!aug_args_ok(src, dst, plan, n_img, h, w) || (phase != 0 && phase != 1)) return PMOE_ERR_ARG;
     const long long work = ((long long)h * w + 3) / 4;      // one thread per 4 pixels
-    long long gx = (work + 255) / 256;
-    gx = gx < 1 ? 1 : (gx > 1024 ? 1024 : gx);
-    hipLaunchKernelGGL(augment_point_kernel<OUT>, dim3((unsigned)gx, (unsigned)n_img), dim3(256), 0, (hipStream_t)stream, src, dst,
-                       plan, h, w, phase);
-    return (int)hipGetLastError();
+    return launch<augment_point_kernel<OUT>, 0>(dim3(grid_for(work, 1024), (unsigned)n_img), dim3(256), 0, (hipStream_t)stream, src,
+                                                dst, plan, h, w, phase);
 }
 
 extern "C" {
@@ -258,17 +255,15 @@ int pmoe_augment_point_to_f32(const uint8_t* src, float* dst_nchw, const pmoe_au
 int pmoe_augment_blur_h(const uint8_t* src, uint8_t* dst, const pmoe_aug_plan* plan, int32_t n_img, int32_t h, int32_t w,
                         void* stream) {
     if (!aug_args_ok(src, dst, plan, n_img, h, w) || src == dst || (h + BH_ROWS - 1) / BH_ROWS > 65535) return PMOE_ERR_ARG;
-    hipLaunchKernelGGL(augment_blur_h_kernel, dim3((w + BH_COLS - 1) / BH_COLS, (h + BH_ROWS - 1) / BH_ROWS, n_img), dim3(256), 0,
-                       (hipStream_t)stream, src, dst, plan, h, w);
-    return (int)hipGetLastError();
+    return launch<augment_blur_h_kernel, 0>(dim3((w + BH_COLS - 1) / BH_COLS, (h + BH_ROWS - 1) / BH_ROWS, n_img), dim3(256), 0,
+                                            (hipStream_t)stream, src, dst, plan, h, w);
 }
 
 int pmoe_augment_blur_v(const uint8_t* src, uint8_t* dst, const pmoe_aug_plan* plan, int32_t n_img, int32_t h, int32_t w,
                         void* stream) {
     if (!aug_args_ok(src, dst, plan, n_img, h, w) || src == dst || (h + BV_ROWS - 1) / BV_ROWS > 65535) return PMOE_ERR_ARG;
-    hipLaunchKernelGGL(augment_blur_v_kernel, dim3((w + BV_COLS - 1) / BV_COLS, (h + BV_ROWS - 1) / BV_ROWS, n_img), dim3(256), 0,
-                       (hipStream_t)stream, src, dst, plan, h, w);
-    return (int)hipGetLastError();
+    return launch<augment_blur_v_kernel, 0>(dim3((w + BV_COLS - 1) / BV_COLS, (h + BV_ROWS - 1) / BV_ROWS, n_img), dim3(256), 0,
+                                            (hipStream_t)stream, src, dst, plan, h, w);
 }
 
 }  // extern "C"

@@ -129,10 +129,11 @@ template <auto KERNEL> static inline hipError_t ensure_dyn_lds(int bytes) {
     return hipSuccess;
 }
 
+// return the first non-zero code: expr is a hipError_t or the code of a launch<> (an entry point that makes several launches)
 #define HIP_RET(expr)                       \
     do {                                    \
-        hipError_t _e = (expr);             \
-        if (_e != hipSuccess) return (int)_e; \
+        const int _e = (int)(expr);         \
+        if (_e != 0) return _e;             \
     } while (0)
 
 // One kernel launch: the opt-in of KERNEL to OPT_IN bytes of dynamic LDS (0: it uses none), the launch, its error code.
@@ -141,6 +142,40 @@ static inline int launch(dim3 grid, dim3 block, size_t smem, hipStream_t st, con
     if constexpr (OPT_IN > 0) HIP_RET((ensure_dyn_lds<KERNEL>(OPT_IN)));
     hipLaunchKernelGGL(KERNEL, grid, block, smem, st, args...);
     return (int)hipGetLastError();
+}
+
+// ---- the host side of every entry point outside the conv planners: the dtype dispatch, the grid rule and the argument checks that
+// go with launch<> above.
+
+// run the statements with T = the element type `dtype` names; any other dtype is refused
+#define DISPATCH_DT(dtype, ...)                                          \
+    do {                                                                 \
+        if ((dtype) == PMOE_DT_BF16) { using T = bf16; __VA_ARGS__; }     \
+        else if ((dtype) == PMOE_DT_F32) { using T = float; __VA_ARGS__; } \
+        else return PMOE_ERR_ARG;                                        \
+    } while (0)
+
+// workgroups of 256 threads over n items of a grid-stride kernel: at least one, at most `cap`
+static inline int grid_for(long long n, int cap) {
+    const long long g = (n + 255) / 256;
+    return (int)(g < 1 ? 1 : g > cap ? cap : g);
+}
+
+static inline bool pow2(int v) { return v > 0 && !(v & (v - 1)); }
+
+// C channels are a power-of-two number, at most 256, of 16-byte vectors of T: a thread of a 256-wide workgroup keeps ONE of them
+template <typename T> static inline bool one_vec_per_thread(int C) {
+    return !(C % VecOf<T>::N) && pow2(C / VecOf<T>::N) && C / VecOf<T>::N <= 256;
+}
+
+// the channel window [coff, coff + C) of rows `ld` wide: row width and offset in whole 16-byte vectors of T, no overhang
+template <typename T> static inline bool window_ok(int C, int ld, int coff) {
+    return !(ld % VecOf<T>::N) && !(coff % VecOf<T>::N) && coff + C <= ld;
+}
+
+// the padded shapes of a weight pack (and of its data-gradient twin, where there is one) hold the filter's real ones
+static inline bool pack_shape_ok(int cout, int cin, int coutp, int cinp, const void* dgrd, int cinp2, int coutp2) {
+    return coutp >= cout && cinp >= cin && (!dgrd || (cinp2 >= cin && coutp2 >= cout));
 }
 
 // The one reader of the library's PMOE_* switches (the table: DESIGN.md, "Switches the library reads"): the integer value of

@@ -1074,18 +1074,14 @@ static int wgrad_finish(const WgradPlan& p, hipStream_t st, bool force = false) 
         if (blocks > 4096) blocks = 4096;
         dim3 grid((unsigned)blocks, p.E);
         if (p.taps == 9)
-            hipLaunchKernelGGL(wgrad_fold_unpack_kernel<9>, grid, dim3(256), 0, st, src, a.grads, p.nsplit, total, a.cout_real,
-                               a.cin_real, a.CoutP, a.CinP);
-        else
-            hipLaunchKernelGGL(wgrad_fold_unpack_kernel<1>, grid, dim3(256), 0, st, src, a.grads, p.nsplit, total, a.cout_real,
-                               a.cin_real, a.CoutP, a.CinP);
-        return (int)hipGetLastError();
+            return launch<wgrad_fold_unpack_kernel<9>, 0>(grid, dim3(256), 0, st, src, a.grads, p.nsplit, total, a.cout_real,
+                                                          a.cin_real, a.CoutP, a.CinP);
+        return launch<wgrad_fold_unpack_kernel<1>, 0>(grid, dim3(256), 0, st, src, a.grads, p.nsplit, total, a.cout_real,
+                                                      a.cin_real, a.CoutP, a.CinP);
     }
-    if (p.nsplit > 1) {
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, st, a.part, a.dw, p.nsplit,
-                           total / 4);
-        return (int)hipGetLastError();
-    }
+    if (p.nsplit > 1)
+        return launch<wgrad_reduce_kernel, 0>(dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, st, a.part, a.dw, p.nsplit,
+                                              total / 4);
     return 0;
 }
 

@@ -5,15 +5,6 @@
 // atomics).  Each C-ABI wrapper cites the reference call site in include/pmoe_hip.h.
 #include "common.h"
 
-#define DISPATCH_DT(dtype, CALL)                      \
-    do {                                              \
-        if ((dtype) == PMOE_DT_BF16) { using T = bf16; CALL; } \
-        else if ((dtype) == PMOE_DT_F32) { using T = float; CALL; } \
-        else return PMOE_ERR_ARG;                     \
-    } while (0)
-
-static inline bool pow2(int v) { return v > 0 && !(v & (v - 1)); }
-
 // ------------------------------------------------------------------------------------------------
 // Column statistics.  MODE 0: sum x, sum x^2.  MODE 1 (BN backward): g = dy*(relu? y>0), sums of g
 // and g*xhat.  block = 256 threads = (256/CV row lanes) x (CV channel vectors).
@@ -97,18 +88,15 @@ template <typename T>
 static int colstats_launch(const void* x, const void* dy, const void* y, const float* mean, const float* invstd,
                            const float* scale, const float* shift, long long rpe, int E, int C, int ld, int coff, int relu, float* part, int nparts, int mode,
                            float* shiftc, hipStream_t st, void* gmask = nullptr) {
-    constexpr int VE = 16 / (int)sizeof(T);
-    if (C % VE || !pow2(C / VE) || C / VE > 256 || nparts < 1 || rpe < 1 || E < 1) return PMOE_ERR_ARG;
+    if (!one_vec_per_thread<T>(C) || nparts < 1 || rpe < 1 || E < 1) return PMOE_ERR_ARG;
     if (ld <= 0) { ld = C; coff = 0; }                                       // dense, as pmoe_bn_apply reads y_ld
-    if (ld % VE || coff < 0 || coff % VE || coff + C > ld) return PMOE_ERR_ARG;   // 16-byte loads from a window inside the row
+    if (coff < 0 || !window_ok<T>(C, ld, coff)) return PMOE_ERR_ARG;         // 16-byte loads from a window inside the row
     dim3 grid(nparts, E), block(256);
     if (mode == 0)
-        hipLaunchKernelGGL((colstats_kernel<T, 0>), grid, block, 0, st, (const T*)x, nullptr, nullptr, nullptr, nullptr,
-                           nullptr, nullptr, rpe, C, ld, coff, 0, part, nparts, shiftc, nullptr);
-    else
-        hipLaunchKernelGGL((colstats_kernel<T, 1>), grid, block, 0, st, (const T*)x, (const T*)dy, (const T*)y, mean,
-                           invstd, scale, shift, rpe, C, ld, coff, relu, part, nparts, nullptr, (T*)gmask);
-    return (int)hipGetLastError();
+        return launch<colstats_kernel<T, 0>, 0>(grid, block, 0, st, (const T*)x, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                                nullptr, rpe, C, ld, coff, 0, part, nparts, shiftc, nullptr);
+    return launch<colstats_kernel<T, 1>, 0>(grid, block, 0, st, (const T*)x, (const T*)dy, (const T*)y, mean, invstd, scale,
+                                            shift, rpe, C, ld, coff, relu, part, nparts, nullptr, (T*)gmask);
 }
 
 __global__ void __launch_bounds__(256) reduce_partials_kernel(const float* __restrict__ in, float* __restrict__ out,
@@ -774,13 +762,6 @@ __global__ void __launch_bounds__(256) act_bwd_kernel(const T* __restrict__ dy, 
     }
 }
 
-static inline int grid_for(long long nvec, int cap = 4096) {
-    long long g = (nvec + 255) / 256;
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return (int)g;
-}
-
 extern "C" {
 
 int pmoe_colstats(const void* x, int64_t rows_per_expert, int32_t E, int32_t C, int32_t ld, int32_t coff, float* part,
@@ -800,9 +781,7 @@ int pmoe_bn_bwd_reduce(const void* dy, const void* y, const void* x, const float
 int pmoe_reduce_partials(const float* part_in, float* part_out, int32_t E, int32_t nin, int32_t nout, int32_t width,
                          void* stream) {
     if (nin < 1 || nout < 1 || width < 1) return PMOE_ERR_ARG;
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3(nout, E), dim3(256), 0, (hipStream_t)stream, part_in, part_out, nin,
-                       nout, width);
-    return (int)hipGetLastError();
+    return launch<reduce_partials_kernel, 0>(dim3(nout, E), dim3(256), 0, (hipStream_t)stream, part_in, part_out, nin, nout, width);
 }
 
 int pmoe_bn_finalize(const float* part, int32_t nparts, int64_t count, const void* const* gamma_ptrs,
@@ -810,36 +789,30 @@ int pmoe_bn_finalize(const float* part, int32_t nparts, int64_t count, const voi
                      float eps, int32_t training, float* scale, float* shift, float* mean, float* invstd, int32_t E,
                      int32_t C, const float* shiftc, void* stream) {
     if (!training && (!rmean_ptrs || !rvar_ptrs)) return PMOE_ERR_ARG;
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + FIN_CH - 1) / FIN_CH, E), dim3(FIN_CH * FIN_LANES), 0, (hipStream_t)stream, part, nparts,
-                       (long long)count, (const float* const*)gamma_ptrs, (const float* const*)beta_ptrs,
-                       (float* const*)rmean_ptrs, (float* const*)rvar_ptrs, momentum, eps, training, scale, shift, mean,
-                       invstd, C, shiftc);
-    return (int)hipGetLastError();
+    return launch<bn_finalize_kernel, 0>(dim3((C + FIN_CH - 1) / FIN_CH, E), dim3(FIN_CH * FIN_LANES), 0, (hipStream_t)stream,
+                                         part, nparts, (long long)count, (const float* const*)gamma_ptrs,
+                                         (const float* const*)beta_ptrs, (float* const*)rmean_ptrs, (float* const*)rvar_ptrs,
+                                         momentum, eps, training, scale, shift, mean, invstd, C, shiftc);
 }
 
 int pmoe_bn_bwd_finalize(const float* part, int32_t nparts, int64_t count, float* dgamma, float* dbeta, float* c1,
                          float* c2, int32_t E, int32_t C, void* stream) {
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + FIN_CH - 1) / FIN_CH, E), dim3(FIN_CH * FIN_LANES), 0, (hipStream_t)stream, part, nparts,
-                       (long long)count, dgamma, dbeta, c1, c2, C);
-    return (int)hipGetLastError();
+    return launch<bn_bwd_finalize_kernel, 0>(dim3((C + FIN_CH - 1) / FIN_CH, E), dim3(FIN_CH * FIN_LANES), 0, (hipStream_t)stream,
+                                             part, nparts, (long long)count, dgamma, dbeta, c1, c2, C);
 }
 
 int pmoe_bn_apply(const void* x, const void* res, void* y, const float* scale, const float* shift, const float* mean,
                   int64_t rows_per_expert, int32_t E, int32_t C, int32_t relu, int32_t y_ld, int32_t y_coff, int32_t dtype,
                   void* y_fp8, float in_scale, void* stream) {
     DISPATCH_DT(dtype, {
-        constexpr int VE = 16 / (int)sizeof(T);
-        if (C % VE || !pow2(C / VE) || C / VE > 256) return PMOE_ERR_ARG;   // kernels keep one channel vector per thread
+        if (!one_vec_per_thread<T>(C)) return PMOE_ERR_ARG;
         if (y_ld <= 0) { y_ld = C; y_coff = 0; }
         if (y_fp8 && (dtype != PMOE_DT_BF16 || y_ld != C)) return PMOE_ERR_ARG;
-        if (y_ld % VE || y_coff % VE || y_coff + C > y_ld) return PMOE_ERR_ARG;
-        int log_cv = 0;
-        while ((1 << log_cv) < C / VE) ++log_cv;
-        const long long nvec = rows_per_expert * (C / VE);
-        hipLaunchKernelGGL((bn_apply_kernel<T>), dim3(grid_for(nvec, 2048), E), dim3(256), 0, (hipStream_t)stream,
-                           (const T*)x, (const T*)res, (T*)y, scale, shift, mean, (long long)rows_per_expert, C, relu,
-                           y_ld, y_coff, log_cv, (unsigned char*)y_fp8, in_scale);
-        return (int)hipGetLastError();
+        if (!window_ok<T>(C, y_ld, y_coff)) return PMOE_ERR_ARG;
+        const int CV = C / VecOf<T>::N;
+        return launch<bn_apply_kernel<T>, 0>(dim3(grid_for(rows_per_expert * CV, 2048), E), dim3(256), 0, (hipStream_t)stream,
+                                             (const T*)x, (const T*)res, (T*)y, scale, shift, mean, (long long)rows_per_expert, C,
+                                             relu, y_ld, y_coff, ilog2_exact(CV), (unsigned char*)y_fp8, in_scale);
     });
 }
 
@@ -848,14 +821,12 @@ int pmoe_bn_apply_pool2(const void* x, void* y, void* pooled, const float* scale
                         int32_t dtype, void* stream) {
     if (!x || !y || !pooled || ipe < 1 || E < 1 || H < 2 || W < 2 || (H & 1) || (W & 1)) return PMOE_ERR_ARG;
     DISPATCH_DT(dtype, {
-        constexpr int VE = 16 / (int)sizeof(T);
-        if (C % VE || !pow2(C / VE) || C / VE > 256) return PMOE_ERR_ARG;
+        if (!one_vec_per_thread<T>(C)) return PMOE_ERR_ARG;
         if (y_ld <= 0) { y_ld = C; y_coff = 0; }
-        if (y_ld % VE || y_coff % VE || y_coff + C > y_ld) return PMOE_ERR_ARG;
-        const long long nq = (long long)ipe * (H / 2) * (W / 2) * (C / VE);
-        hipLaunchKernelGGL((bn_apply_pool2_kernel<T>), dim3(grid_for(nq, 2048), E), dim3(256), 0, (hipStream_t)stream, (const T*)x,
-                           (T*)y, (T*)pooled, scale, shift, mean, ipe, H, W, C, relu, y_ld, y_coff);
-        return (int)hipGetLastError();
+        if (!window_ok<T>(C, y_ld, y_coff)) return PMOE_ERR_ARG;
+        const long long nq = (long long)ipe * (H / 2) * (W / 2) * (C / VecOf<T>::N);
+        return launch<bn_apply_pool2_kernel<T>, 0>(dim3(grid_for(nq, 2048), E), dim3(256), 0, (hipStream_t)stream, (const T*)x,
+                                                   (T*)y, (T*)pooled, scale, shift, mean, ipe, H, W, C, relu, y_ld, y_coff);
     });
 }
 
@@ -863,39 +834,35 @@ int pmoe_bn_bwd_apply(const void* dy, const void* y, const void* x, const float*
                       const float* scale, const float* shift, const float* c1, const float* c2, void* dx, void* gmask_out,
                       int64_t rows_per_expert, int32_t E, int32_t C, int32_t relu, int32_t dtype, void* stream) {
     DISPATCH_DT(dtype, {
-        constexpr int VE = 16 / (int)sizeof(T);
-        if (C % VE || !pow2(C / VE) || C / VE > 256) return PMOE_ERR_ARG;   // kernels keep one channel vector per thread
-        const long long nvec = rows_per_expert * (C / VE);
+        if (!one_vec_per_thread<T>(C)) return PMOE_ERR_ARG;
+        const long long nvec = rows_per_expert * (C / VecOf<T>::N);
         // every thread first loads 6 per-channel constant vectors: keep ~1024 workgroups in total (4 per CU) so that this
         // prologue is amortised over many rows (8192 workgroups cost a flat 170 us on the small layer3/4 tensors)
         int cap = 1024 / (E > 0 ? E : 1);
         cap = cap < 64 ? 64 : cap;
-        hipLaunchKernelGGL((bn_bwd_apply_kernel<T>), dim3(grid_for(nvec, cap), E), dim3(256), 0, (hipStream_t)stream,
-                           (const T*)dy, (const T*)y, (const T*)x, mean, invstd, scale, shift, c1, c2, (T*)dx, (T*)gmask_out,
-                           (long long)rows_per_expert, C, relu);
-        return (int)hipGetLastError();
+        return launch<bn_bwd_apply_kernel<T>, 0>(dim3(grid_for(nvec, cap), E), dim3(256), 0, (hipStream_t)stream, (const T*)dy,
+                                                 (const T*)y, (const T*)x, mean, invstd, scale, shift, c1, c2, (T*)dx,
+                                                 (T*)gmask_out, (long long)rows_per_expert, C, relu);
     });
 }
 
 int pmoe_act_fwd(const void* x, void* y, int64_t n, int32_t act, float drop_p, uint64_t seed, int32_t dtype, void* stream) {
     if (!x || !y || n <= 0 || act < PMOE_ACT_NONE || act > PMOE_ACT_SIGMOID || drop_p < 0.f || drop_p >= 1.f) return PMOE_ERR_ARG;
     DISPATCH_DT(dtype, {
-        constexpr int VE = 16 / (int)sizeof(T);
+        constexpr int VE = VecOf<T>::N;
         if (n % VE) return PMOE_ERR_ARG;
-        hipLaunchKernelGGL((act_fwd_kernel<T>), dim3(grid_for(n / VE)), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)y,
-                           (long long)(n / VE), act, drop_p, (unsigned long long)seed);
-        return (int)hipGetLastError();
+        return launch<act_fwd_kernel<T>, 0>(dim3(grid_for(n / VE, 4096)), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)y,
+                                            (long long)(n / VE), act, drop_p, (unsigned long long)seed);
     });
 }
 
 int pmoe_act_bwd(const void* dy, const void* y, void* dx, int64_t n, int32_t act, float drop_p, int32_t dtype, void* stream) {
     if (!dy || !y || !dx || n <= 0 || act < PMOE_ACT_NONE || act > PMOE_ACT_SIGMOID || drop_p < 0.f || drop_p >= 1.f) return PMOE_ERR_ARG;
     DISPATCH_DT(dtype, {
-        constexpr int VE = 16 / (int)sizeof(T);
+        constexpr int VE = VecOf<T>::N;
         if (n % VE) return PMOE_ERR_ARG;
-        hipLaunchKernelGGL((act_bwd_kernel<T>), dim3(grid_for(n / VE)), dim3(256), 0, (hipStream_t)stream, (const T*)dy,
-                           (const T*)y, (T*)dx, (long long)(n / VE), act, drop_p);
-        return (int)hipGetLastError();
+        return launch<act_bwd_kernel<T>, 0>(dim3(grid_for(n / VE, 4096)), dim3(256), 0, (hipStream_t)stream, (const T*)dy,
+                                            (const T*)y, (T*)dx, (long long)(n / VE), act, drop_p);
     });
 }
 
@@ -903,12 +870,10 @@ int pmoe_maxpool3s2_fwd(const void* x, void* y, uint8_t* argmax, int32_t N, int3
                         int32_t dtype, void* stream) {
     const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
     DISPATCH_DT(dtype, {
-        constexpr int VE = 16 / (int)sizeof(T);
+        constexpr int VE = VecOf<T>::N;
         if (C % VE) return PMOE_ERR_ARG;
-        const long long nvec = (long long)N * Ho * Wo * (C / VE);
-        hipLaunchKernelGGL((maxpool_fwd_kernel<T>), dim3(grid_for(nvec, 8192)), dim3(256), 0, (hipStream_t)stream,
-                           (const T*)x, (T*)y, argmax, N, H, W, C, Ho, Wo);
-        return (int)hipGetLastError();
+        return launch<maxpool_fwd_kernel<T>, 0>(dim3(grid_for((long long)N * Ho * Wo * (C / VE), 8192)), dim3(256), 0,
+                                                (hipStream_t)stream, (const T*)x, (T*)y, argmax, N, H, W, C, Ho, Wo);
     });
 }
 
@@ -916,23 +881,20 @@ int pmoe_maxpool3s2_bwd(const void* dy, const uint8_t* argmax, void* dx, int32_t
                         int32_t dtype, void* stream) {
     const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
     DISPATCH_DT(dtype, {
-        constexpr int VE = 16 / (int)sizeof(T);
+        constexpr int VE = VecOf<T>::N;
         if (C % VE) return PMOE_ERR_ARG;
-        const long long nvec = (long long)N * H * W * (C / VE);
-        hipLaunchKernelGGL((maxpool_bwd_kernel<T>), dim3(grid_for(nvec, 8192)), dim3(256), 0, (hipStream_t)stream,
-                           (const T*)dy, argmax, (T*)dx, N, H, W, C, Ho, Wo);
-        return (int)hipGetLastError();
+        return launch<maxpool_bwd_kernel<T>, 0>(dim3(grid_for((long long)N * H * W * (C / VE), 8192)), dim3(256), 0,
+                                                (hipStream_t)stream, (const T*)dy, argmax, (T*)dx, N, H, W, C, Ho, Wo);
     });
 }
 
 int pmoe_gap_partial(const void* a, const void* b, float* part, int32_t N, int64_t HW, int32_t C, int32_t nparts,
                      int32_t b_shared_ipe, int32_t dtype, void* stream) {
     DISPATCH_DT(dtype, {
-        constexpr int VE = 16 / (int)sizeof(T);
+        constexpr int VE = VecOf<T>::N;
         if (C % VE || C / VE > 256 || nparts < 1) return PMOE_ERR_ARG;
-        hipLaunchKernelGGL((gap_partial_kernel<T>), dim3(nparts, N), dim3(256), 0, (hipStream_t)stream, (const T*)a,
-                           (const T*)b, part, (long long)HW, C, nparts, b_shared_ipe);
-        return (int)hipGetLastError();
+        return launch<gap_partial_kernel<T>, 0>(dim3(nparts, N), dim3(256), 0, (hipStream_t)stream, (const T*)a, (const T*)b, part,
+                                                (long long)HW, C, nparts, b_shared_ipe);
     });
 }
 
@@ -940,50 +902,44 @@ int pmoe_bn_apply_gap(const void* x, void* y, const float* scale, const float* s
                       int32_t nparts, int32_t N, int32_t ipe, int64_t HW, int32_t C, int32_t relu, int32_t dtype, void* stream) {
     if (!x || !y || !scale || !shift || !mean || !gap_part || nparts < 1 || N < 1 || ipe < 1 || N % ipe || HW < 1) return PMOE_ERR_ARG;
     DISPATCH_DT(dtype, {
-        constexpr int VE = 16 / (int)sizeof(T);
+        constexpr int VE = VecOf<T>::N;
         if (C % VE || C / VE > 256) return PMOE_ERR_ARG;
-        hipLaunchKernelGGL((bn_apply_gap_kernel<T>), dim3(nparts, N), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)y, scale,
-                           shift, mean, gap_part, (long long)HW, C, nparts, ipe, relu);
-        return (int)hipGetLastError();
+        return launch<bn_apply_gap_kernel<T>, 0>(dim3(nparts, N), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)y, scale,
+                                                 shift, mean, gap_part, (long long)HW, C, nparts, ipe, relu);
     });
 }
 
 int pmoe_gap_finish(const float* part, void* out, int32_t N, int32_t C, int32_t nparts, int64_t HW, int32_t out_ld,
                     int32_t out_coff, int32_t dtype, void* stream) {
-    DISPATCH_DT(dtype, {
-        hipLaunchKernelGGL((gap_finish_kernel<T>), dim3(grid_for((long long)N * C, 1024)), dim3(256), 0,
-                           (hipStream_t)stream, part, (T*)out, N, C, nparts, 1.f / (float)HW, out_ld, out_coff);
-        return (int)hipGetLastError();
-    });
+    DISPATCH_DT(dtype, return launch<gap_finish_kernel<T>, 0>(dim3(grid_for((long long)N * C, 1024)), dim3(256), 0,
+                                                              (hipStream_t)stream, part, (T*)out, N, C, nparts, 1.f / (float)HW,
+                                                              out_ld, out_coff));
 }
 
 int pmoe_gap_bwd(const void* g, void* dx, int32_t N, int64_t HW, int32_t C, int32_t g_ld, int32_t g_coff, int32_t dtype,
                  void* stream) {
     DISPATCH_DT(dtype, {
-        constexpr int VE = 16 / (int)sizeof(T);
+        constexpr int VE = VecOf<T>::N;
         if (C % VE || g_ld % VE || g_coff % VE) return PMOE_ERR_ARG;
-        hipLaunchKernelGGL((gap_bwd_kernel<T>), dim3(grid_for(HW * (C / VE), 256), N), dim3(256), 0,
-                           (hipStream_t)stream, (const T*)g, (T*)dx, (long long)HW, C, g_ld, g_coff, 1.f / (float)HW);
-        return (int)hipGetLastError();
+        return launch<gap_bwd_kernel<T>, 0>(dim3(grid_for(HW * (C / VE), 256), N), dim3(256), 0, (hipStream_t)stream, (const T*)g,
+                                            (T*)dx, (long long)HW, C, g_ld, g_coff, 1.f / (float)HW);
     });
 }
 
 int pmoe_eca_gate(const float* gap_part, int32_t nparts, int64_t HW, const void* const* w_ptrs, int32_t k, float* gate,
                   float* gapmean, int32_t N, int32_t ipe, int32_t in_ipe, int32_t C, int32_t creal, void* stream) {
     if (C > 1024 || k > 9 || k < 1 || !(k & 1)) return PMOE_ERR_ARG;
-    hipLaunchKernelGGL(eca_gate_kernel, dim3(N), dim3(256), 0, (hipStream_t)stream, gap_part, nparts, 1.f / (float)HW,
-                       (const float* const*)w_ptrs, k, gate, gapmean, ipe, in_ipe, C, creal);
-    return (int)hipGetLastError();
+    return launch<eca_gate_kernel, 0>(dim3(N), dim3(256), 0, (hipStream_t)stream, gap_part, nparts, 1.f / (float)HW,
+                                      (const float* const*)w_ptrs, k, gate, gapmean, ipe, in_ipe, C, creal);
 }
 
 int pmoe_eca_scale(const void* x, const float* gate, void* y, int32_t N, int64_t HW, int32_t C, int32_t x_shared_ipe,
                    int32_t dtype, void* stream) {
     DISPATCH_DT(dtype, {
-        constexpr int VE = 16 / (int)sizeof(T);
+        constexpr int VE = VecOf<T>::N;
         if (C % VE) return PMOE_ERR_ARG;
-        hipLaunchKernelGGL((eca_scale_kernel<T>), dim3(grid_for(HW * (C / VE), 512), N), dim3(256), 0,
-                           (hipStream_t)stream, (const T*)x, gate, (T*)y, (long long)HW, C, x_shared_ipe);
-        return (int)hipGetLastError();
+        return launch<eca_scale_kernel<T>, 0>(dim3(grid_for(HW * (C / VE), 512), N), dim3(256), 0, (hipStream_t)stream, (const T*)x,
+                                              gate, (T*)y, (long long)HW, C, x_shared_ipe);
     });
 }
 
@@ -991,20 +947,18 @@ int pmoe_eca_bwd_small(const float* dot_part, int32_t nparts, const float* gate,
                        const void* const* w_ptrs, int32_t k, float* dgap, float* dw, float* dw_scratch, int32_t N,
                        int32_t ipe, int32_t C, int32_t creal, float dgap_scale, void* stream) {
     if (C > 1024 || k > 9 || k < 1 || N % ipe || !dw_scratch) return PMOE_ERR_ARG;
-    hipLaunchKernelGGL(eca_bwd_small_kernel, dim3(N), dim3(256), 0, (hipStream_t)stream, dot_part, nparts, gate,
-                       gapmean, (const float* const*)w_ptrs, k, dgap, dw_scratch, ipe, C, creal, dgap_scale);
-    hipLaunchKernelGGL(eca_bwd_dw_kernel, dim3(N / ipe), dim3(64), 0, (hipStream_t)stream, dw_scratch, dw, ipe, k);
-    return (int)hipGetLastError();
+    HIP_RET((launch<eca_bwd_small_kernel, 0>(dim3(N), dim3(256), 0, (hipStream_t)stream, dot_part, nparts, gate, gapmean,
+                                             (const float* const*)w_ptrs, k, dgap, dw_scratch, ipe, C, creal, dgap_scale)));
+    return launch<eca_bwd_dw_kernel, 0>(dim3(N / ipe), dim3(64), 0, (hipStream_t)stream, dw_scratch, dw, ipe, k);
 }
 
 int pmoe_eca_bwd_apply(const void* dy, const float* gate, const float* dgap, void* dx, int32_t N, int64_t HW, int32_t C,
                        int32_t dtype, void* stream) {
     DISPATCH_DT(dtype, {
-        constexpr int VE = 16 / (int)sizeof(T);
+        constexpr int VE = VecOf<T>::N;
         if (C % VE) return PMOE_ERR_ARG;
-        hipLaunchKernelGGL((eca_bwd_apply_kernel<T>), dim3(grid_for(HW * (C / VE), 512), N), dim3(256), 0,
-                           (hipStream_t)stream, (const T*)dy, gate, dgap, (T*)dx, (long long)HW, C, 1.f / (float)HW);
-        return (int)hipGetLastError();
+        return launch<eca_bwd_apply_kernel<T>, 0>(dim3(grid_for(HW * (C / VE), 512), N), dim3(256), 0, (hipStream_t)stream,
+                                                  (const T*)dy, gate, dgap, (T*)dx, (long long)HW, C, 1.f / (float)HW);
     });
 }
 
@@ -1012,26 +966,22 @@ int pmoe_nchw_to_nhwc(const float* src, void* dst, int32_t B, int32_t C, int32_t
                       int32_t dtype, void* stream) {
     if (B < 1 || C < 1 || H < 1 || W < 1 || Cp < C) return PMOE_ERR_ARG;
     const long long HW = (long long)H * W, nblk = (HW + 63) / 64 * B, nblk4 = (HW + 255) / 256 * B;
+    hipStream_t st = (hipStream_t)stream;
     DISPATCH_DT(dtype, {
         if (Cp <= 32 && nblk4 <= 0x7fffffffLL)           // few channels (camera frames): 256 pixels per workgroup
-            hipLaunchKernelGGL((nchw_to_nhwc_tiled_kernel<T, 256>), dim3((unsigned)nblk4), dim3(256),
-                               256 * (Cp + 1) * sizeof(float), (hipStream_t)stream, src, (T*)dst, B, C, HW, Cp);
-        else if (Cp <= 240 && nblk <= 0x7fffffffLL)
-            hipLaunchKernelGGL((nchw_to_nhwc_tiled_kernel<T, 64>), dim3((unsigned)nblk), dim3(256),
-                               64 * (Cp + 1) * sizeof(float), (hipStream_t)stream, src, (T*)dst, B, C, HW, Cp);
-        else
-            hipLaunchKernelGGL((nchw_to_nhwc_kernel<T>), dim3(grid_for((long long)B * H * W, 8192)), dim3(256), 0,
-                               (hipStream_t)stream, src, (T*)dst, B, C, H, W, Cp);
-        return (int)hipGetLastError();
+            return launch<nchw_to_nhwc_tiled_kernel<T, 256>, 0>(dim3((unsigned)nblk4), dim3(256), 256 * (Cp + 1) * sizeof(float),
+                                                                st, src, (T*)dst, B, C, HW, Cp);
+        if (Cp <= 240 && nblk <= 0x7fffffffLL)
+            return launch<nchw_to_nhwc_tiled_kernel<T, 64>, 0>(dim3((unsigned)nblk), dim3(256), 64 * (Cp + 1) * sizeof(float), st,
+                                                               src, (T*)dst, B, C, HW, Cp);
+        return launch<nchw_to_nhwc_kernel<T>, 0>(dim3(grid_for((long long)B * H * W, 8192)), dim3(256), 0, st, src, (T*)dst, B, C,
+                                                 H, W, Cp);
     });
 }
 
 int pmoe_pad_rows(const float* src, void* dst, int32_t B, int32_t K, int32_t Kp, int32_t dtype, void* stream) {
-    DISPATCH_DT(dtype, {
-        hipLaunchKernelGGL((pad_rows_kernel<T>), dim3(grid_for((long long)B * Kp, 64)), dim3(256), 0,
-                           (hipStream_t)stream, src, (T*)dst, B, K, Kp);
-        return (int)hipGetLastError();
-    });
+    DISPATCH_DT(dtype, return launch<pad_rows_kernel<T>, 0>(dim3(grid_for((long long)B * Kp, 64)), dim3(256), 0,
+                                                            (hipStream_t)stream, src, (T*)dst, B, K, Kp));
 }
 
 }  // extern "C"

@@ -428,97 +428,62 @@ int pmoe_pack_conv_weights_fp8(const void* const* src_ptrs, void* fwd_e4m3, void
                                float in_scale, int32_t E, int32_t cout, int32_t cin, int32_t ks, int32_t coutp, int32_t cinp,
                                int32_t cinp2, int32_t coutp2, void* stream) {
     if (!src_ptrs || !wscale || !oscale || !(in_scale > 0.f)) return PMOE_ERR_ARG;
-    if (coutp < cout || cinp < cin || (dgrd_bf16 && (cinp2 < cin || coutp2 < cout))) return PMOE_ERR_ARG;
+    if (!pack_shape_ok(cout, cin, coutp, cinp, dgrd_bf16, cinp2, coutp2)) return PMOE_ERR_ARG;
     const int taps = ks * ks;
-    hipLaunchKernelGGL(fp8_row_scale_kernel, dim3(coutp, E), dim3(256), 0, (hipStream_t)stream,
-                       (const float* const*)src_ptrs, wscale, oscale, in_scale, cout, coutp, cin * taps);
+    HIP_RET((launch<fp8_row_scale_kernel, 0>(dim3(coutp, E), dim3(256), 0, (hipStream_t)stream, (const float* const*)src_ptrs,
+                                             wscale, oscale, in_scale, cout, coutp, cin * taps)));
     const long long n = (fwd_e4m3 ? (long long)coutp * taps * cinp : 0) + (dgrd_bf16 ? (long long)cinp2 * taps * coutp2 : 0);
-    long long g = (n + 255) / 256;
-    if (g > 1024) g = 1024;
-    if (n > 0)
-        hipLaunchKernelGGL(pack_w_fp8_kernel, dim3((int)g, E), dim3(256), 0, (hipStream_t)stream,
-                           (const float* const*)src_ptrs, wscale, (unsigned char*)fwd_e4m3, (bf16*)dgrd_bf16, cout, cin, taps,
-                           coutp, cinp, cinp2, coutp2);
-    return (int)hipGetLastError();
+    if (n <= 0) return 0;
+    return launch<pack_w_fp8_kernel, 0>(dim3(grid_for(n, 1024), E), dim3(256), 0, (hipStream_t)stream,
+                                        (const float* const*)src_ptrs, wscale, (unsigned char*)fwd_e4m3, (bf16*)dgrd_bf16, cout,
+                                        cin, taps, coutp, cinp, cinp2, coutp2);
 }
 
 int pmoe_pack_conv_weights(const void* const* src_ptrs, void* fwd, void* dgrd, int32_t E, int32_t cout, int32_t cin,
                            int32_t ks, int32_t coutp, int32_t cinp, int32_t cinp2, int32_t coutp2, int32_t dtype,
                            void* stream) {
-    if (coutp < cout || cinp < cin || (dgrd && (cinp2 < cin || coutp2 < cout))) return PMOE_ERR_ARG;
+    if (!pack_shape_ok(cout, cin, coutp, cinp, dgrd, cinp2, coutp2)) return PMOE_ERR_ARG;
     const int taps = ks * ks;
     const long long n = (fwd ? (long long)coutp * taps * cinp : 0) + (dgrd ? (long long)cinp2 * taps * coutp2 : 0);
     if (n >= 0x7fffffffll) return PMOE_ERR_ARG;
-    long long g = (n + 255) / 256;
-    if (g > 1024) g = 1024;
-    if (dtype == PMOE_DT_BF16)
-        hipLaunchKernelGGL((pack_w_kernel<bf16>), dim3((int)g, E), dim3(256), 0, (hipStream_t)stream,
-                           (const float* const*)src_ptrs, (bf16*)fwd, (bf16*)dgrd, cout, cin, taps, coutp, cinp, cinp2,
-                           coutp2);
-    else if (dtype == PMOE_DT_F32)
-        hipLaunchKernelGGL((pack_w_kernel<float>), dim3((int)g, E), dim3(256), 0, (hipStream_t)stream,
-                           (const float* const*)src_ptrs, (float*)fwd, (float*)dgrd, cout, cin, taps, coutp, cinp, cinp2,
-                           coutp2);
-    else
-        return PMOE_ERR_ARG;
-    return (int)hipGetLastError();
+    DISPATCH_DT(dtype, return launch<pack_w_kernel<T>, 0>(dim3(grid_for(n, 1024), E), dim3(256), 0, (hipStream_t)stream,
+                                                          (const float* const*)src_ptrs, (T*)fwd, (T*)dgrd, cout, cin, taps, coutp,
+                                                          cinp, cinp2, coutp2));
 }
 
 int pmoe_pack_conv_weights_gated(const void* const* src_ptrs, const float* gate, int32_t gate_ld, void* fwd, void* dgrd,
                                  int32_t N, int32_t ipe, int32_t cout, int32_t cin, int32_t ks, int32_t coutp, int32_t cinp,
                                  int32_t cinp2, int32_t coutp2, int32_t dtype, void* stream) {
-    if (N < 1 || ipe < 1 || N % ipe || coutp < cout || cinp < cin || gate_ld < cin || !gate ||
-        (dgrd && (cinp2 < cin || coutp2 < cout)))
+    if (N < 1 || ipe < 1 || N % ipe || gate_ld < cin || !gate || !pack_shape_ok(cout, cin, coutp, cinp, dgrd, cinp2, coutp2))
         return PMOE_ERR_ARG;
     const int taps = ks * ks;
     const long long n = (fwd ? (long long)coutp * taps * cinp : 0) + (dgrd ? (long long)cinp2 * taps * coutp2 : 0);
-    long long g = (n + 255) / 256;
-    if (g > 64) g = 64;
-    if (dtype == PMOE_DT_BF16)
-        hipLaunchKernelGGL((pack_w_gated_kernel<bf16>), dim3((int)g, N), dim3(256), 0, (hipStream_t)stream,
-                           (const float* const*)src_ptrs, gate, gate_ld, (bf16*)fwd, (bf16*)dgrd, ipe, cout, cin, taps, coutp,
-                           cinp, cinp2, coutp2);
-    else if (dtype == PMOE_DT_F32)
-        hipLaunchKernelGGL((pack_w_gated_kernel<float>), dim3((int)g, N), dim3(256), 0, (hipStream_t)stream,
-                           (const float* const*)src_ptrs, gate, gate_ld, (float*)fwd, (float*)dgrd, ipe, cout, cin, taps, coutp,
-                           cinp, cinp2, coutp2);
-    else
-        return PMOE_ERR_ARG;
-    return (int)hipGetLastError();
+    DISPATCH_DT(dtype, return launch<pack_w_gated_kernel<T>, 0>(dim3(grid_for(n, 64), N), dim3(256), 0, (hipStream_t)stream,
+                                                                (const float* const*)src_ptrs, gate, gate_ld, (T*)fwd, (T*)dgrd,
+                                                                ipe, cout, cin, taps, coutp, cinp, cinp2, coutp2));
 }
 
 int pmoe_pack_conv_weights_scaled(const void* const* src_ptrs, const float* scale, const float* shift, const float* mean,
                                   void* fwd, float* bias, int32_t E, int32_t cout, int32_t cin, int32_t ks, int32_t coutp,
                                   int32_t cinp, int32_t dtype, void* stream) {
-    if (E < 1 || coutp < cout || cinp < cin || !scale || !shift || !mean || !fwd || !bias) return PMOE_ERR_ARG;
-    const int taps = ks * ks;
-    long long g = ((long long)coutp * taps * cinp + 255) / 256;
-    if (g > 1024) g = 1024;
-    if (dtype == PMOE_DT_BF16)
-        hipLaunchKernelGGL((pack_w_scaled_kernel<bf16>), dim3((int)g, E), dim3(256), 0, (hipStream_t)stream,
-                           (const float* const*)src_ptrs, scale, shift, mean, (bf16*)fwd, bias, cout, cin, taps, coutp, cinp);
-    else if (dtype == PMOE_DT_F32)
-        hipLaunchKernelGGL((pack_w_scaled_kernel<float>), dim3((int)g, E), dim3(256), 0, (hipStream_t)stream,
-                           (const float* const*)src_ptrs, scale, shift, mean, (float*)fwd, bias, cout, cin, taps, coutp, cinp);
-    else
+    if (E < 1 || !pack_shape_ok(cout, cin, coutp, cinp, nullptr, 0, 0) || !scale || !shift || !mean || !fwd || !bias)
         return PMOE_ERR_ARG;
-    return (int)hipGetLastError();
+    const int taps = ks * ks;
+    DISPATCH_DT(dtype, return launch<pack_w_scaled_kernel<T>, 0>(dim3(grid_for((long long)coutp * taps * cinp, 1024), E),
+            dim3(256), 0, (hipStream_t)stream, (const float* const*)src_ptrs, scale, shift, mean, (T*)fwd, bias, cout, cin, taps,
+            coutp, cinp));
 }
 
 int pmoe_unpack_conv_wgrad(const float* dw_ws, float* grads, int32_t E, int32_t cout, int32_t cin, int32_t ks,
                            int32_t coutp, int32_t cinp, void* stream) {
     const int taps = ks * ks;
-    long long g = ((long long)cout * cin * taps + 255) / 256;
-    if (g > 1024) g = 1024;
-    hipLaunchKernelGGL(unpack_wgrad_kernel, dim3((int)g, E), dim3(256), 0, (hipStream_t)stream, dw_ws, grads, cout, cin,
-                       taps, coutp, cinp);
-    return (int)hipGetLastError();
+    return launch<unpack_wgrad_kernel, 0>(dim3(grid_for((long long)cout * cin * taps, 1024), E), dim3(256), 0, (hipStream_t)stream,
+                                          dw_ws, grads, cout, cin, taps, coutp, cinp);
 }
 
 int pmoe_pack_bias(const void* const* src_ptrs, float* dst, int32_t E, int32_t cout, int32_t coutp, void* stream) {
-    hipLaunchKernelGGL(pack_bias_kernel, dim3((coutp + 255) / 256, E), dim3(256), 0, (hipStream_t)stream,
-                       (const float* const*)src_ptrs, dst, cout, coutp);
-    return (int)hipGetLastError();
+    return launch<pack_bias_kernel, 0>(dim3((coutp + 255) / 256, E), dim3(256), 0, (hipStream_t)stream,
+                                       (const float* const*)src_ptrs, dst, cout, coutp);
 }
 
 int pmoe_eca_stem_fold(const float* G, const float* gate, const void* const* w_ptrs, float* dw, float* ds, int32_t N,
@@ -526,12 +491,10 @@ int pmoe_eca_stem_fold(const float* G, const float* gate, const void* const* w_p
                        void* stream) {
     if (N % ipe || gate_ld > 256 || cin > cinp || cin > gate_ld || cout > coutp) return PMOE_ERR_ARG;
     const int taps = ks * ks, E = N / ipe;
-    int g = (cout * cin * taps + 255) / 256;
-    hipLaunchKernelGGL(eca_stem_fold_dw_kernel, dim3(g, E), dim3(256), 0, (hipStream_t)stream, G, gate, dw, ipe, cout, cin,
-                       taps, coutp, cinp, gate_ld);
-    hipLaunchKernelGGL(eca_stem_fold_ds_kernel, dim3(N), dim3(256), 0, (hipStream_t)stream, G,
-                       (const float* const*)w_ptrs, ds, ipe, cout, cin, taps, coutp, cinp, gate_ld);
-    return (int)hipGetLastError();
+    HIP_RET((launch<eca_stem_fold_dw_kernel, 0>(dim3((cout * cin * taps + 255) / 256, E), dim3(256), 0, (hipStream_t)stream, G,
+                                                gate, dw, ipe, cout, cin, taps, coutp, cinp, gate_ld)));
+    return launch<eca_stem_fold_ds_kernel, 0>(dim3(N), dim3(256), 0, (hipStream_t)stream, G, (const float* const*)w_ptrs, ds, ipe,
+                                              cout, cin, taps, coutp, cinp, gate_ld);
 }
 
 int pmoe_gate_mixture_fwd(const void* head, int32_t head_ld, const void* spd, int32_t spd_ld, float* probs, float* mean,
@@ -539,16 +502,9 @@ int pmoe_gate_mixture_fwd(const void* head, int32_t head_ld, const void* spd, in
                           int32_t dtype, void* stream) {
     if (E < 1 || E > 64 || head_ld < (shared ? 5 * E : 5)) return PMOE_ERR_ARG;
     const int G = pow2ceil(E);
-    const int blocks = (B * G + 255) / 256;
-    if (dtype == PMOE_DT_BF16)
-        hipLaunchKernelGGL((gate_fwd_kernel<bf16>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const bf16*)head,
-                           head_ld, (const bf16*)spd, spd_ld, probs, mean, std_, speeds, B, E, G, alpha_relu, shared);
-    else if (dtype == PMOE_DT_F32)
-        hipLaunchKernelGGL((gate_fwd_kernel<float>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const float*)head,
-                           head_ld, (const float*)spd, spd_ld, probs, mean, std_, speeds, B, E, G, alpha_relu, shared);
-    else
-        return PMOE_ERR_ARG;
-    return (int)hipGetLastError();
+    DISPATCH_DT(dtype, return launch<gate_fwd_kernel<T>, 0>(dim3((B * G + 255) / 256), dim3(256), 0, (hipStream_t)stream,
+                                                            (const T*)head, head_ld, (const T*)spd, spd_ld, probs, mean, std_,
+                                                            speeds, B, E, G, alpha_relu, shared));
 }
 
 int pmoe_gate_mixture_bwd(const void* head, int32_t head_ld, const float* probs, const float* dprobs, const float* dmean,
@@ -556,27 +512,17 @@ int pmoe_gate_mixture_bwd(const void* head, int32_t head_ld, const float* probs,
                           int32_t E, int32_t alpha_relu, int32_t shared, int32_t dtype, void* stream) {
     if (E < 1 || E > 64 || head_ld < (shared ? 5 * E : 5)) return PMOE_ERR_ARG;
     const int G = pow2ceil(E);
-    const int blocks = (B * G + 255) / 256;
-    if (dtype == PMOE_DT_BF16)
-        hipLaunchKernelGGL((gate_bwd_kernel<bf16>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const bf16*)head,
-                           head_ld, probs, dprobs, dmean, dstd, dspeeds, (bf16*)dhead, (bf16*)dspd, spd_ld, B, E, G,
-                           alpha_relu, shared);
-    else if (dtype == PMOE_DT_F32)
-        hipLaunchKernelGGL((gate_bwd_kernel<float>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const float*)head,
-                           head_ld, probs, dprobs, dmean, dstd, dspeeds, (float*)dhead, (float*)dspd, spd_ld, B, E, G,
-                           alpha_relu, shared);
-    else
-        return PMOE_ERR_ARG;
-    return (int)hipGetLastError();
+    DISPATCH_DT(dtype, return launch<gate_bwd_kernel<T>, 0>(dim3((B * G + 255) / 256), dim3(256), 0, (hipStream_t)stream,
+                                                            (const T*)head, head_ld, probs, dprobs, dmean, dstd, dspeeds, (T*)dhead,
+                                                            (T*)dspd, spd_ld, B, E, G, alpha_relu, shared));
 }
 
 int pmoe_moe_loss(const float* probs, const float* mean, const float* std_, const float* speeds, const float* actions,
                   const float* target_speed, float c0, float c1, float* loss, float* loglik, float* dprobs, float* dmean,
                   float* dstd, float* dspeeds, int32_t B, int32_t E, int32_t shared_speed, void* stream) {
     if (E < 1 || E > 64) return PMOE_ERR_ARG;
-    hipLaunchKernelGGL(moe_loss_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, probs, mean, std_, speeds, actions,
-                       target_speed, c0, c1, loss, loglik, dprobs, dmean, dstd, dspeeds, B, E, pow2ceil(E), shared_speed);
-    return (int)hipGetLastError();
+    return launch<moe_loss_kernel, 0>(dim3(1), dim3(256), 0, (hipStream_t)stream, probs, mean, std_, speeds, actions, target_speed,
+                                      c0, c1, loss, loglik, dprobs, dmean, dstd, dspeeds, B, E, pow2ceil(E), shared_speed);
 }
 
 }  // extern "C"

@@ -399,22 +399,19 @@ extern "C" {
 int pmoe_mt_grad_norm(const pmoe_opt_tensor* table, const int32_t* chunk_tensor, const int32_t* chunk_index,
                       int32_t n_chunks, float max_norm, float* partial, float* norm, int32_t scale_grads, void* stream) {
     if (n_chunks < 1 || !table || !partial || !norm) return PMOE_ERR_ARG;
-    hipLaunchKernelGGL(mt_sqsum_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, table, chunk_tensor, chunk_index,
-                       partial);
-    hipLaunchKernelGGL(mt_norm_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partial, n_chunks, max_norm, norm);
-    if (scale_grads)
-        hipLaunchKernelGGL(mt_scale_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, table, chunk_tensor,
-                           chunk_index, norm);
-    return (int)hipGetLastError();
+    hipStream_t st = (hipStream_t)stream;
+    HIP_RET((launch<mt_sqsum_kernel, 0>(dim3(n_chunks), dim3(256), 0, st, table, chunk_tensor, chunk_index, partial)));
+    HIP_RET((launch<mt_norm_finish_kernel, 0>(dim3(1), dim3(256), 0, st, partial, n_chunks, max_norm, norm)));
+    if (!scale_grads) return 0;
+    return launch<mt_scale_kernel, 0>(dim3(n_chunks), dim3(256), 0, st, table, chunk_tensor, chunk_index, norm);
 }
 
 int pmoe_mt_adam(const pmoe_opt_tensor* table, const int32_t* chunk_tensor, const int32_t* chunk_index, int32_t n_chunks,
                  float lr, float beta1, float beta2, float eps, float weight_decay, int32_t amsgrad, float bc1_all,
                  float bc2_sqrt_all, const float* norm, void* stream) {
     if (n_chunks < 1 || !table) return PMOE_ERR_ARG;
-    hipLaunchKernelGGL(mt_adam_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, table, chunk_tensor, chunk_index,
-                       lr, beta1, beta2, eps, weight_decay, amsgrad, bc1_all, bc2_sqrt_all, norm);
-    return (int)hipGetLastError();
+    return launch<mt_adam_kernel, 0>(dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, table, chunk_tensor, chunk_index, lr, beta1,
+                                     beta2, eps, weight_decay, amsgrad, bc1_all, bc2_sqrt_all, norm);
 }
 
 int pmoe_mt_adam_packs(const pmoe_opt_tensor* table, const pmoe_opt_pack* packs, const int32_t* tile_tensor,
@@ -422,35 +419,31 @@ int pmoe_mt_adam_packs(const pmoe_opt_tensor* table, const pmoe_opt_pack* packs,
                        float eps, float weight_decay, int32_t amsgrad, float bc1_all, float bc2_sqrt_all, const float* norm,
                        void* stream) {
     if (n_tiles < 1 || !table || !packs || !tile_tensor || !tile_co0 || !tile_ci0) return PMOE_ERR_ARG;
-    hipLaunchKernelGGL(mt_adam_pack_kernel, dim3(n_tiles), dim3(256), 0, (hipStream_t)stream, table, packs, tile_tensor,
-                       tile_co0, tile_ci0, lr, beta1, beta2, eps, weight_decay, amsgrad, bc1_all, bc2_sqrt_all, norm);
-    return (int)hipGetLastError();
+    return launch<mt_adam_pack_kernel, 0>(dim3(n_tiles), dim3(256), 0, (hipStream_t)stream, table, packs, tile_tensor, tile_co0,
+                                          tile_ci0, lr, beta1, beta2, eps, weight_decay, amsgrad, bc1_all, bc2_sqrt_all, norm);
 }
 
 int pmoe_mt_rmsprop(const pmoe_opt_tensor* table, const int32_t* chunk_tensor, const int32_t* chunk_index, int32_t n_chunks,
                     float lr, float alpha, float eps, float weight_decay, float momentum, int32_t centered, const float* norm,
                     void* stream) {
     if (n_chunks < 1 || !table || !chunk_tensor || !chunk_index) return PMOE_ERR_ARG;
-    hipLaunchKernelGGL(mt_rmsprop_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, table, chunk_tensor, chunk_index,
-                       lr, alpha, eps, weight_decay, momentum, centered, norm);
-    return (int)hipGetLastError();
+    return launch<mt_rmsprop_kernel, 0>(dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, table, chunk_tensor, chunk_index, lr,
+                                        alpha, eps, weight_decay, momentum, centered, norm);
 }
 
 int pmoe_mt_rmsprop_packs(const pmoe_opt_tensor* table, const pmoe_opt_pack* packs, const int32_t* tile_tensor,
                           const int32_t* tile_co0, const int32_t* tile_ci0, int32_t n_tiles, float lr, float alpha, float eps,
                           float weight_decay, float momentum, int32_t centered, const float* norm, void* stream) {
     if (n_tiles < 1 || !table || !packs || !tile_tensor || !tile_co0 || !tile_ci0) return PMOE_ERR_ARG;
-    hipLaunchKernelGGL(mt_rmsprop_pack_kernel, dim3(n_tiles), dim3(256), 0, (hipStream_t)stream, table, packs, tile_tensor,
-                       tile_co0, tile_ci0, lr, alpha, eps, weight_decay, momentum, centered, norm);
-    return (int)hipGetLastError();
+    return launch<mt_rmsprop_pack_kernel, 0>(dim3(n_tiles), dim3(256), 0, (hipStream_t)stream, table, packs, tile_tensor, tile_co0,
+                                             tile_ci0, lr, alpha, eps, weight_decay, momentum, centered, norm);
 }
 
 int pmoe_mt_swa_update(const pmoe_opt_tensor* table, const int32_t* chunk_tensor, const int32_t* chunk_index,
                        int32_t n_chunks, int64_t n_averaged, void* stream) {
     if (n_chunks < 1 || !table || n_averaged < 0) return PMOE_ERR_ARG;
-    hipLaunchKernelGGL(mt_swa_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, table, chunk_tensor, chunk_index,
-                       1.f / (float)(n_averaged + 1));
-    return (int)hipGetLastError();
+    return launch<mt_swa_kernel, 0>(dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, table, chunk_tensor, chunk_index,
+                                    1.f / (float)(n_averaged + 1));
 }
 
 }  // extern "C"

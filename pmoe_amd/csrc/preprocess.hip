@@ -65,11 +65,6 @@ __global__ void __launch_bounds__(256) resample_v_kernel(const uint8_t* __restri
     }
 }
 
-static inline int grid_for(long long n) {
-    long long g = (n + 255) / 256;
-    return (int)(g < 1 ? 1 : (g > 16384 ? 16384 : g));
-}
-
 extern "C" {
 
 int pmoe_resample_u8_horizontal(const uint8_t* src, uint8_t* dst, int32_t n_img, int32_t H0, int32_t W0, int32_t row0,
@@ -78,9 +73,8 @@ int pmoe_resample_u8_horizontal(const uint8_t* src, uint8_t* dst, int32_t n_img,
     if (!src || !dst || !bounds || !coeffs || n_img < 1 || rows < 1 || row0 < 0 || row0 + rows > H0 || W0 < 1 || Wout < 1 ||
         C < 1 || ksize < 1)
         return PMOE_ERR_ARG;
-    hipLaunchKernelGGL(resample_h_kernel, dim3(grid_for((long long)n_img * rows * Wout)), dim3(256), 0, (hipStream_t)stream,
-                       src, dst, n_img, H0, W0, row0, rows, C, Wout, bounds, coeffs, ksize);
-    return (int)hipGetLastError();
+    return launch<resample_h_kernel, 0>(dim3(grid_for((long long)n_img * rows * Wout, 16384)), dim3(256), 0, (hipStream_t)stream,
+                                        src, dst, n_img, H0, W0, row0, rows, C, Wout, bounds, coeffs, ksize);
 }
 
 int pmoe_resample_u8_vertical_to_f32(const uint8_t* src, float* dst_nchw, int32_t n_img, int32_t Hin, int32_t W, int32_t C,
@@ -88,9 +82,8 @@ int pmoe_resample_u8_vertical_to_f32(const uint8_t* src, float* dst_nchw, int32_
                                      void* stream) {
     if (!src || !dst_nchw || !bounds || !coeffs || n_img < 1 || Hin < 1 || W < 1 || C < 1 || Hout < 1 || ksize < 1)
         return PMOE_ERR_ARG;
-    hipLaunchKernelGGL(resample_v_kernel<float>, dim3(grid_for((long long)n_img * Hout * W)), dim3(256), 0,
-                       (hipStream_t)stream, src, dst_nchw, n_img, Hin, W, C, Hout, bounds, coeffs, ksize);
-    return (int)hipGetLastError();
+    return launch<resample_v_kernel<float>, 0>(dim3(grid_for((long long)n_img * Hout * W, 16384)), dim3(256), 0,
+                                               (hipStream_t)stream, src, dst_nchw, n_img, Hin, W, C, Hout, bounds, coeffs, ksize);
 }
 
 int pmoe_resample_u8_vertical_to_i64(const uint8_t* src, int64_t* dst_nchw, int32_t n_img, int32_t Hin, int32_t W, int32_t C,
@@ -98,18 +91,17 @@ int pmoe_resample_u8_vertical_to_i64(const uint8_t* src, int64_t* dst_nchw, int3
                                      void* stream) {
     if (!src || !dst_nchw || !bounds || !coeffs || n_img < 1 || Hin < 1 || W < 1 || C < 1 || Hout < 1 || ksize < 1)
         return PMOE_ERR_ARG;
-    hipLaunchKernelGGL(resample_v_kernel<long long>, dim3(grid_for((long long)n_img * Hout * W)), dim3(256), 0,
-                       (hipStream_t)stream, src, (long long*)dst_nchw, n_img, Hin, W, C, Hout, bounds, coeffs, ksize);
-    return (int)hipGetLastError();
+    return launch<resample_v_kernel<long long>, 0>(dim3(grid_for((long long)n_img * Hout * W, 16384)), dim3(256), 0,
+                                                   (hipStream_t)stream, src, (long long*)dst_nchw, n_img, Hin, W, C, Hout, bounds,
+                                                   coeffs, ksize);
 }
 
 int pmoe_resample_u8_vertical_to_u8(const uint8_t* src, uint8_t* dst_nhwc, int32_t n_img, int32_t Hin, int32_t W, int32_t C,
                                     int32_t Hout, const int32_t* bounds, const int32_t* coeffs, int32_t ksize, void* stream) {
     if (!src || !dst_nhwc || !bounds || !coeffs || n_img < 1 || Hin < 1 || W < 1 || C < 1 || Hout < 1 || ksize < 1)
         return PMOE_ERR_ARG;
-    hipLaunchKernelGGL(resample_v_kernel<uint8_t>, dim3(grid_for((long long)n_img * Hout * W)), dim3(256), 0,
-                       (hipStream_t)stream, src, dst_nhwc, n_img, Hin, W, C, Hout, bounds, coeffs, ksize);
-    return (int)hipGetLastError();
+    return launch<resample_v_kernel<uint8_t>, 0>(dim3(grid_for((long long)n_img * Hout * W, 16384)), dim3(256), 0,
+                                                 (hipStream_t)stream, src, dst_nhwc, n_img, Hin, W, C, Hout, bounds, coeffs, ksize);
 }
 
 }  // extern "C"

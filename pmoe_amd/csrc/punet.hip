@@ -8,19 +8,6 @@
 // All of them are HBM-bound streaming kernels: 16-byte vectors, grid-stride, no LDS.
 #include "common.h"
 
-#define DISPATCH_DT(dtype, CALL)                      \
-    do {                                              \
-        if ((dtype) == PMOE_DT_BF16) { using T = bf16; CALL; } \
-        else if ((dtype) == PMOE_DT_F32) { using T = float; CALL; } \
-        else return PMOE_ERR_ARG;                     \
-    } while (0)
-
-static inline int grid_for(long long n, int cap = 8192) {
-    long long g = (n + 255) / 256;
-    if (g < 1) g = 1;
-    return (int)(g > cap ? cap : g);
-}
-
 // ------------------------------------------------------------------------------------------------
 template <typename T>
 __global__ void __launch_bounds__(256) maxpool2_kernel(const T* __restrict__ x, T* __restrict__ y, int N, int H, int W,
@@ -283,14 +270,12 @@ static int history_push_launch(void* ring, const void* item, int B, int T, long 
     constexpr int VR = 16 / (int)sizeof(RT);
     const bool vec = !(L % VR) && !((uintptr_t)ring % 16) && !((uintptr_t)item % 16);
     const long long work = vec ? L / VR : L;
-    const dim3 grid(grid_for(work > HW ? work : HW), B);
+    const dim3 grid(grid_for(work > HW ? work : HW, 8192), B);
     if (vec)
-        hipLaunchKernelGGL((history_push_kernel<RT, ET, VR>), grid, dim3(256), 0, stream, (RT*)ring, (const RT*)item, T, L,
-                           (ET*)nhwc, C, HW, Cp);
-    else
-        hipLaunchKernelGGL((history_push_kernel<RT, ET, 1>), grid, dim3(256), 0, stream, (RT*)ring, (const RT*)item, T, L,
-                           (ET*)nhwc, C, HW, Cp);
-    return (int)hipGetLastError();
+        return launch<history_push_kernel<RT, ET, VR>, 0>(grid, dim3(256), 0, stream, (RT*)ring, (const RT*)item, T, L, (ET*)nhwc,
+                                                          C, HW, Cp);
+    return launch<history_push_kernel<RT, ET, 1>, 0>(grid, dim3(256), 0, stream, (RT*)ring, (const RT*)item, T, L, (ET*)nhwc, C,
+                                                     HW, Cp);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -301,22 +286,21 @@ int pmoe_maxpool2s2_fwd(const void* x, void* y, int32_t N, int32_t H, int32_t W,
     if (H < 2 || W < 2 || N < 1) return PMOE_ERR_ARG;
     const int Ho = H / 2, Wo = W / 2;
     DISPATCH_DT(dtype, {
-        constexpr int VE = 16 / (int)sizeof(T);
-        if (C % VE || x_ld % VE || x_coff % VE || x_coff + C > x_ld) return PMOE_ERR_ARG;
-        hipLaunchKernelGGL((maxpool2_kernel<T>), dim3(grid_for((long long)N * Ho * Wo * (C / VE))), dim3(256), 0,
-                           (hipStream_t)stream, (const T*)x, (T*)y, N, H, W, C, Ho, Wo, x_ld, x_coff);
-        return (int)hipGetLastError();
+        constexpr int VE = VecOf<T>::N;
+        if (C % VE || !window_ok<T>(C, x_ld, x_coff)) return PMOE_ERR_ARG;
+        return launch<maxpool2_kernel<T>, 0>(dim3(grid_for((long long)N * Ho * Wo * (C / VE), 8192)), dim3(256), 0,
+                                             (hipStream_t)stream, (const T*)x, (T*)y, N, H, W, C, Ho, Wo, x_ld, x_coff);
     });
 }
 
 int pmoe_pixel_shuffle2(const void* src, void* dst, int32_t N, int32_t H, int32_t W, int32_t C, int32_t src_ld,
                         int32_t dst_ld, int32_t dst_coff, int32_t dtype, void* stream) {
     DISPATCH_DT(dtype, {
-        constexpr int VE = 16 / (int)sizeof(T);
-        if (C % VE || src_ld % VE || src_ld < 4 * C || dst_ld % VE || dst_coff % VE || dst_coff + C > dst_ld) return PMOE_ERR_ARG;
-        hipLaunchKernelGGL((pixel_shuffle2_kernel<T>), dim3(grid_for((long long)N * H * W * 4 * (C / VE))), dim3(256), 0,
-                           (hipStream_t)stream, (const T*)src, (T*)dst, N, H, W, C, src_ld, dst_ld, dst_coff);
-        return (int)hipGetLastError();
+        constexpr int VE = VecOf<T>::N;
+        if (C % VE || src_ld % VE || src_ld < 4 * C || !window_ok<T>(C, dst_ld, dst_coff)) return PMOE_ERR_ARG;
+        return launch<pixel_shuffle2_kernel<T>, 0>(dim3(grid_for((long long)N * H * W * 4 * (C / VE), 8192)), dim3(256), 0,
+                                                   (hipStream_t)stream, (const T*)src, (T*)dst, N, H, W, C, src_ld, dst_ld,
+                                                   dst_coff);
     });
 }
 
@@ -325,62 +309,51 @@ int pmoe_copy_window(const void* src, int32_t src_ld, int32_t src_coff, void* ds
     if (rows < 0 || C < 1 || src_coff + C > src_ld || dst_coff + C > dst_ld) return PMOE_ERR_ARG;
     if (rows == 0) return 0;
     DISPATCH_DT(dtype, {
-        constexpr int VE = 16 / (int)sizeof(T);
-        const bool vec = !(C % VE) && !(src_ld % VE) && !(src_coff % VE) && !(dst_ld % VE) && !(dst_coff % VE);
-        if (vec)
-            hipLaunchKernelGGL((copy_window_kernel<T, VE>), dim3(grid_for(rows * (C / VE))), dim3(256), 0,
-                               (hipStream_t)stream, (const T*)src, src_ld, src_coff, (T*)dst, dst_ld, dst_coff,
-                               (long long)rows, C);
-        else
-            hipLaunchKernelGGL((copy_window_kernel<T, 1>), dim3(grid_for(rows * C)), dim3(256), 0, (hipStream_t)stream,
-                               (const T*)src, src_ld, src_coff, (T*)dst, dst_ld, dst_coff, (long long)rows, C);
-        return (int)hipGetLastError();
+        constexpr int VE = VecOf<T>::N;
+        // whole 16-byte vectors on both sides, or the scalar kernel
+        if (!(C % VE) && window_ok<T>(C, src_ld, src_coff) && window_ok<T>(C, dst_ld, dst_coff))
+            return launch<copy_window_kernel<T, VE>, 0>(dim3(grid_for(rows * (C / VE), 8192)), dim3(256), 0, (hipStream_t)stream,
+                                                        (const T*)src, src_ld, src_coff, (T*)dst, dst_ld, dst_coff,
+                                                        (long long)rows, C);
+        return launch<copy_window_kernel<T, 1>, 0>(dim3(grid_for(rows * C, 8192)), dim3(256), 0, (hipStream_t)stream, (const T*)src,
+                                                   src_ld, src_coff, (T*)dst, dst_ld, dst_coff, (long long)rows, C);
     });
 }
 
 int pmoe_action_head_fwd(const void* head, int32_t head_ld, const void* spd, int32_t spd_ld, float* actions,
                          float* speeds, int32_t B, int32_t dtype, void* stream) {
     if (B < 1 || head_ld < 2 || spd_ld < 1) return PMOE_ERR_ARG;
-    DISPATCH_DT(dtype, {
-        hipLaunchKernelGGL((action_head_fwd_kernel<T>), dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream,
-                           (const T*)head, head_ld, (const T*)spd, spd_ld, actions, speeds, B);
-        return (int)hipGetLastError();
-    });
+    DISPATCH_DT(dtype, return launch<action_head_fwd_kernel<T>, 0>(dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream,
+            (const T*)head, head_ld, (const T*)spd, spd_ld, actions, speeds, B));
 }
 
 int pmoe_action_head_bwd(const float* actions, const float* dactions, const float* dspeeds, void* dhead, int32_t head_ld,
                          void* dspd, int32_t spd_ld, int32_t B, int32_t dtype, void* stream) {
     if (B < 1 || head_ld < 2 || spd_ld < 1) return PMOE_ERR_ARG;
-    DISPATCH_DT(dtype, {
-        hipLaunchKernelGGL((action_head_bwd_kernel<T>), dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, actions,
-                           dactions, dspeeds, (T*)dhead, head_ld, (T*)dspd, spd_ld, B);
-        return (int)hipGetLastError();
-    });
+    DISPATCH_DT(dtype, return launch<action_head_bwd_kernel<T>, 0>(dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream,
+            actions, dactions, dspeeds, (T*)dhead, head_ld, (T*)dspd, spd_ld, B));
 }
 
 int pmoe_action_loss(const float* actions, const float* speeds, const float* actions_gt, const float* speed_gt, float c0,
                      float c1, float* loss, float* dactions, float* dspeeds, int32_t B, void* stream) {
     if (B < 1 || (speeds && (!speed_gt || !dspeeds))) return PMOE_ERR_ARG;
-    hipLaunchKernelGGL(action_loss_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, actions, speeds, actions_gt, speed_gt,
-                       c0, c1, loss, dactions, dspeeds, B);
-    return (int)hipGetLastError();
+    return launch<action_loss_kernel, 0>(dim3(1), dim3(256), 0, (hipStream_t)stream, actions, speeds, actions_gt, speed_gt, c0, c1,
+                                         loss, dactions, dspeeds, B);
 }
 
 int pmoe_blend_fwd(const float* moe_actions, const float* punet_actions, const float* lat_w, const float* lat_b,
                    const float* long_w, const float* long_b, float* out, int32_t B, void* stream) {
     if (B < 1) return PMOE_ERR_ARG;
-    hipLaunchKernelGGL(blend_fwd_kernel, dim3((2 * B + 255) / 256), dim3(256), 0, (hipStream_t)stream, moe_actions,
-                       punet_actions, lat_w, lat_b, long_w, long_b, out, B);
-    return (int)hipGetLastError();
+    return launch<blend_fwd_kernel, 0>(dim3((2 * B + 255) / 256), dim3(256), 0, (hipStream_t)stream, moe_actions, punet_actions,
+                                       lat_w, lat_b, long_w, long_b, out, B);
 }
 
 int pmoe_blend_bwd(const float* moe_actions, const float* punet_actions, const float* lat_w, const float* long_w,
                    const float* out, const float* dout, float* dlat_w, float* dlat_b, float* dlong_w, float* dlong_b,
                    float* dpunet, int32_t B, void* stream) {
     if (B < 1) return PMOE_ERR_ARG;
-    hipLaunchKernelGGL(blend_bwd_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, moe_actions, punet_actions, lat_w,
-                       long_w, out, dout, dlat_w, dlat_b, dlong_w, dlong_b, dpunet, B);
-    return (int)hipGetLastError();
+    return launch<blend_bwd_kernel, 0>(dim3(1), dim3(256), 0, (hipStream_t)stream, moe_actions, punet_actions, lat_w, long_w, out,
+                                       dout, dlat_w, dlat_b, dlong_w, dlong_b, dpunet, B);
 }
 
 int pmoe_history_push(void* ring, const void* item, int32_t B, int32_t T, int64_t L, int32_t dtype, void* nhwc, int32_t C,
@@ -407,9 +380,8 @@ int pmoe_mixture_draw(const float* probs, const float* mean, const float* std_, 
                       const float* long_b, float* out, int32_t B, int32_t E, void* stream) {
     if (!probs || !mean || !std_ || !state || !raw || B < 1 || E < 1 || (uintptr_t)state % 8) return PMOE_ERR_ARG;
     if (punet_actions && (!lat_w || !lat_b || !long_w || !long_b || !out)) return PMOE_ERR_ARG;
-    hipLaunchKernelGGL(mixture_draw_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, probs, mean, std_,
-                       (unsigned long long*)state, raw, punet_actions, lat_w, lat_b, long_w, long_b, out, B, E);
-    return (int)hipGetLastError();
+    return launch<mixture_draw_kernel, 0>(dim3(1), dim3(256), 0, (hipStream_t)stream, probs, mean, std_, (unsigned long long*)state,
+                                          raw, punet_actions, lat_w, lat_b, long_w, long_b, out, B, E);
 }
 
 }  // extern "C"

@@ -6,12 +6,6 @@
 // Counts are integers (LDS and global integer adds: the result does not depend on their order), no float atomics anywhere.
 #include "common.h"
 
-static inline int grid_for0(long long n, int cap = 8192) {
-    long long g = (n + 255) / 256;
-    if (g < 1) g = 1;
-    return (int)(g > cap ? cap : g);
-}
-
 constexpr int DICE_MAX_C = 64;
 
 // logits f32 [B][C][HW], target int64 [B][HW].  counts [3][C] (q: 0 arg-max == target == c, 1 arg-max == c, 2 target == c),
@@ -87,37 +81,29 @@ int pmoe_dice_score(const float* logits, const int64_t* target, int32_t B, int32
                     uint64_t* counts, float* dice, void* stream) {
     if (!logits || !target || !counts || !dice || B < 1 || C < 1 || C > DICE_MAX_C || HW < 1) return PMOE_ERR_ARG;
     HIP_RET(hipMemsetAsync(counts, 0, sizeof(uint64_t) * 3 * (size_t)C, (hipStream_t)stream));
-    hipLaunchKernelGGL(dice_count_kernel, dim3(grid_for0((long long)B * HW, 2048)), dim3(256), 0, (hipStream_t)stream, logits,
-                       (const long long*)target, B, C, (long long)HW, (unsigned long long*)counts);
-    hipLaunchKernelGGL(dice_finalize_kernel, dim3(1), dim3(DICE_MAX_C), 0, (hipStream_t)stream,
-                       (const unsigned long long*)counts, C, epsilon, dice);
-    return (int)hipGetLastError();
+    HIP_RET((launch<dice_count_kernel, 0>(dim3(grid_for((long long)B * HW, 2048)), dim3(256), 0, (hipStream_t)stream, logits,
+                                          (const long long*)target, B, C, (long long)HW, (unsigned long long*)counts)));
+    return launch<dice_finalize_kernel, 0>(dim3(1), dim3(DICE_MAX_C), 0, (hipStream_t)stream, (const unsigned long long*)counts, C,
+                                           epsilon, dice);
 }
 
 int pmoe_dropout2d_table(float* table, int32_t N, int32_t C, float p, uint64_t seed, void* stream) {
     if (!table || N < 1 || C < 1 || !(p >= 0.f) || p > 1.f) return PMOE_ERR_ARG;
     const long long total = (long long)N * C;
     const float keep_scale = p < 1.f ? 1.f / (1.f - p) : 0.f;
-    hipLaunchKernelGGL(dropout2d_table_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, table,
-                       total, p, keep_scale, (unsigned long long)seed);
-    return (int)hipGetLastError();
+    return launch<dropout2d_table_kernel, 0>(dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, table, total,
+                                             p, keep_scale, (unsigned long long)seed);
 }
 
 int pmoe_channel_scale(void* x, int32_t ld, int32_t coff, const float* table, int32_t N, int64_t HW, int32_t C, int32_t dtype,
                        void* stream) {
     if (!x || !table || N < 1 || HW < 1 || C < 1 || coff < 0 || coff + C > ld) return PMOE_ERR_ARG;
-    if (dtype == PMOE_DT_BF16) {
-        if (C % 8 || ld % 8 || coff % 8) return PMOE_ERR_ARG;
-        hipLaunchKernelGGL((channel_scale_kernel<bf16>), dim3(grid_for0((long long)N * HW * (C / 8))), dim3(256), 0,
-                           (hipStream_t)stream, (bf16*)x, ld, coff, table, N, (long long)HW, C);
-    } else if (dtype == PMOE_DT_F32) {
-        if (C % 4 || ld % 4 || coff % 4) return PMOE_ERR_ARG;
-        hipLaunchKernelGGL((channel_scale_kernel<float>), dim3(grid_for0((long long)N * HW * (C / 4))), dim3(256), 0,
-                           (hipStream_t)stream, (float*)x, ld, coff, table, N, (long long)HW, C);
-    } else {
-        return PMOE_ERR_ARG;
-    }
-    return (int)hipGetLastError();
+    DISPATCH_DT(dtype, {
+        constexpr int VE = VecOf<T>::N;
+        if (C % VE || !window_ok<T>(C, ld, coff)) return PMOE_ERR_ARG;
+        return launch<channel_scale_kernel<T>, 0>(dim3(grid_for((long long)N * HW * (C / VE), 8192)), dim3(256), 0,
+                                                  (hipStream_t)stream, (T*)x, ld, coff, table, N, (long long)HW, C);
+    });
 }
 
 }  // extern "C"

@@ -9,19 +9,6 @@
 // All HBM-bound streaming kernels; every reduction is fixed-order (partial rows + one finalize), no float atomics.
 #include "common.h"
 
-#define DISPATCH_DT(dtype, CALL)                      \
-    do {                                              \
-        if ((dtype) == PMOE_DT_BF16) { using T = bf16; CALL; } \
-        else if ((dtype) == PMOE_DT_F32) { using T = float; CALL; } \
-        else return PMOE_ERR_ARG;                     \
-    } while (0)
-
-static inline int grid_for(long long n, int cap = 8192) {
-    long long g = (n + 255) / 256;
-    if (g < 1) g = 1;
-    return (int)(g > cap ? cap : g);
-}
-
 // ------------------------------------------------------------------------------------------------
 // dx[n,2oy+i,2ox+j,c] = (first maximum of the 2x2 window in row-major order ? dy[n,oy,ox,c] : 0) + dskip[n,2oy+i,2ox+j,c]
 // (torch max_pool2d keeps the FIRST maximal element; ties are common after ReLU).  x and dskip may be channel windows.
@@ -435,13 +422,12 @@ int pmoe_maxpool2s2_bwd(const void* x, int32_t x_ld, int32_t x_coff, const void*
                         void* stream) {
     if (N < 1 || H < 2 || W < 2 || (H & 1) || (W & 1)) return PMOE_ERR_ARG;
     DISPATCH_DT(dtype, {
-        constexpr int VE = 16 / (int)sizeof(T);
-        if (C % VE || x_ld % VE || x_coff % VE || x_coff + C > x_ld) return PMOE_ERR_ARG;
-        if (dskip && (dskip_ld % VE || dskip_coff % VE || dskip_coff + C > dskip_ld)) return PMOE_ERR_ARG;
-        hipLaunchKernelGGL((maxpool2_bwd_kernel<T>), dim3(grid_for((long long)N * (H / 2) * (W / 2) * (C / VE))), dim3(256),
-                           0, (hipStream_t)stream, (const T*)x, x_ld, x_coff, (const T*)dy, (const T*)dskip, dskip_ld,
-                           dskip_coff, (T*)dx, N, H, W, C);
-        return (int)hipGetLastError();
+        constexpr int VE = VecOf<T>::N;
+        if (C % VE || !window_ok<T>(C, x_ld, x_coff)) return PMOE_ERR_ARG;
+        if (dskip && !window_ok<T>(C, dskip_ld, dskip_coff)) return PMOE_ERR_ARG;
+        return launch<maxpool2_bwd_kernel<T>, 0>(dim3(grid_for((long long)N * (H / 2) * (W / 2) * (C / VE), 8192)), dim3(256), 0,
+                                                 (hipStream_t)stream, (const T*)x, x_ld, x_coff, (const T*)dy, (const T*)dskip,
+                                                 dskip_ld, dskip_coff, (T*)dx, N, H, W, C);
     });
 }
 
@@ -449,11 +435,11 @@ int pmoe_pixel_unshuffle2(const void* src, int32_t src_ld, int32_t src_coff, voi
                           int32_t W, int32_t C, int32_t dtype, void* stream) {
     if (N < 1 || H < 1 || W < 1) return PMOE_ERR_ARG;
     DISPATCH_DT(dtype, {
-        constexpr int VE = 16 / (int)sizeof(T);
-        if (C % VE || src_ld % VE || src_coff % VE || src_coff + C > src_ld || dst_ld % VE || dst_ld < 4 * C) return PMOE_ERR_ARG;
-        hipLaunchKernelGGL((pixel_unshuffle2_kernel<T>), dim3(grid_for((long long)N * H * W * 4 * (C / VE))), dim3(256), 0,
-                           (hipStream_t)stream, (const T*)src, src_ld, src_coff, (T*)dst, dst_ld, N, H, W, C);
-        return (int)hipGetLastError();
+        constexpr int VE = VecOf<T>::N;
+        if (C % VE || !window_ok<T>(C, src_ld, src_coff) || dst_ld % VE || dst_ld < 4 * C) return PMOE_ERR_ARG;
+        return launch<pixel_unshuffle2_kernel<T>, 0>(dim3(grid_for((long long)N * H * W * 4 * (C / VE), 8192)), dim3(256), 0,
+                                                     (hipStream_t)stream, (const T*)src, src_ld, src_coff, (T*)dst, dst_ld, N, H,
+                                                     W, C);
     });
 }
 
@@ -462,15 +448,14 @@ int pmoe_add_window(const void* src, int32_t src_ld, int32_t src_coff, void* dst
     if (rows < 0 || C < 1 || src_coff + C > src_ld || dst_coff + C > dst_ld) return PMOE_ERR_ARG;
     if (rows == 0) return 0;
     DISPATCH_DT(dtype, {
-        constexpr int VE = 16 / (int)sizeof(T);
-        const bool vec = !(C % VE) && !(src_ld % VE) && !(src_coff % VE) && !(dst_ld % VE) && !(dst_coff % VE);
-        if (vec)
-            hipLaunchKernelGGL((add_window_kernel<T, VE>), dim3(grid_for(rows * (C / VE))), dim3(256), 0, (hipStream_t)stream,
-                               (const T*)src, src_ld, src_coff, (T*)dst, dst_ld, dst_coff, (long long)rows, C);
-        else
-            hipLaunchKernelGGL((add_window_kernel<T, 1>), dim3(grid_for(rows * C)), dim3(256), 0, (hipStream_t)stream,
-                               (const T*)src, src_ld, src_coff, (T*)dst, dst_ld, dst_coff, (long long)rows, C);
-        return (int)hipGetLastError();
+        constexpr int VE = VecOf<T>::N;
+        // whole 16-byte vectors on both sides, or the scalar kernel
+        if (!(C % VE) && window_ok<T>(C, src_ld, src_coff) && window_ok<T>(C, dst_ld, dst_coff))
+            return launch<add_window_kernel<T, VE>, 0>(dim3(grid_for(rows * (C / VE), 8192)), dim3(256), 0, (hipStream_t)stream,
+                                                       (const T*)src, src_ld, src_coff, (T*)dst, dst_ld, dst_coff,
+                                                       (long long)rows, C);
+        return launch<add_window_kernel<T, 1>, 0>(dim3(grid_for(rows * C, 8192)), dim3(256), 0, (hipStream_t)stream, (const T*)src,
+                                                  src_ld, src_coff, (T*)dst, dst_ld, dst_coff, (long long)rows, C);
     });
 }
 
@@ -483,19 +468,16 @@ int pmoe_cat_windows(const void* const* srcs, int32_t K, int32_t c, int32_t src_
     CatSrcs cs;
     for (int k = 0; k < 8; ++k) cs.p[k] = k < K ? srcs[k] : nullptr;       /* srcs is a HOST array of device pointers */
     DISPATCH_DT(dtype, {
-        constexpr int VE = 16 / (int)sizeof(T);
+        constexpr int VE = VecOf<T>::N;
         if (dst_c % VE || dst_ld % VE) return PMOE_ERR_ARG;
         bool aligned = src_ld % VE == 0 && (size_t)CAT_ROWS * dst_c * sizeof(T) <= 48 * 1024;
         for (int k = 0; k < K; ++k) aligned = aligned && ((uintptr_t)srcs[k] & 15) == 0;
-        if (aligned) {
-            hipLaunchKernelGGL((cat_windows_lds_kernel<T>), dim3((unsigned)((rows + CAT_ROWS - 1) / CAT_ROWS)), dim3(256),
-                               (size_t)CAT_ROWS * dst_c * sizeof(T), (hipStream_t)stream, cs, K, c, src_ld, src_coff, (T*)dst,
-                               dst_ld, dst_c, (long long)rows);
-            return (int)hipGetLastError();
-        }
-        hipLaunchKernelGGL((cat_windows_kernel<T>), dim3(grid_for(rows * (dst_c / VE))), dim3(256), 0, (hipStream_t)stream, cs,
-                           K, c, src_ld, src_coff, (T*)dst, dst_ld, dst_c, (long long)rows);
-        return (int)hipGetLastError();
+        if (aligned)
+            return launch<cat_windows_lds_kernel<T>, 0>(dim3((unsigned)((rows + CAT_ROWS - 1) / CAT_ROWS)), dim3(256),
+                                                        (size_t)CAT_ROWS * dst_c * sizeof(T), (hipStream_t)stream, cs, K, c, src_ld,
+                                                        src_coff, (T*)dst, dst_ld, dst_c, (long long)rows);
+        return launch<cat_windows_kernel<T>, 0>(dim3(grid_for(rows * (dst_c / VE), 8192)), dim3(256), 0, (hipStream_t)stream, cs,
+                                                K, c, src_ld, src_coff, (T*)dst, dst_ld, dst_c, (long long)rows);
     });
 }
 
@@ -504,11 +486,9 @@ int pmoe_nhwc_to_nchw(const void* src, int32_t src_ld, int32_t src_coff, float* 
     if (N < 1 || HW < 1 || C < 1 || src_coff + C > src_ld || C > 1024) return PMOE_ERR_ARG;
     const long long nblk = (HW + 63) / 64 * N;
     if (nblk > 0x7fffffffLL) return PMOE_ERR_ARG;
-    DISPATCH_DT(dtype, {
-        hipLaunchKernelGGL((nhwc_to_nchw_kernel<T>), dim3((unsigned)nblk), dim3(256), 64 * (C + 1) * sizeof(float),
-                           (hipStream_t)stream, (const T*)src, src_ld, src_coff, dst, N, (long long)HW, C);
-        return (int)hipGetLastError();
-    });
+    DISPATCH_DT(dtype, return launch<nhwc_to_nchw_kernel<T>, 0>(dim3((unsigned)nblk), dim3(256), 64 * (C + 1) * sizeof(float),
+                                                                (hipStream_t)stream, (const T*)src, src_ld, src_coff, dst, N,
+                                                                (long long)HW, C));
 }
 
 static int seg_cp(int C) { return C <= 8 ? 8 : C <= 16 ? 16 : C <= 24 ? 24 : 32; }
@@ -530,18 +510,15 @@ int pmoe_seg_loss_fwd(const float* logits, const int64_t* target, int32_t B, int
     const int NS = pmoe_seg_loss_rows(B, H, W);
     const int nsplit = NS / xb, CP = seg_cp(C);
     const dim3 grid(xb, nsplit, F);
-#define SEG_STATS(CPV)                                                                                                   \
-    hipLaunchKernelGGL((seg_loss_stats_kernel<CPV>), grid, dim3(256), 0, (hipStream_t)stream, logits,                    \
-                       (const long long*)target, B, F, C, H, W, mode, partT, partG, nsplit)
-    if (CP == 8) SEG_STATS(8);
-    else if (CP == 16) SEG_STATS(16);
-    else if (CP == 24) SEG_STATS(24);
-    else SEG_STATS(32);
+    hipStream_t st = (hipStream_t)stream;
+    const long long* tgt = (const long long*)target;
+#define SEG_STATS(CPV) \
+    launch<seg_loss_stats_kernel<CPV>, 0>(grid, dim3(256), 0, st, logits, tgt, B, F, C, H, W, mode, partT, partG, nsplit)
+    HIP_RET((CP == 8 ? SEG_STATS(8) : CP == 16 ? SEG_STATS(16) : CP == 24 ? SEG_STATS(24) : SEG_STATS(32)));
 #undef SEG_STATS
-    hipLaunchKernelGGL(seg_loss_finalize_kernel, dim3(F), dim3(256), 0, (hipStream_t)stream, partT, partG, B, F, C, CP, H, W,
-                       mode, NS, nsplit, ce_weight, tversky_weight, alpha, beta, coefG, coefT, loss);
-    hipLaunchKernelGGL(seg_loss_total_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, loss, F);
-    return (int)hipGetLastError();
+    HIP_RET((launch<seg_loss_finalize_kernel, 0>(dim3(F), dim3(256), 0, st, partT, partG, B, F, C, CP, H, W, mode, NS, nsplit,
+                                                 ce_weight, tversky_weight, alpha, beta, coefG, coefT, loss)));
+    return launch<seg_loss_total_kernel, 0>(dim3(1), dim3(1), 0, st, loss, F);
 }
 
 int pmoe_seg_loss_bwd(const float* logits, const int64_t* target, const float* coefG, const float* coefT, const float* dloss,
@@ -549,16 +526,13 @@ int pmoe_seg_loss_bwd(const float* logits, const int64_t* target, const float* c
     if (B < 1 || F < 1 || C < 2 || C > 32 || H < 1 || W < 1 || mode < 0 || mode > 2 || !dlogits) return PMOE_ERR_ARG;
     if (mode == 0 && (!coefG || !coefT)) return PMOE_ERR_ARG;
     const int CP = seg_cp(C);
-    const int grid = grid_for((long long)B * F * H * W, 16384);
-#define SEG_BWD(CPV)                                                                                                     \
-    hipLaunchKernelGGL((seg_loss_bwd_kernel<CPV>), dim3(grid), dim3(256), 0, (hipStream_t)stream, logits,                \
-                       (const long long*)target, coefG, coefT, dloss, dlogits, B, F, C, H, W, mode)
-    if (CP == 8) SEG_BWD(8);
-    else if (CP == 16) SEG_BWD(16);
-    else if (CP == 24) SEG_BWD(24);
-    else SEG_BWD(32);
+    const dim3 grid(grid_for((long long)B * F * H * W, 16384));
+    hipStream_t st = (hipStream_t)stream;
+    const long long* tgt = (const long long*)target;
+#define SEG_BWD(CPV) \
+    launch<seg_loss_bwd_kernel<CPV>, 0>(grid, dim3(256), 0, st, logits, tgt, coefG, coefT, dloss, dlogits, B, F, C, H, W, mode)
+    return CP == 8 ? SEG_BWD(8) : CP == 16 ? SEG_BWD(16) : CP == 24 ? SEG_BWD(24) : SEG_BWD(32);
 #undef SEG_BWD
-    return (int)hipGetLastError();
 }
 
 int pmoe_seg_loss_cp(int32_t C) { return (C < 2 || C > 32) ? PMOE_ERR_ARG : seg_cp(C); }

@@ -576,9 +576,11 @@ __global__ void __launch_bounds__(256) stem_tail_dz_walk_kernel(const T* __restr
 
 static inline int walk_enabled() { return sw("PMOE_STEM_WALK", 1) != 0; }
 static inline int walk_ko() { return sw("PMOE_STEM_WALK_KO", 2) == 4 ? 4 : 2; }      // pooled columns per lane group (tools/ab_stem_tail.py: 2 vs 4)
-static inline int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 
-static inline bool pow2i(int v) { return v > 0 && !(v & (v - 1)); }
+// the 12 per-(expert, channel) f32 arrays of an entry point's `consts`, in the order of struct TailConsts (unused ones may be null)
+static inline TailConsts tail_consts(const float* const* c) {
+    return TailConsts{c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8], c[9], c[10], c[11]};
+}
 
 extern "C" {
 
@@ -587,87 +589,72 @@ int pmoe_stem_tail_stats(const void* z2, const float* sc2, const float* sh2, con
                          int32_t C, int32_t dtype, void* stream) {
     TailConsts k{};
     k.sc2 = sc2; k.sh2 = sh2; k.mu2 = mu2;
-    const int ve = dtype == PMOE_DT_BF16 ? 8 : 4;
-    if (C % ve || !pow2i(C / ve) || C / ve > 256 || nparts < 1) return PMOE_ERR_ARG;
-    if (dtype == PMOE_DT_BF16)
-        hipLaunchKernelGGL((stem_tail_kernel<bf16, 0>), dim3(nparts, E), dim3(256), 0, (hipStream_t)stream, (const bf16*)z2,
-                           nullptr, nullptr, nullptr, k, part, nparts, ipe, H, W, C, shiftc, part_x);
-    else if (dtype == PMOE_DT_F32)
-        hipLaunchKernelGGL((stem_tail_kernel<float, 0>), dim3(nparts, E), dim3(256), 0, (hipStream_t)stream,
-                           (const float*)z2, nullptr, nullptr, nullptr, k, part, nparts, ipe, H, W, C, shiftc, part_x);
-    else
-        return PMOE_ERR_ARG;
-    return (int)hipGetLastError();
+    DISPATCH_DT(dtype, {
+        if (!one_vec_per_thread<T>(C) || nparts < 1) return PMOE_ERR_ARG;
+        return launch<stem_tail_kernel<T, 0>, 0>(dim3(nparts, E), dim3(256), 0, (hipStream_t)stream, (const T*)z2, nullptr, nullptr,
+                                                 nullptr, k, part, nparts, ipe, H, W, C, shiftc, part_x);
+    });
 }
 
 int pmoe_stem_tail_pool(const void* z2, void* y, uint8_t* argmax, const float* sc2, const float* sh2, const float* sc1,
                         const float* sh1, const float* mu2, const float* mu1, int32_t N, int32_t ipe, int32_t H, int32_t W, int32_t C, int32_t dtype,
                         void* stream) {
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-    const int ve = dtype == PMOE_DT_BF16 ? 8 : 4;
-    if (C % ve || N % ipe || !pow2i(C / ve) || C / ve > 256) return PMOE_ERR_ARG;   // one channel vector per thread
-    if (walk_enabled() && dtype == PMOE_DT_BF16) {            // (f32 is the parity mode: gather kernel)
-        const int KO = walk_ko(), SR = 8;
-        const int G = (Wo + KO - 1) / KO, NS = (Ho + SR - 1) / SR, lcv = ilog2(C / ve);
-        const long long groups = (long long)N * NS * G, wgs = (groups * (C / ve) + 255) / 256;
-        if (wgs > 0x7fffffffll) return PMOE_ERR_ARG;
-#define POOL_WALK(K)                                                                                                        \
-        hipLaunchKernelGGL((stem_tail_pool_walk_kernel<K>), dim3((int)wgs), dim3(256), 0, (hipStream_t)stream, (const bf16*)z2, \
-                           (bf16*)y, argmax, sc2, sh2, sc1, sh1, mu2, mu1, N, ipe, H, W, C, Ho, Wo, G, NS, SR, lcv)
-        if (KO == 4) POOL_WALK(4); else POOL_WALK(2);
-#undef POOL_WALK
-        return (int)hipGetLastError();
-    }
-    long long g = ((long long)N * Ho * Wo * (C / ve) + 255) / 256;
-    if (g > 16384) g = 16384;
-    if (dtype == PMOE_DT_BF16)
-        hipLaunchKernelGGL((stem_tail_pool_kernel<bf16>), dim3((int)g), dim3(256), 0, (hipStream_t)stream, (const bf16*)z2,
-                           (bf16*)y, argmax, sc2, sh2, sc1, sh1, mu2, mu1, N, ipe, H, W, C, Ho, Wo);
-    else if (dtype == PMOE_DT_F32)
-        hipLaunchKernelGGL((stem_tail_pool_kernel<float>), dim3((int)g), dim3(256), 0, (hipStream_t)stream,
-                           (const float*)z2, (float*)y, argmax, sc2, sh2, sc1, sh1, mu2, mu1, N, ipe, H, W, C, Ho, Wo);
-    else
-        return PMOE_ERR_ARG;
-    return (int)hipGetLastError();
+    hipStream_t st = (hipStream_t)stream;
+    DISPATCH_DT(dtype, {
+        if (!one_vec_per_thread<T>(C) || N % ipe) return PMOE_ERR_ARG;
+        const int CV = C / VecOf<T>::N;
+        if (walk_enabled() && dtype == PMOE_DT_BF16) {            // (f32 is the parity mode: gather kernel)
+            const int KO = walk_ko(), SR = 8;
+            const int G = (Wo + KO - 1) / KO, NS = (Ho + SR - 1) / SR, lcv = ilog2_exact(CV);
+            const long long groups = (long long)N * NS * G, wgs = (groups * CV + 255) / 256;
+            if (wgs > 0x7fffffffll) return PMOE_ERR_ARG;
+            const bf16* z = (const bf16*)z2;
+            if (KO == 4)
+                return launch<stem_tail_pool_walk_kernel<4>, 0>(dim3((int)wgs), dim3(256), 0, st, z, (bf16*)y, argmax, sc2, sh2,
+                                                                sc1, sh1, mu2, mu1, N, ipe, H, W, C, Ho, Wo, G, NS, SR, lcv);
+            return launch<stem_tail_pool_walk_kernel<2>, 0>(dim3((int)wgs), dim3(256), 0, st, z, (bf16*)y, argmax, sc2, sh2, sc1,
+                                                            sh1, mu2, mu1, N, ipe, H, W, C, Ho, Wo, G, NS, SR, lcv);
+        }
+        return launch<stem_tail_pool_kernel<T>, 0>(dim3(grid_for((long long)N * Ho * Wo * CV, 16384)), dim3(256), 0, st,
+                                                   (const T*)z2, (T*)y, argmax, sc2, sh2, sc1, sh1, mu2, mu1, N, ipe, H, W, C, Ho,
+                                                   Wo);
+    });
 }
 
-/* phase 1: part = (sum g3, sum g3*xhat1); phase 2: (sum g2, sum g2*xhat2); phase 3: writes dz2.
- * consts: 12 per-(expert,channel) f32 arrays in the order of struct TailConsts (unused ones may be null). */
+/* phase 1: part = (sum g3, sum g3*xhat1); phase 2: (sum g2, sum g2*xhat2); phase 3: writes dz2. */
 int pmoe_stem_tail_bwd(int32_t phase, const void* z2, const void* dpool, const uint8_t* argmax, void* dz2,
                        const float* const* consts, float* part, int32_t nparts, int32_t E, int32_t ipe, int32_t H,
                        int32_t W, int32_t C, int32_t dtype, void* stream) {
-    TailConsts k{consts[0], consts[1], consts[2], consts[3], consts[4], consts[5],
-                 consts[6], consts[7], consts[8], consts[9], consts[10], consts[11]};
-    const int ve = dtype == PMOE_DT_BF16 ? 8 : 4;
-    if (C % ve || !pow2i(C / ve) || C / ve > 256 || nparts < 1 || phase < 1 || phase > 3) return PMOE_ERR_ARG;
-    dim3 grid(nparts, E), block(256);
+    const TailConsts k = tail_consts(consts);
     hipStream_t st = (hipStream_t)stream;
-    if (phase == 3 && walk_enabled()) {
-        const int KO = walk_ko(), SR = 16;
-        const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1, N = E * ipe;
-        const int G = (W + 2 * KO - 1) / (2 * KO), NS = (H + SR - 1) / SR, lcv = ilog2(C / ve);
-        const long long groups = (long long)N * NS * G, wgs = (groups * (C / ve) + 255) / 256;
-        if (wgs > 0x7fffffffll || (dtype != PMOE_DT_BF16 && dtype != PMOE_DT_F32)) return PMOE_ERR_ARG;
-#define DZ_WALK(TT, K)                                                                                                       \
-        hipLaunchKernelGGL((stem_tail_dz_walk_kernel<TT, K>), dim3((int)wgs), block, 0, st, (const TT*)z2, (const TT*)dpool, argmax, \
-                           (TT*)dz2, k, N, ipe, H, W, C, Ho, Wo, G, NS, SR, lcv)
-        if (dtype == PMOE_DT_BF16) { if (KO == 4) DZ_WALK(bf16, 4); else DZ_WALK(bf16, 2); }
-        else { if (KO == 4) DZ_WALK(float, 4); else DZ_WALK(float, 2); }
-#undef DZ_WALK
-        return (int)hipGetLastError();
-    }
-#define TAIL_LAUNCH(TT, M)                                                                                           \
-    hipLaunchKernelGGL((stem_tail_kernel<TT, M>), grid, block, 0, st, (const TT*)z2, (const TT*)dpool, argmax, (TT*)dz2, k, \
-                       part, nparts, ipe, H, W, C, nullptr, nullptr)
-    if (dtype == PMOE_DT_BF16) {
-        if (phase == 1) TAIL_LAUNCH(bf16, 1); else if (phase == 2) TAIL_LAUNCH(bf16, 2); else TAIL_LAUNCH(bf16, 3);
-    } else if (dtype == PMOE_DT_F32) {
-        if (phase == 1) TAIL_LAUNCH(float, 1); else if (phase == 2) TAIL_LAUNCH(float, 2); else TAIL_LAUNCH(float, 3);
-    } else {
-        return PMOE_ERR_ARG;
-    }
-#undef TAIL_LAUNCH
-    return (int)hipGetLastError();
+    DISPATCH_DT(dtype, {
+        if (!one_vec_per_thread<T>(C) || nparts < 1 || phase < 1 || phase > 3) return PMOE_ERR_ARG;
+        const T* z = (const T*)z2;
+        const T* dp = (const T*)dpool;
+        T* dz = (T*)dz2;
+        if (phase == 3 && walk_enabled()) {
+            const int KO = walk_ko(), SR = 16, CV = C / VecOf<T>::N;
+            const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1, N = E * ipe;
+            const int G = (W + 2 * KO - 1) / (2 * KO), NS = (H + SR - 1) / SR, lcv = ilog2_exact(CV);
+            const long long groups = (long long)N * NS * G, wgs = (groups * CV + 255) / 256;
+            if (wgs > 0x7fffffffll) return PMOE_ERR_ARG;
+            if (KO == 4)
+                return launch<stem_tail_dz_walk_kernel<T, 4>, 0>(dim3((int)wgs), dim3(256), 0, st, z, dp, argmax, dz, k, N, ipe,
+                        H, W, C, Ho, Wo, G, NS, SR, lcv);
+            return launch<stem_tail_dz_walk_kernel<T, 2>, 0>(dim3((int)wgs), dim3(256), 0, st, z, dp, argmax, dz, k, N, ipe, H, W,
+                                                             C, Ho, Wo, G, NS, SR, lcv);
+        }
+        const dim3 grid(nparts, E), block(256);
+        if (phase == 1)
+            return launch<stem_tail_kernel<T, 1>, 0>(grid, block, 0, st, z, dp, argmax, dz, k, part, nparts, ipe, H, W, C,
+                                                     nullptr, nullptr);
+        if (phase == 2)
+            return launch<stem_tail_kernel<T, 2>, 0>(grid, block, 0, st, z, dp, argmax, dz, k, part, nparts, ipe, H, W, C,
+                                                     nullptr, nullptr);
+        return launch<stem_tail_kernel<T, 3>, 0>(grid, block, 0, st, z, dp, argmax, dz, k, part, nparts, ipe, H, W, C, nullptr,
+                                                 nullptr);
+    });
 }
 
 /* train-mode replacement of phases 1 and 2: pooled pass (part4 [E][nparts][4][C]) and the closed-form combine
@@ -675,29 +662,20 @@ int pmoe_stem_tail_bwd(int32_t phase, const void* z2, const void* dpool, const u
  * consts as in pmoe_stem_tail_bwd (entries 0..7 used); part_x [E][npx][3][C] from pmoe_stem_tail_stats. */
 int pmoe_stem_tail_pooled(const void* y, const void* dpool, const uint8_t* argmax, const float* const* consts, float* part4,
                           int32_t nparts, int32_t E, int64_t rows_per_expert, int32_t C, int32_t dtype, void* stream) {
-    TailConsts k{consts[0], consts[1], consts[2], consts[3], consts[4], consts[5],
-                 consts[6], consts[7], consts[8], consts[9], consts[10], consts[11]};
-    const int ve = dtype == PMOE_DT_BF16 ? 8 : 4;
-    if (C % ve || !pow2i(C / ve) || C / ve > 256 || nparts < 1 || rows_per_expert < 1) return PMOE_ERR_ARG;
-    if (dtype == PMOE_DT_BF16)
-        hipLaunchKernelGGL((stem_tail_pooled_kernel<bf16>), dim3(nparts, E), dim3(256), 0, (hipStream_t)stream, (const bf16*)y,
-                           (const bf16*)dpool, argmax, k, part4, nparts, (long long)rows_per_expert, C);
-    else if (dtype == PMOE_DT_F32)
-        hipLaunchKernelGGL((stem_tail_pooled_kernel<float>), dim3(nparts, E), dim3(256), 0, (hipStream_t)stream,
-                           (const float*)y, (const float*)dpool, argmax, k, part4, nparts, (long long)rows_per_expert, C);
-    else
-        return PMOE_ERR_ARG;
-    return (int)hipGetLastError();
+    const TailConsts k = tail_consts(consts);
+    DISPATCH_DT(dtype, {
+        if (!one_vec_per_thread<T>(C) || nparts < 1 || rows_per_expert < 1) return PMOE_ERR_ARG;
+        return launch<stem_tail_pooled_kernel<T>, 0>(dim3(nparts, E), dim3(256), 0, (hipStream_t)stream, (const T*)y,
+                                                     (const T*)dpool, argmax, k, part4, nparts, (long long)rows_per_expert, C);
+    });
 }
 
 int pmoe_stem_tail_combine(const float* part4, int32_t np4, const float* part_x, int32_t npx, const float* const* consts,
                            int64_t count, float* out1, float* out2, int32_t E, int32_t C, void* stream) {
-    TailConsts k{consts[0], consts[1], consts[2], consts[3], consts[4], consts[5],
-                 consts[6], consts[7], consts[8], consts[9], consts[10], consts[11]};
+    const TailConsts k = tail_consts(consts);
     if (np4 < 1 || npx < 1 || count < 1) return PMOE_ERR_ARG;
-    hipLaunchKernelGGL(stem_tail_combine_kernel, dim3(E), dim3(256), 0, (hipStream_t)stream, part4, np4, part_x, npx, k,
-                       (float)count, out1, out2, C);
-    return (int)hipGetLastError();
+    return launch<stem_tail_combine_kernel, 0>(dim3(E), dim3(256), 0, (hipStream_t)stream, part4, np4, part_x, npx, k, (float)count,
+                                               out1, out2, C);
 }
 
 }  // extern "C"

@@ -369,6 +369,19 @@ def test_switch_table_is_what_the_sources_read():
     assert not unnamed, unnamed
 
 
+def test_one_launch_call_dtype_dispatch_and_grid_rule():
+    """The host side of an entry point has one definition of each step (csrc/common.h): the launch and its error code, the dtype
+    dispatch, the grid rule of the grid-stride kernels."""
+    csrc = REPO / "pmoe_amd" / "csrc"
+    sources = {f.name: f.read_text() for f in sorted(csrc.glob("*.hip")) + sorted(csrc.glob("*.h")) + sorted(csrc.glob("*.inc"))}
+    assert len(sources) > 17
+    for word in ("hipLaunchKernelGGL", "hipGetLastError"):
+        assert [name for name, text in sources.items() if word in text] == ["common.h"], word
+    for definition in (r"#\s*define\s+DISPATCH_DT\b", r"\bgrid_for\w*\s*\([^;{}]*\)\s*\{"):
+        found = [name for name, text in sources.items() for _ in re.findall(definition, text, flags=re.M)]
+        assert found == ["common.h"], (definition, found)
+
+
 def _option_table():
     """the attribute names in the table of DESIGN.md's section "Options of the Python engines" """
     text = (REPO / "DESIGN.md").read_text()
