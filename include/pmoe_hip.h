@@ -687,6 +687,22 @@ int pmoe_augment_blur_h(const uint8_t* src, uint8_t* dst, const pmoe_aug_plan* p
 int pmoe_augment_blur_v(const uint8_t* src, uint8_t* dst, const pmoe_aug_plan* plan, int32_t n_img, int32_t h, int32_t w,
                         void* stream);
 
+/* ---- device-resident dataset (pmoe_amd/data.py; the reference's loaders: model/data_loader.py CarlaSeg / CarlaSegPred).
+ * The Resize output of every frame is kept in device memory as uint8 rows; a batch is an int64 index table `idx` (device
+ * memory, n entries) plus a gather.  Every byte offset is 64-bit.  An index outside [0, n_src) reads nothing and its row is
+ * written as zeros (the Python side checks its tables on the host and never sends one).  No atomics, no host synchronisation.
+ * PMOE_ERR_ARG before any launch: a null pointer, n < 1, n_src < 1, an extent < 1, dst == src. */
+/* dst[i] = src[idx[i]], rows of row_bytes bytes (uint8 NHWC frames, f32 measurement rows): 16-byte lanes when both bases and
+ * row_bytes are 16-byte aligned, 4-byte lanes when they are 4-byte aligned, bytes otherwise */
+int pmoe_gather_rows(const void* src, const int64_t* idx, void* dst, int64_t n_src, int64_t n, int64_t row_bytes, void* stream);
+/* store uint8 [n_src][h][w][C] -> dst f32 [n][C][h][w] = value / 255 (ToTensor): the bits pmoe_resample_u8_vertical_to_f32
+ * writes for the same 8-bit value.  h * w <= 2^28. */
+int pmoe_gather_frames_to_f32(const uint8_t* store, const int64_t* idx, float* dst_nchw, int64_t n_src, int32_t n, int32_t h,
+                              int32_t w, int32_t C, void* stream);
+/* store uint8 [n_src][hw] -> dst int64 [n][hw] (MaskPILToTensor) */
+int pmoe_gather_labels_to_i64(const uint8_t* store, const int64_t* idx, int64_t* dst, int64_t n_src, int32_t n, int64_t hw,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -98,7 +98,19 @@ class FramePreprocessor:
         out = self._run(masks.unsqueeze(-1), labels=True)
         return out.squeeze(-3)
 
-    def _run(self, frames, labels, augment=None):
+    def resized(self, frames):
+        """``Resize(Crop(frame))`` itself: uint8 device frames ``[..., H0, W0, C]`` -> uint8 ``[..., h, w, C]`` (NHWC), the 8-bit
+        image that ``__call__`` divides by 255 and that the augmenter reads.  It is a pure function of the frame, so a dataset
+        computes it once per frame and keeps it (``pmoe_amd.data.FrameStore``)."""
+        if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8:
+            raise TypeError("FramePreprocessor.resized: expected a uint8 tensor [..., H0, W0, C]")
+        if not frames.is_cuda:
+            raise RuntimeError("FramePreprocessor: frames must be on the MI355X (cuda) device; pmoe_amd has no CPU path")
+        if frames.dim() < 3:
+            raise ValueError("FramePreprocessor.resized: expected [..., H0, W0, C]")
+        return self._run(frames, labels=False, u8=True)
+
+    def _run(self, frames, labels, augment=None, u8=False):
         lead = frames.shape[:-3]
         H0, W0, Cc = frames.shape[-3:]
         rows = H0 - self.top - self.bottom
@@ -115,14 +127,17 @@ class FramePreprocessor:
             from .augment import run_plan
             aug, generator, plan = augment
             plan = aug._plan_for(n, h, w, generator, plan)
-        out = torch.empty(n, Cc, h, w, dtype=torch.int64 if labels else torch.float32, device=dev)
+        if not u8:
+            out = torch.empty(n, Cc, h, w, dtype=torch.int64 if labels else torch.float32, device=dev)
         p = lambda t: C.c_void_p(t.data_ptr())      # noqa: E731
         check(load().pmoe_resample_u8_horizontal(p(src), p(tmp), n, H0, W0, self.top, rows, Cc, w, p(bh), p(ch), kh,
                                                  stream_ptr()), "pmoe_resample_u8_horizontal")
-        if augment is not None:                     # Resize output as uint8 NHWC -> augmenter -> ToTensor in its last launch
+        if augment is not None or u8:               # Resize output as uint8 NHWC -> augmenter -> ToTensor in its last launch
             res = torch.empty(n, h, w, Cc, dtype=torch.uint8, device=dev)
             check(load().pmoe_resample_u8_vertical_to_u8(p(tmp), p(res), n, rows, w, Cc, h, p(bv), p(cv), kv, stream_ptr()),
                   "pmoe_resample_u8_vertical_to_u8")
+            if u8:
+                return res.view(*lead, h, w, Cc)
             run_plan(res, plan, out)
             return out.view(*lead, Cc, h, w)
         vert = load().pmoe_resample_u8_vertical_to_i64 if labels else load().pmoe_resample_u8_vertical_to_f32
