@@ -143,6 +143,22 @@ int pmoe_conv2d_stat_rows(const pmoe_conv_desc* d);
  * A stride-2 1x1 data gradient accumulated in place (dilate, PMOE_RES_ADD with res == out) is ONE class-(0,0) launch: the
  * code of its tile, without the 4000.  One selection (conv_select) decides this code, the launch and pmoe_conv2d_stat_rows.
  *
+ * ORDER OF ROUNDINGS of a bf16 output, per kernel family (tests/conv_ref.py ROUNDING holds it per code, tests/test_conv_gpu.py
+ * asserts it element for element).  Bias always joins the accumulator in f32; a mask (PMOE_RES_DRELU, PMOE_RES_DBN) and a ReLU
+ * give the same value on either side of a rounding; the statistics are sums of the STORED values.  What differs is PMOE_RES_ADD:
+ *   conv_igemm_kernel / conv_igemm_lite_kernel, also as parity-class launches:  out = bf16(act(acc + bias + res)).
+ *   conv3x3_res_kernel / conv3x3_resdma_kernel / conv3x3_respipe_kernel:  out = bf16(bf16(acc) + res) -- the accumulator is
+ *     staged as bf16 before the residual is added (they take no bias with PMOE_RES_ADD).
+ *   conv3x3_dma_kernel (5007 | 5017):  out = bf16(bf16(acc) + res) for a launch without bias / activation / dropout (the one-phase
+ *     read-out, residual prefetched: the data gradients that accumulate onto an existing gradient); with one of them,
+ *     out = bf16(act(acc + bias + res)).
+ *   conv3x3s2_dma_kernel (5207 | 9207):  out = bf16(act(acc + bias + res)).
+ *   The producer-wave / persistent LDS-DMA kernels, conv3x3_c16_kernel and conv1x1_direct_kernel take no side input.
+ * So the A/B partners of a switch are bit-identical for every launch but a bare PMOE_RES_ADD on 64-channel-chunk 3x3 stride-1 layers
+ * of >= 128 output channels: PMOE_CONV_DMA=0 moves those from the staged order (5007 | 5017) to the single rounding of
+ * conv_igemm_lite_kernel (2007): up to one bf16 ulp of the larger operand apart.  PMOE_RES_DMA / PMOE_RES_PIPE (1007 | 1107 | 1227)
+ * and PMOE_DMA_NARROW (5067 | 741: plain launches) switch between kernels of one order.
+ *
  * What a non-negative plan means for the FUSED REQUESTS.  A descriptor that sets res_mode to PMOE_RES_INBN or PMOE_RES_DBN, or
  * sets shuffle_c or in_fp8 (a weight-gradient descriptor: bn_fused), is run by a kernel that implements everything it asks for;
  * where no such kernel serves it, pmoe_conv2d_plan, pmoe_conv2d_stat_rows and pmoe_conv2d_igemm (pmoe_conv2d_wgrad_plan,

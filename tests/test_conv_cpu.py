@@ -1,0 +1,417 @@
+"""The float64 convolution reference (tests/conv_ref.py) checked against float64 torch.autograd of F.conv2d / F.conv_transpose2d /
+F.batch_norm, its input generators checked for everything tests/test_conv_gpu.py assumes of them, and the case table checked
+against the planners: every case plans to the codes it names, and every code the planners can answer over a grid of shapes,
+requests and switches is in the table or on its short exclusion list.  No GPU: pmoe_conv2d_plan and pmoe_conv2d_wgrad_plan are
+host code."""
+import ctypes as C
+import itertools
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+from pmoe_amd import hip, ops
+from tests import bn_ref
+from tests import conv_ref as R
+from tests.stem_tail_ref import bf16_boundary_distance
+
+F64, F32, BF16 = R.F64, R.F32, R.BF16
+IDS = [R.case_id(c) for c in R.CASES]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# a launch of conv_ref.launches as ops sees it (tests/test_conv_gpu.py runs the same objects)
+
+def conv_tensors(L, device):
+    """the tensors of a conv launch in their storage types: on ``device``, or -- device "meta" -- shapes and types only"""
+    kw = L["kw"]
+    dtype, E, ks = kw["dtype"], L["w"].shape[0], kw["ks"]
+    coutp = R.r64(kw["cout"])
+    if device == "meta":
+        mk = lambda t, dt: None if t is None else torch.empty(t.shape, dtype=dt, device="meta")
+        wp = torch.empty(E, coutp, ks * ks, kw["cin"], dtype=dtype, device="meta")
+        bias = None if L["bias"] is None else torch.empty(E, coutp, dtype=F32, device="meta")
+    else:
+        mk = lambda t, dt: None if t is None else t.to(dt).to(device).contiguous()
+        wp = mk(R.pack_weights(L["w"], coutp, kw["cin"], dtype), dtype)
+        bias = None
+        if L["bias"] is not None:
+            bias = torch.zeros(E, coutp, dtype=F32)
+            bias[:, :kw["cout"]] = L["bias"].to(F32)
+            bias = bias.to(device)
+    t = {"x": mk(L["inp"], dtype), "w": wp, "out": mk(L["out_init"], dtype), "bias": bias, "bn_coef": mk(L["bn_coef"], F32)}
+    t["res"] = t["out"] if L["res_is_out"] else mk(L["res"], dtype)
+    return t
+
+
+def conv_prepare(L, t, stats=None):
+    """ops.conv2d_prepare of the launch on the tensors ``t``"""
+    kw = L["kw"]
+    return ops.conv2d_prepare(
+        t["x"], t["w"], t["out"], cin=kw["cin"], cout=kw["cout"], coutp=R.r64(kw["cout"]), ipe=kw["ipe"], ks=kw["ks"],
+        stride=kw["stride"], pad=kw["pad"], dilate=kw.get("dilate", False), in_shared=kw.get("in_shared", False),
+        in_coff=kw["in_coff"], out_coff=kw["out_coff"], res=t["res"], res_coff=kw.get("res_coff", 0),
+        res_mode=kw.get("res_mode", hip.RES_NONE), bias=t["bias"], act=kw.get("act", hip.ACT_NONE),
+        stats=(True if stats is None else stats) if kw["stats"] else None, bn_coef=t["bn_coef"], bn_ipe=kw.get("bn_ipe", 0),
+        shuffle2_c=kw.get("shuffle_c", 0), shapes_only=t["x"].device.type == "meta")
+
+
+def wgrad_desc(L):
+    """the pmoe_wgrad_desc of a weight-gradient launch, pointers null: what the planning calls read"""
+    kw = L["kw"]
+    n, ho, wo, dy_ld = L["dy"].shape
+    _, h, w_, x_ld = L["x"].shape
+    return ops._wgrad_desc(n, h, w_, ho, wo, kw["cin"], kw["cout"], kw["cinp"], kw["coutp"], kw["ipe"], kw["ks"], kw["stride"],
+                           kw["pad"], hip._TORCH_DT[kw["dtype"]], x_ld=x_ld, dy_ld=dy_ld, x_coff=kw["x_coff"], dy_coff=kw["dy_coff"],
+                           x_shared=kw["x_shared"], per_image=kw["per_image"], bn_z_ld=None if L["bn"] is None else L["bn"][0].shape[-1])
+
+
+def wgrad_plan(L):
+    """(plan code, K-split count)"""
+    d = wgrad_desc(L)
+    code = hip.load().pmoe_conv2d_wgrad_plan(C.byref(d))
+    return code, (ops._wgrad_ws(d)[1] if code >= 0 else 0)
+
+
+def set_switches(monkeypatch, case):
+    for k, v in case.switches:
+        monkeypatch.setenv(k, v)
+
+
+def planned_codes(case, kind="unit"):
+    ls = R.launches(case, kind)
+    conv = lambda k: conv_prepare(ls[k], conv_tensors(ls[k], "meta")).plan() if k in ls else None
+    return conv("f"), conv("d"), wgrad_plan(ls["w"])[0] if "w" in ls else None
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# routing and coverage
+
+@pytest.mark.parametrize("case", R.CASES, ids=IDS)
+def test_case_plans_to_the_codes_it_names(case, monkeypatch):
+    set_switches(monkeypatch, case)
+    assert planned_codes(case) == case.codes
+
+
+CHANNELS = (16, 32, 48, 64, 128, 192, 256, 512)
+SIDES = (4, 7, 8, 16, 32, 64, 128)
+IPES = (1, 2, 5)
+# every switch conv_select / wgrad_select read per launch (csrc: sw("PMOE_...")), at the value that turns its kernel off; the
+# tri-state ones also at their "always" value
+CONV_SWITCHES = (None, ("PMOE_CONV_C16", "0"), ("PMOE_RES_DMA", "0"), ("PMOE_RES_PIPE", "0"), ("PMOE_CONV_C1X1", "0"),
+                 ("PMOE_CONV_DMA", "0"), ("PMOE_DMA_STREAM", "0"), ("PMOE_DMA_STREAM", "2"), ("PMOE_DMA_PRODUCER", "0"),
+                 ("PMOE_DMA_PRODUCER", "2"), ("PMOE_DMA_NARROW", "0"), ("PMOE_DMA_MF16", "0"), ("PMOE_DMA_MF16", "1"))
+WGRAD_SWITCHES = (None, ("PMOE_WGRAD_DMA", "0"), ("PMOE_WGRAD_NARROW", "0"), ("PMOE_WGRAD_V2", "0"), ("PMOE_WGRAD_REQ", "0"),
+                  ("PMOE_WGRAD_REQ", "2"), ("PMOE_WGRAD_PIPE", "0"))
+# request -> (keywords of ops._planning_desc, the launch is a data gradient, res == out)
+REQUESTS = {
+    "plain": ({}, False), "bias": (dict(bias=True), False), "stats": (dict(stats=True), False),
+    "bias+relu": (dict(bias=True, act=hip.ACT_RELU), False), "add": (dict(res_mode=hip.RES_ADD), False),
+    "add+stats": (dict(res_mode=hip.RES_ADD, stats=True), False), "drelu": (dict(res_mode=hip.RES_DRELU), False),
+    "dbn": (dict(res_mode=hip.RES_DBN, stats=True), False), "dbn+bias": (dict(res_mode=hip.RES_DBN, stats=True, bias=True), False),
+    "inbn": (dict(res_mode=hip.RES_INBN), False), "inbn+stats": (dict(res_mode=hip.RES_INBN, stats=True), False),
+    "inbn+bias": (dict(res_mode=hip.RES_INBN, bias=True), False), "shared": (dict(in_shared=True), False),
+    "shuffle": ("shuffle", False), "shuffle+inbn": ("shuffle+inbn", False),
+    "dgrad": ({}, True), "dgrad+bias": (dict(bias=True), True), "dgrad+add": (dict(res_mode=hip.RES_ADD), True),
+    "dgrad+addin": (dict(res_mode=hip.RES_ADD), True), "dgrad+drelu": (dict(res_mode=hip.RES_DRELU), True),
+    "dgrad+dbn": (dict(res_mode=hip.RES_DBN, stats=True), True), "dgrad+dbn+bias": (dict(res_mode=hip.RES_DBN, stats=True, bias=True), True),
+}
+
+
+# the single-form requests of the grid -> the flag of conv_ref.CASES that runs the form.  A data gradient is the same kernel under
+# another descriptor, so a (code, dtype, form) counts as run whichever of a case's two conv launches carries it.
+FORM_OF = {"bias": "bias", "dgrad+bias": "bias", "bias+relu": "relu", "add": "add", "dgrad+add": "add", "dgrad+addin": "addin",
+           "drelu": "drelu", "dgrad+drelu": "drelu", "shared": "shared", "stats": "stats"}
+
+
+def _grid_plan(lib, E, ipe, cin, cout, side, ks, stride, dtype, name):
+    kw, dgrad = REQUESTS[name]
+    pad, N = ks // 2, E * ipe
+    so = ops.conv_out_size(side, ks, stride, pad)
+    if isinstance(kw, str):
+        if cout % 32:
+            return None
+        kw = dict(shuffle2_c=cout // 4, **(dict(res_mode=hip.RES_INBN) if "inbn" in kw else {}))
+    if not dgrad:
+        d = ops._planning_desc(N, side, side, so, so, cin, cout, R.r64(cout), ipe, ks, stride, pad, dtype, **kw)
+    else:
+        d = ops._planning_desc(N, so, so, side, side, cout, cin, R.r64(cin), ipe, ks, 1, ks - 1 - pad, dtype, dilate=stride == 2, **kw)
+        if name == "dgrad+addin":
+            d.res = d.out
+    return lib.pmoe_conv2d_plan(C.byref(d))
+
+
+def test_every_plan_code_of_the_grid_has_a_case(monkeypatch):
+    """plans only: channels x sides x images per expert x filter x stride x dtype x request x per-launch switch"""
+    lib = hip.load()
+    seen, accepted = {"conv": set(), "wgrad": set()}, set()
+    for sw in CONV_SWITCHES:
+        with monkeypatch.context() as m:
+            if sw:
+                m.setenv(*sw)
+            for dtype, cin, cout, side, ipe, ks, stride in itertools.product((torch.bfloat16, torch.float32), CHANNELS, CHANNELS,
+                                                                             SIDES, IPES, (1, 3), (1, 2)):
+                for name in REQUESTS:
+                    code = _grid_plan(lib, 2, ipe, cin, cout, side, ks, stride, dtype, name)
+                    if code is not None and code >= 0:
+                        seen["conv"].add(code)
+                        if name in FORM_OF and not R.is_excluded(code):
+                            accepted.add((code, dtype, FORM_OF[name]))
+    for sw in WGRAD_SWITCHES:
+        with monkeypatch.context() as m:
+            if sw:
+                m.setenv(*sw)
+            for dtype, cin, cout, side, ipe, ks, stride in itertools.product((torch.bfloat16, torch.float32), CHANNELS, CHANNELS,
+                                                                             SIDES, IPES, (1, 3), (1, 2)):
+                ckw = 64 if dtype == torch.bfloat16 else 32
+                so = ops.conv_out_size(side, ks, stride, ks // 2)
+                for per_image, bn in ((False, False), (True, False), (True, True)):
+                    d = ops._wgrad_desc(2 * ipe, side, side, so, so, cin, cout, (cin + ckw - 1) // ckw * ckw, (cout + ckw - 1) // ckw * ckw,
+                                        ipe, ks, stride, ks // 2, hip._TORCH_DT[dtype], per_image=per_image, bn_z_ld=0 if bn else None)
+                    code = lib.pmoe_conv2d_wgrad_plan(C.byref(d))
+                    if code >= 0:
+                        seen["wgrad"].add(code)
+    covered = {"conv": {c for case in R.CASES for c in case.codes[:2] if c is not None},
+               "wgrad": {case.codes[2] for case in R.CASES if case.codes[2] is not None}}
+    excluded = R.is_excluded
+    assert sorted(R.EXCLUDED) == [3000, 8000], "the exclusion list is the skinny GEMM and the e4m3 codes, nothing else"
+    for k in seen:
+        missing = sorted(c for c in seen[k] - covered[k] if not excluded(c))
+        assert not missing, f"{k} plan codes without a case: {missing}"
+        print(k, "codes seen:", sorted(seen[k]), "excluded:", sorted(c for c in seen[k] if excluded(c)))
+    # the table names nothing the grid does not know (a stale code would be a case that runs on something else)
+    assert covered["conv"] <= seen["conv"] and covered["wgrad"] <= seen["wgrad"]
+    assert covered["conv"] <= set(R.ROUNDING), sorted(covered["conv"] - set(R.ROUNDING))
+    # every form on every code (and dtype) whose planner accepts it, and channel windows on every code
+    ran, windowed = set(), set()
+    for case in R.CASES:
+        fl = R.flags(case)
+        for i, k in enumerate("fd"):
+            if fl[k] is not None:
+                ran |= {(case.codes[i], case.dtype, form) for form in fl[k]}
+                if "win" in fl[k]:
+                    windowed.add(case.codes[i])
+    missing = sorted((c, str(d), f) for c, d, f in accepted - ran)
+    assert not missing, f"(code, dtype, form) accepted by the planner and run by no case: {missing}"
+    unwindowed = sorted(c for c in covered["conv"] - windowed if not excluded(c))
+    assert not unwindowed, f"plan codes no case runs on channel windows: {unwindowed}"
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# generator properties
+
+def _representable(t, dtype):
+    return torch.equal(t.to(dtype).to(F64)[~torch.isnan(t)], t[~torch.isnan(t)])
+
+
+@pytest.mark.parametrize("kind", R.KINDS)
+@pytest.mark.parametrize("case", R.CASES, ids=IDS)
+def test_generator_properties(case, kind):
+    ls = R.launches(case, kind)
+    dtype = case.dtype
+    for k in ("f", "d"):
+        if k not in ls:
+            continue
+        L = ls[k]
+        kw = L["kw"]
+        for name in ("inp", "w", "out_init", "res"):
+            assert L[name] is None or _representable(L[name], dtype), (k, name)
+        for name in ("bias", "bn_coef"):
+            assert L[name] is None or _representable(L[name], F32), (k, name)
+        bound = R.abs_bound(L)
+        assert bound < 2 ** 24, (k, bound)
+        ref = R.conv_reference(L)
+        # float32 in two orders == float64, bit for bit (INBN: the operand is the reference's own)
+        xw = L["inp"][..., kw["in_coff"]:kw["in_coff"] + kw["cin"]]
+        if kw.get("res_mode") == R.RES_INBN:
+            c = L["bn_coef"]
+            xw = bn_ref.bn_apply(xw, None, c[2], c[3], c[0], c.shape[1], True, dtype)["y"]
+        ho, wo = ref["acc"].shape[1:3]
+        geo = dict(ipe=kw["ipe"], in_shared=kw.get("in_shared", False), stride=kw["stride"], pad=kw["pad"], ho=ho, wo=wo,
+                   dilate=kw.get("dilate", False))
+        for taps in (False, True):
+            a32 = R.conv_acc(xw, L["w"], dtype=F32, taps=taps, **geo)
+            assert torch.equal(a32.to(F64), ref["acc"]), (k, "float32 accumulation differs from float64", taps)
+        stored, pre = ref["stored"], ref["pre"]
+        if kind == "unit":
+            assert pre.abs().max() < 256 and torch.equal(stored, pre), (k, pre.abs().max().item())
+            if kw["stats"]:
+                assert (ref["sums_abs"] < 2 ** 24).all(), k                   # (integer terms: the unit kind's x-hat is one too)
+        elif dtype == BF16:
+            # (of the elements the launch computes and keeps: the in-place 1x1 form computes a quarter of the pixels, a mask
+            #  clears its share)
+            nz = (ref["acc"] != 0) & (pre != 0)
+            inexact = (stored != pre)
+            tie = inexact & (bf16_boundary_distance(pre.abs()) == 0)
+            fi, ft = inexact.sum().item() / nz.sum().item(), tie.sum().item() / nz.sum().item()
+            print(f"{k}: {100 * fi:.1f} % of the non-zero outputs round, {100 * ft:.1f} % on exact ties; max sum|x||w| {bound:.0f}")
+            assert fi >= 0.05 and ft >= 0.05, (k, fi, ft)
+        mode, fl = kw.get("res_mode"), R.flags(case)[k]
+        if kw.get("act") == R.ACT_RELU:
+            edge = ref["acc"][0, min(2, ho - 1) // kw["stride"], min(2, wo - 1) // kw["stride"]] + L["bias"][0]
+            if mode == R.RES_ADD:                                               # (a separate residual is zero on the planted pixel)
+                res = L["out_init"] if L["res_is_out"] else L["res"]
+                edge = edge + res[0, min(2, ho - 1) // kw["stride"], min(2, wo - 1) // kw["stride"], kw["res_coff"]:kw["res_coff"] + kw["cout"]]
+            assert L["res_is_out"] or all((edge == v).any() for v in (-1.0, 0.0, 1.0)), k
+            assert (pre == 0).any() and (ref["acc"] > 0).any() and (ref["acc"] < 0).any()
+        if mode in (R.RES_DBN, R.RES_INBN):
+            c = L["bn_coef"]
+            z = xw if mode == R.RES_INBN else L["res"][..., kw["res_coff"]:kw["res_coff"] + kw["cout"]]
+            zin = L["inp"][..., kw["in_coff"]:kw["in_coff"] + kw["cin"]] if mode == R.RES_INBN else z
+            p = (zin - R._per_image(c[0], kw["bn_ipe"])) * R._per_image(c[2], kw["bn_ipe"]) + R._per_image(c[3], kw["bn_ipe"])
+            step = (R._per_image(c[2], kw["bn_ipe"]) * (1.0 if kind == "unit" else 0.25)).abs()
+            assert (p == 0).any() and (p == step).any() and (p == -step).any(), k
+        if mode == R.RES_DRELU:
+            r = L["res"][..., kw["res_coff"]:kw["res_coff"] + kw["cout"]]
+            assert all((r == v).any() for v in (-1.0, 0.0, 1.0)), k
+    if "w" in ls:
+        L = ls["w"]
+        assert _representable(L["x"], dtype) and _representable(L["dy"], dtype)
+        ref = R.wgrad_reference(L)
+        if L["bn"] is not None:
+            z, coef, c1, c2 = L["bn"]
+            assert _representable(z, dtype) and all(_representable(t, F32) for t in (coef, c1, c2))
+            raw = bn_ref.bn_bwd_apply(L["dy"], None, z, coef[0], coef[1], coef[2], coef[3], c1, c2, case.E, False, F64)["dx"]
+            assert ((ref["dz"] != raw).float().mean() > 0.05), "the fused BatchNorm backward's bfloat16 rounding never rounds"
+        kw = L["kw"]
+        mags = R.wgrad(L["x"].abs(), ref["dz"].abs() if L["bn"] is not None else L["dy"].abs(),
+                       **{**kw, "dy_coff": 0 if L["bn"] is not None else kw["dy_coff"]})["dw_ws"]
+        unit = 2048 if L["bn"] is not None else 1                           # (dz: multiples of 2^-11)
+        assert mags.max() * unit < 2 ** 24, mags.max().item()
+        assert torch.equal(R.wgrad_reference(L, evaluate=F32)["dw_ws"].to(F64), ref["dw_ws"])
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the reference against torch and its autograd (continuous float64 data, one small shape per form)
+
+def relerr(a, b):
+    return ((a - b).abs().max() / b.abs().max().clamp_min(1e-300)).item()
+
+
+def nchw(t):
+    return t.permute(0, 3, 1, 2)
+
+
+def nhwc(t):
+    return t.permute(0, 2, 3, 1)
+
+
+@pytest.mark.parametrize("shape", [(2, 3, 5, 6, 7, 9, 3, 1), (1, 2, 4, 6, 9, 7, 3, 2), (2, 2, 6, 4, 8, 8, 3, 2), (2, 1, 5, 3, 7, 6, 1, 2),
+                                   (1, 3, 4, 8, 5, 5, 1, 1)], ids=lambda s: "x".join(map(str, s)))
+def test_reference_matches_autograd(shape):
+    """forward with bias / residual / ReLU / statistics, the data gradient as the launch forms it (flipped transposed filter,
+    zero-dilated source at stride 2, accumulated in place) and the weight gradient with its workspace layout"""
+    E, ipe, cin, cout, H, W, ks, stride = shape
+    g = torch.Generator().manual_seed(sum(shape))
+    rn = lambda *s: torch.randn(*s, generator=g, dtype=F64)
+    N, pad = E * ipe, ks // 2
+    Ho, Wo = R.out_size(H, ks, stride, pad), R.out_size(W, ks, stride, pad)
+    x, w, b, res, dy, prev = rn(N, H, W, cin), rn(E, cout, cin, ks, ks), rn(E, cout), rn(N, Ho, Wo, cout), rn(N, Ho, Wo, cout), rn(N, H, W, cin)
+    xr, wr, br = nchw(x).clone().requires_grad_(True), w.clone().requires_grad_(True), b.clone().requires_grad_(True)
+    lin = torch.cat([F.conv2d(xr[e * ipe:(e + 1) * ipe], wr[e], br[e], stride=stride, padding=pad) for e in range(E)])
+    y = F.relu(lin + nchw(res))
+    y.backward(nchw(dy))
+    buf, coff = R._window(x, True)
+    out_init = torch.full((N, Ho, Wo, cout + 8), R.SENTINEL, dtype=F64)
+    f = R.conv2d(buf, w, out_init, cin=cin, cout=cout, ipe=ipe, ks=ks, stride=stride, pad=pad, dtype=F64, in_coff=coff, out_coff=8,
+                 bias=b, res=res, res_mode=R.RES_ADD, act=R.ACT_RELU, stats=True)
+    assert relerr(nchw(f["stored"]), y.detach()) < 1e-12 and relerr(nchw(f["acc"]), (lin - br.repeat_interleave(ipe, 0)[:, :, None, None]).detach()) < 1e-12
+    assert (f["out"][..., :8] == R.SENTINEL).all() and torch.equal(f["out"][..., 8:], f["stored"])
+    ye = nhwc(y.detach()).reshape(E, -1, cout)
+    assert relerr(f["sums"][:, 0], ye.sum(1)) < 1e-12 and relerr(f["sums"][:, 1], (ye * ye).sum(1)) < 1e-12
+    # data gradient: g = dy masked by the ReLU (PMOE_RES_DRELU on the saved output is that mask applied to a convolution)
+    gm = dy * (f["stored"] > 0)
+    wd = w.flip(3, 4).transpose(1, 2).contiguous()
+    dgr = R.conv2d(gm, wd, prev, cin=cout, cout=cin, ipe=ipe, ks=ks, stride=1, pad=ks - 1 - pad, dtype=F64, dilate=stride == 2,
+                   res=prev, res_mode=R.RES_ADD)
+    assert relerr(nchw(dgr["out"]), xr.grad + nchw(prev)) < 1e-12
+    fwd, dgrd = R.pack_weights(w, cout + 3, cin + 2, F64, cin + 1, cout + 5)
+    assert torch.equal(dgrd[:, :cin, :, :cout], wd.reshape(E, cin, cout, ks * ks).permute(0, 1, 3, 2))
+    assert torch.equal(fwd[:, :cout, :, :cin], w.reshape(E, cout, cin, ks * ks).permute(0, 1, 3, 2)) and fwd[:, cout:].abs().sum() == 0
+    # weight gradient
+    wg = R.wgrad(x, gm, cin=cin, cout=cout, cinp=cin + 3, coutp=cout + 2, ipe=ipe, ks=ks, stride=stride, pad=pad, dtype=F64)
+    assert relerr(wg["grads"], wr.grad) < 1e-12
+    assert wg["dw_ws"].shape == (E, ks * ks, cout + 2, cin + 3) and wg["dw_ws"][:, :, cout:].abs().sum() == 0
+    pi = R.wgrad(x, gm, cin=cin, cout=cout, cinp=cin + 3, coutp=cout + 2, ipe=ipe, ks=ks, stride=stride, pad=pad, dtype=F64, per_image=True)
+    assert relerr(pi["dw_ws"].reshape(E, ipe, ks * ks, cout + 2, cin + 3).sum(1), wg["dw_ws"]) < 1e-12
+    if stride == 1:
+        # a shared input: every expert reads the same ipe images
+        xs = x[:ipe]
+        sh = R.conv2d(xs, w, out_init[..., :cout], cin=cin, cout=cout, ipe=ipe, ks=ks, stride=1, pad=pad, dtype=F64, in_shared=True)
+        want = torch.cat([F.conv2d(nchw(xs), w[e], padding=pad) for e in range(E)])
+        assert relerr(nchw(sh["stored"]), want) < 1e-12
+        ws = R.wgrad(xs, gm, cin=cin, cout=cout, cinp=cin, coutp=cout, ipe=ipe, ks=ks, stride=1, pad=pad, dtype=F64, x_shared=True)
+        xr2, w2 = nchw(xs).clone(), w.clone().requires_grad_(True)
+        torch.cat([F.conv2d(xr2, w2[e], padding=pad) for e in range(E)]).backward(nchw(gm))
+        assert relerr(ws["grads"], w2.grad) < 1e-12
+
+
+def test_reference_shuffle_matches_conv_transpose():
+    E, ipe, cin, c_up, H, W = 2, 2, 6, 8, 4, 8
+    g = torch.Generator().manual_seed(7)
+    rn = lambda *s: torch.randn(*s, generator=g, dtype=F64)
+    x, wt, b = rn(E * ipe, H, W, cin), rn(E, cin, c_up, 2, 2), rn(E, c_up)
+    # the 1x1 layer of include/pmoe_hip.h: row (2 dy + dx) * c_up + c of its filter
+    w = wt.permute(0, 3, 4, 2, 1).reshape(E, 4 * c_up, cin, 1, 1)
+    out_init = torch.full((E * ipe, 2 * H, 2 * W, 2 * c_up), R.SENTINEL, dtype=F64)
+    r = R.conv2d(x, w, out_init, cin=cin, cout=4 * c_up, ipe=ipe, ks=1, stride=1, pad=0, dtype=F64, out_coff=c_up, shuffle_c=c_up,
+                 bias=b.repeat(1, 4))
+    want = torch.cat([F.conv_transpose2d(nchw(x[e * ipe:(e + 1) * ipe]), wt[e], b[e], stride=2) for e in range(E)])
+    assert relerr(nchw(r["out"][..., c_up:]), want) < 1e-12 and (r["out"][..., :c_up] == R.SENTINEL).all()
+
+
+def test_reference_fused_batchnorm_forms_match_batch_norm_and_autograd():
+    """PMOE_RES_INBN forward, PMOE_RES_DBN data gradient with its two reductions, and the bn_fused weight gradient against
+    conv -> batch_norm -> relu -> conv in float64 autograd"""
+    E, ipe, C, H, W, eps = 2, 3, 5, 6, 7, 1e-5
+    g = torch.Generator().manual_seed(11)
+    rn = lambda *s: torch.randn(*s, generator=g, dtype=F64)
+    N = E * ipe
+    x, w1, w2, dy = rn(N, H, W, C), rn(E, C, C, 3, 3), rn(E, C, C, 3, 3), rn(N, H, W, C)
+    gamma, beta = 1 + 0.1 * rn(E, C), 0.1 * rn(E, C)
+    xr, w1r, gr, br = nchw(x).clone().requires_grad_(True), w1.clone().requires_grad_(True), gamma.clone().requires_grad_(True), beta.clone().requires_grad_(True)
+    zs, outs = [], []
+    for e in range(E):
+        z = F.conv2d(xr[e * ipe:(e + 1) * ipe], w1r[e], padding=1)
+        zs.append(z)
+        outs.append(F.conv2d(F.relu(F.batch_norm(z, None, None, gr[e], br[e], True, 0.1, eps)), w2[e], padding=1))
+    torch.cat(outs).backward(nchw(dy))
+    z = nhwc(torch.cat(zs).detach()).contiguous()
+    ze = z.reshape(E, -1, C)
+    mean, var = ze.mean(1), ze.var(1, unbiased=False)
+    invstd = 1 / torch.sqrt(var + eps)
+    coef = torch.stack([mean, invstd, gamma * invstd, beta])
+    blank = torch.zeros(N, H, W, C, dtype=F64)
+    f = R.conv2d(z, w2, blank, cin=C, cout=C, ipe=ipe, ks=3, stride=1, pad=1, dtype=F64, res_mode=R.RES_INBN, bn_coef=coef, bn_ipe=ipe)
+    assert relerr(nchw(f["stored"]), torch.cat(outs).detach()) < 1e-11
+    wd = w2.flip(3, 4).transpose(1, 2).contiguous()
+    d = R.conv2d(dy, wd, blank, cin=C, cout=C, ipe=ipe, ks=3, stride=1, pad=1, dtype=F64, res=z, res_mode=R.RES_DBN, bn_coef=coef,
+                 bn_ipe=ipe, stats=True)
+    assert relerr(d["sums"][:, 0], br.grad) < 1e-11 and relerr(d["sums"][:, 1], gr.grad) < 1e-11
+    fin = bn_ref.bn_bwd_finalize(d["sums"][:, None], ipe * H * W)
+    wg = R.wgrad(x, d["stored"], cin=C, cout=C, cinp=C, coutp=C, ipe=ipe, ks=3, stride=1, pad=1, dtype=F64,
+                 bn=(z, coef, fin["c1"], fin["c2"]))
+    assert relerr(wg["grads"], w1r.grad) < 1e-10
+    dz = bn_ref.bn_bwd_apply(d["stored"], None, z, mean, invstd, coef[2], beta, fin["c1"], fin["c2"], E, False, F64)["dx"]
+    wd1 = w1.flip(3, 4).transpose(1, 2).contiguous()
+    dx = R.conv2d(dz, wd1, blank, cin=C, cout=C, ipe=ipe, ks=3, stride=1, pad=1, dtype=F64)
+    assert relerr(nchw(dx["stored"]), xr.grad) < 1e-10
+
+
+def test_reference_scaled_and_gated_packs():
+    E, ipe, cout, cin, ks = 2, 3, 4, 5, 3
+    g = torch.Generator().manual_seed(3)
+    rn = lambda *s: torch.randn(*s, generator=g, dtype=F64)
+    w, sc, sh, mu, gate, x = rn(E, cout, cin, ks, ks), rn(E, cout), rn(E, cout), rn(E, cout), rn(E * ipe, cin + 2), rn(E * ipe, 6, 6, cin)
+    fwd, bias = R.pack_weights_scaled(w, sc, sh, mu, cout, cin, F64)
+    blank = torch.zeros(E * ipe, 6, 6, cout, dtype=F64)
+    unpack = lambda p: p.permute(0, 1, 3, 2).reshape(p.shape[0], cout, cin, ks, ks)
+    y = R.conv2d(x, unpack(fwd), blank, cin=cin, cout=cout, ipe=ipe, ks=ks, stride=1, pad=1, dtype=F64, bias=bias)["stored"]
+    plain = R.conv2d(x, w, blank, cin=cin, cout=cout, ipe=ipe, ks=ks, stride=1, pad=1, dtype=F64)["stored"]
+    bc = lambda t: t.repeat_interleave(ipe, 0)[:, None, None, :]
+    assert relerr(y, (plain - bc(mu)) * bc(sc) + bc(sh)) < 1e-12                 # eval-mode BatchNorm folded into the filter
+    gf, gd = R.pack_weights_gated(w, gate, ipe, cout, cin, F64, cin, cout)
+    yg = R.conv2d(x, unpack(gf), blank, cin=cin, cout=cout, ipe=1, ks=ks, stride=1, pad=1, dtype=F64)["stored"]
+    want = R.conv2d(x * gate[:, None, None, :cin], w, blank, cin=cin, cout=cout, ipe=ipe, ks=ks, stride=1, pad=1, dtype=F64)["stored"]
+    assert relerr(yg, want) < 1e-12
+    assert torch.equal(gd, R.pack_weights(unpack(gf), cout, cin, F64, cin, cout)[1])

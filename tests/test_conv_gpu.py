@@ -1,0 +1,186 @@
+"""Every convolution kernel (csrc/conv_igemm.hip, conv_dma.hip + conv_dma_epilogue.inc, conv_res.hip, conv_c1x1.hip,
+conv_c16.hip, conv_wgrad.hip) and the weight packs against the float64 reference of their own operation (tests/conv_ref.py), at
+the smallest shapes that reach each plan code (conv_ref.CASES; tests/test_conv_cpu.py proves that the table covers every code the
+planners answer), through pmoe_amd.ops, the binding the engines use.
+
+Two kinds of input (tests/test_conv_cpu.py checks on the CPU what is assumed of them here):
+  lattice  integers with sum |x||w| < 2^24: a float32 accumulation is exact in any order, so every STORED element must equal the
+           reference's, rounded in the order conv_ref.ROUNDING names for the kernel -- one missing or doubled term, a truncation, a
+           second rounding or a residual left out all show as unequal elements.  Fused statistics: per-expert totals within
+           (L + 8) 2^-24 sum|term|, L = conv_ref.chain_stats.
+  unit     {-1, 0, 1}: nothing rounds and the statistics are exact too.
+Every buffer is compared WHOLE: outputs are sentinel-filled before the launch, so pad channels, the other columns of out_ld, the
+untouched half of a concatenation buffer and the odd pixels of the in-place stride-2 1x1 gradient must come back unchanged;
+everything outside an input's channel window is NaN, so a read outside it poisons the output.  The plan code is asserted before
+each launch; every kernel gets the generator's (= the reference's) inputs, never another kernel's output.
+"""
+
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+from pmoe_amd import hip, ops  # noqa: E402
+from tests import conv_ref as R  # noqa: E402
+from tests.test_bn_gpu import same  # noqa: E402
+from tests.test_conv_cpu import conv_prepare, conv_tensors, set_switches, wgrad_plan  # noqa: E402
+
+DEV = "cuda"
+F64, F32, BF16 = R.F64, R.F32, R.BF16
+EPS = R.EPS24
+CONV_CASES = [c for c in R.CASES if c.codes[0] is not None or c.codes[1] is not None]
+WGRAD_CASES = [c for c in R.CASES if c.codes[2] is not None]
+
+
+def ids(cases):
+    return [R.case_id(c) for c in cases]
+
+
+def check_conv_launch(L, code_expected, kind, what):
+    kw = L["kw"]
+    t = conv_tensors(L, DEV)
+    p = conv_prepare(L, t)
+    code = p.plan()
+    assert code == code_expected, f"{what}: routed to kernel code {code}, this case is meant for {code_expected}"
+    E, cout, coutp = L["w"].shape[0], kw["cout"], R.r64(kw["cout"])
+    guard = None
+    if kw["stats"]:
+        rows = p.stat_rows()
+        assert rows > 0 and rows % E == 0, (rows, E)
+        guard = torch.full((rows + 3, 2, coutp), float("nan"), dtype=F32, device=DEV)
+        p = conv_prepare(L, t, stats=guard[:rows])
+    p.launch()
+    torch.cuda.synchronize()
+    order = R.rounding_of(code, kw.get("res_mode", R.RES_NONE), L["bias"] is not None, kw.get("act", R.ACT_NONE))
+    ref = R.conv_reference(L, order)
+    got = t["out"].cpu().to(F64)
+    if not (got == ref["out"]).all():
+        other = R.conv_reference(L, "staged" if order == "once" else "once")["out"]
+        hint = f" (it DOES equal the '{'staged' if order == 'once' else 'once'}' order)" if (got == other).all() else ""
+        same(got, ref["out"], f"{what}: code {code}, rounding order '{order}'{hint}")
+    if kw.get("res_mode", R.RES_NONE) not in (R.RES_DRELU, R.RES_DBN):
+        # the sign of a zero is exempt in MASKED gradients only (+0 or -0 by how the mask is applied): bit for bit elsewhere
+        neg = torch.signbit(t["out"].float().cpu()) != torch.signbit(ref["out"].to(F32))
+        assert not neg.any(), f"{what}: code {code}: {int(neg.sum())} elements differ in sign only (a zero of the other sign); first {neg.nonzero()[:4].tolist()}"
+    for name, src in (("x", L["inp"]), ("res", None if L["res_is_out"] else L["res"])):
+        if src is not None:                                            # inputs come back as they went in (NaN outside the windows)
+            back = t[name].cpu().to(F64)
+            assert torch.equal(torch.isnan(back), torch.isnan(src)) and torch.equal(back.nan_to_num(), src.nan_to_num()), f"{what}: {name} modified"
+    if guard is None:
+        return
+    g = guard.cpu().to(F64)
+    assert torch.isnan(g[rows:]).all(), f"{what}: statistics rows beyond conv2d_stat_rows = {rows} written"
+    assert not torch.isnan(g[:rows, :, :cout]).any(), f"{what}: statistics rows left unwritten"
+    tot = g[:rows].reshape(E, rows // E, 2, coutp).sum(1)[..., :cout]
+    n, ho, wo = ref["acc"].shape[:3]
+    Lc = R.chain_stats(code, R.tiles_per_expert(code, kw["ipe"], ho, wo), rows // E)
+    err = (tot - ref["sums"]).abs()
+    print(f"{what}: statistics rows {rows}, L {Lc}, max err / (2^-24 sum|term|) "
+          f"{(err / (EPS * ref['sums_abs']).clamp_min(1e-300)).max().item():.2f}")
+    if kind == "unit":
+        same(tot, ref["sums"], f"{what}: statistics totals (exact on the unit kind)")
+    else:
+        bad = err > (Lc + 8) * EPS * ref["sums_abs"]
+        assert not bad.any(), (f"{what}: {int(bad.sum())} statistics totals beyond (L + 8) 2^-24 sum|term|, L = {Lc}; first "
+                               f"{bad.nonzero()[:4].tolist()}, worst err {err.max().item():.3e}")
+
+
+@pytest.mark.parametrize("kind", R.KINDS)
+@pytest.mark.parametrize("case", CONV_CASES, ids=ids(CONV_CASES))
+def test_conv_launches_match_reference(case, kind, monkeypatch):
+    """forward and data gradient of the case, each under its request: stored output, untouched bytes, statistics"""
+    set_switches(monkeypatch, case)
+    ls = R.launches(case, kind)
+    for i, k in enumerate("fd"):
+        if k in ls:
+            check_conv_launch(ls[k], case.codes[i], kind, f"{'forward' if k == 'f' else 'data gradient'} [{R.flags(case)[k] and '+'.join(sorted(R.flags(case)[k]))}]")
+
+
+SENTINEL = R.SENTINEL
+
+
+@pytest.mark.parametrize("kind", R.KINDS)
+@pytest.mark.parametrize("case", WGRAD_CASES, ids=ids(WGRAD_CASES))
+def test_wgrad_matches_reference(case, kind, monkeypatch):
+    """dw_ws exact with its pad rows and columns (zeros: every element is stored); the parameter-layout gradient of the fused
+    fold, of the deferred fold and of pmoe_unpack_conv_wgrad bit-identical to each other and to the reference"""
+    set_switches(monkeypatch, case)
+    L = R.launches(case, kind)["w"]
+    kw = L["kw"]
+    dtype = kw["dtype"]
+    code, nsplit = wgrad_plan(L)
+    assert code == case.codes[2], f"weight gradient routed to kernel code {code}, this case is meant for {case.codes[2]}"
+    ref = R.wgrad_reference(L)
+    x, dy = L["x"].to(dtype).to(DEV), L["dy"].to(dtype).to(DEV)
+    bn = None
+    if L["bn"] is not None:
+        z, coef, c1, c2 = L["bn"]
+        bn = (z.to(dtype).to(DEV), coef.to(F32).to(DEV), c1.to(F32).to(DEV), c2.to(F32).to(DEV))
+    common = dict(cin=kw["cin"], cout=kw["cout"], cinp=kw["cinp"], coutp=kw["coutp"], ipe=kw["ipe"], ks=kw["ks"], stride=kw["stride"],
+                  pad=kw["pad"], x_shared=kw["x_shared"], x_coff=kw["x_coff"], dy_coff=kw["dy_coff"], per_image=kw["per_image"], bn_fuse=bn)
+    ws = torch.full(ref["dw_ws"].shape, SENTINEL, dtype=F32, device=DEV)
+    ops.conv2d_wgrad(x, dy, ws, **common)
+    torch.cuda.synchronize()
+    print(f"weight gradient: code {code}, K-split {nsplit}, workspace {tuple(ws.shape)}")
+    same(ws, ref["dw_ws"], f"dw_ws (code {code}, K-split {nsplit})")
+    for name, t, src in (("x", x, L["x"]), ("dy", dy, L["dy"])):
+        assert torch.equal(t.cpu().to(F64).nan_to_num(), src.nan_to_num()), f"{name} modified"
+    if kw["per_image"]:
+        return
+    E, cout, cin, ks = ws.shape[0], kw["cout"], kw["cin"], kw["ks"]
+    shape = (E, cout, cin, ks, ks)
+    fused, deferred, unpacked = (torch.full(shape, SENTINEL, dtype=F32, device=DEV) for _ in range(3))
+    scratch = torch.full_like(ws, SENTINEL)
+    ops.conv2d_wgrad(x, dy, scratch, grads=fused.view(-1), grads_cout=cout, grads_cin=cin, **common)
+    d = ops.conv2d_wgrad(x, dy, scratch, grads=deferred.view(-1), grads_cout=cout, grads_cin=cin, defer_fold=True, **common)
+    ops.conv2d_wgrad_fold(d)
+    ops.unpack_conv_wgrad(ref["dw_ws"].to(F32).to(DEV), unpacked, E, cout, cin, ks, kw["coutp"], kw["cinp"])
+    torch.cuda.synchronize()
+    same(fused, ref["grads"], "grads of the fused fold")
+    same(deferred, ref["grads"], "grads of the deferred fold")
+    same(unpacked, ref["grads"], "pmoe_unpack_conv_wgrad of the reference's workspace")
+    assert torch.equal(fused, deferred) and torch.equal(fused, unpacked)
+
+
+@pytest.mark.parametrize("dtype", [BF16, F32], ids=["bf16", "f32"])
+@pytest.mark.parametrize("shape", [(2, 3, 24, 12, 3), (3, 2, 72, 40, 1), (1, 2, 64, 64, 3)], ids=lambda s: "x".join(map(str, s)))
+def test_weight_packs_match_reference(shape, dtype):
+    """forward, data-gradient (taps reversed), scaled and gated packs on lattice values whose products are exact: every element,
+    pad rows and columns zero"""
+    E, ipe, cout, cin, ks = shape
+    g = torch.Generator().manual_seed(sum(shape))
+    coutp, cinp, cinp2, coutp2 = R.r64(cout), R.r16(cin), R.r64(cin), R.r16(cout)
+    w = torch.randint(-7, 8, (E, cout, cin, ks, ks), generator=g).to(F64)
+    dev_w = [w[e].to(F32).to(DEV).contiguous() for e in range(E)]
+    tab = hip.ptr_table(dev_w, DEV)
+    nan = lambda *s: torch.full(s, float("nan"), dtype=dtype, device=DEV)
+    fwd, dgrd = nan(E, coutp, ks * ks, cinp), nan(E, cinp2, ks * ks, coutp2)
+    ops.pack_conv_weights(tab, fwd, dgrd, E, cout, cin, ks, coutp, cinp, cinp2, coutp2, dtype)
+    rf, rd = R.pack_weights(w, coutp, cinp, dtype, cinp2, coutp2)
+    same(fwd, rf, "forward pack")
+    same(dgrd, rd, "data-gradient pack")
+    # eval-mode BatchNorm folded in: W * scale (integers and halves up to 21: exact in bfloat16), bias = shift - mean * scale
+    pick = lambda vals, *s: torch.tensor(vals, dtype=F64)[torch.randint(0, len(vals), s, generator=g)]
+    scale, shift, mean = pick([-2.0, -1.0, 0.5, 1.0, 2.0, 3.0], E, cout), pick([-1.5, -0.5, 0.0, 0.25, 2.0], E, cout), pick([-0.75, 0.0, 0.5, 1.25], E, cout)
+    fs, bias = nan(E, coutp, ks * ks, cinp), torch.full((E, coutp), float("nan"), dtype=F32, device=DEV)
+    ops.pack_conv_weights_scaled(tab, scale.to(F32).to(DEV), shift.to(F32).to(DEV), mean.to(F32).to(DEV), fs, bias, E, cout, cin, ks,
+                                 coutp, cinp, dtype)
+    rs, rb = R.pack_weights_scaled(w, scale, shift, mean, coutp, cinp, dtype)
+    same(fs, rs, "scaled pack")
+    same(bias, rb, "bias of the scaled pack")
+    # per-image packs with the ECA gate folded in
+    N, gate_ld = E * ipe, R.r16(cin) + 16
+    gate = pick([0.0, 0.25, 0.5, 1.0, 2.0], N, gate_ld)
+    fg, dg = nan(N, coutp, ks * ks, cinp), nan(N, cinp2, ks * ks, coutp2)
+    ops.pack_conv_weights_gated(tab, gate.to(F32).to(DEV), fg, dg, N, ipe, cout, cin, ks, coutp, cinp, cinp2, coutp2, dtype)
+    rg, rgd = R.pack_weights_gated(w, gate, ipe, coutp, cinp, dtype, cinp2, coutp2)
+    same(fg, rg, "gated forward pack")
+    same(dg, rgd, "gated data-gradient pack")
+    # and back: workspace -> parameter layout
+    ckw = 64 if dtype == BF16 else 32
+    cop, cip = (cout + ckw - 1) // ckw * ckw, (cin + ckw - 1) // ckw * ckw
+    ws = torch.randint(-999, 1000, (E, ks * ks, cop, cip), generator=g).to(F64)
+    grads = torch.full((E, cout, cin, ks, ks), float("nan"), dtype=F32, device=DEV)
+    ops.unpack_conv_wgrad(ws.to(F32).to(DEV), grads, E, cout, cin, ks, cop, cip)
+    torch.cuda.synchronize()
+    same(grads, R.unpack_wgrad(ws, cout, cin, ks), "pmoe_unpack_conv_wgrad")

@@ -97,6 +97,11 @@ CONV_CASES = [
 ]
 
 
+# Which suite proves what: this file runs continuous random data at the full-size layer shapes against fp32 CPU autograd, within
+# 1e-2 of each element's magnitude plus a share of the tensor's scale (bf16) -- the kernels work at the sizes the models use.
+# tests/test_conv_gpu.py runs every plan code at its smallest shape on integer lattices against a float64 reference, element for
+# element -- no term is missing or doubled, the output is rounded once in the stated order, the fused statistics are sums of the
+# stored values, and nothing outside the windows is read or written.
 def _conv_case(case, dtype, plan=None):
     """forward (+ fused BatchNorm partial sums), data gradient, weight gradient of one grouped conv against CPU fp32 autograd.
     ``plan`` = (forward code, data-gradient code, weight-gradient K-split x channel-tile pairs[, weight-gradient code]): asserted
