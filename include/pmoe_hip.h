@@ -481,6 +481,31 @@ int pmoe_history_push(void* ring, const void* item, int32_t B, int32_t T, int64_
 int pmoe_mixture_draw(const float* probs, const float* mean, const float* std_, void* state, float* raw,
                       const float* punet_actions, const float* lat_w, const float* lat_b, const float* long_w,
                       const float* long_b, float* out, int32_t B, int32_t E, void* stream);
+/* ---- the agent's step around the tick (pmoe_amd/infer.py:AgentStep; autoagents/image_agent.py:114-125,127-160)
+ * Sensor frame -> history ring in ONE launch: bgra [B][H0][W0][4] bytes in the order B, G, R, A (what the CARLA camera delivers;
+ * 4-byte aligned) -> Crop (source rows row0 .. row0 + rows - 1) -> Resize to Hout x Wout -> ToTensor, pushed into ring f32
+ * [B][T][3][Hout][Wout] the way pmoe_history_push pushes an item: slot t + 1 moves to slot t, oldest first, by the thread that owns the
+ * element, and the new frame becomes slot T-1.  Output channel c reads byte 2 - c of a pixel; the alpha byte reaches no result.
+ * The resize is pmoe_resample_u8_horizontal followed by pmoe_resample_u8_vertical_to_f32 (same tables, 22-bit coefficients, the
+ * intermediate rounded to 8 bits, value / 255): bit-exact with Pillow.  nhwc != NULL: the new frame also as `nhwc_dtype`
+ * [B][Hout][Wout][Cp], zero padded, under the rules of pmoe_history_push (16-byte aligned, Cp >= 3 and a multiple of the 16-byte
+ * vector, bf16 or f32); NULL: Cp / nhwc_dtype unused.
+ * A workgroup owns tile_rows (8, 4, 2 or 1) output rows of one image and keeps the horizontally resampled 8-bit source rows they
+ * read -- at most tile_in_rows of them, starting at the first tap of the tile's first output row -- in LDS:
+ * tile_in_rows * Wout * 3 bytes, more than 64 KiB: PMOE_ERR_UNSUPPORTED.  PMOE_ERR_ARG: a null or misaligned pointer, a size < 1,
+ * B > 65535, a crop outside the frame, another tile_rows, a refused Cp / nhwc_dtype.  The tables are device memory: the kernel
+ * clamps every tap to the frame's columns, to the staged rows and to hksize / vksize coefficients, so their content decides
+ * pixels, never an address outside the buffers.  No atomics: the result is a function of the bytes and the ring alone. */
+int pmoe_sensor_push(const uint8_t* bgra, void* ring, int32_t B, int32_t T, int32_t H0, int32_t W0, int32_t row0, int32_t rows,
+                     int32_t Hout, int32_t Wout, const int32_t* hbounds, const int32_t* hcoeffs, int32_t hksize,
+                     const int32_t* vbounds, const int32_t* vcoeffs, int32_t vksize, int32_t tile_rows, int32_t tile_in_rows,
+                     void* nhwc, int32_t Cp, int32_t nhwc_dtype, void* stream);
+/* postprocess of image_agent.py:114-125 on the device: actions [B][2] f32 -> control [B][3] f64 = (steer, throttle, brake), the
+ * Python floats the reference hands to carla.VehicleControl.  With clipf(x, lo, hi) = x < lo ? lo : (x > hi ? hi : x) in f32 (a
+ * NaN passes through):  a1 < -0.5f: (0, 0, (double)clipf(-a1, 0, 1));  otherwise steer = (double)clipf(a0, -1, 1),
+ * t = (double)clipf(a1, 0, 0.75f), throttle = 0.4 > t ? 0.4 : t compared in double (the reference's floor is the double 0.4,
+ * which no f32 holds; a NaN t stays NaN), brake = 0.  PMOE_ERR_ARG: a null pointer, B < 1. */
+int pmoe_control_postprocess(const float* actions, double* control, int32_t B, void* stream);
 
 /* ---- stage-1 PU-Net training (trainer/train_1.py:129-141) ------------------------------------------
  * Backward of nn.MaxPool2d(2,2) (blocks/unet.py:52-62): dx = scatter of dy to the FIRST maximum of each 2x2 window of x

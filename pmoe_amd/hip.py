@@ -126,6 +126,8 @@ SIGNATURES = {
     "pmoe_blend_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P],
     "pmoe_history_push": [_P, _P, _I, _I, _L, _I, _P, _I, _I, _I, _P],
     "pmoe_mixture_draw": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P],
+    "pmoe_sensor_push": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _I, _I, _P, _I, _I, _P],
+    "pmoe_control_postprocess": [_P, _P, _I, _P],
     "pmoe_maxpool2s2_bwd": [_P, _I, _I, _P, _P, _I, _I, _P, _I, _I, _I, _I, _I, _P],
     "pmoe_pixel_unshuffle2": [_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P],
     "pmoe_add_window": [_P, _I, _I, _P, _I, _I, _L, _I, _I, _P],

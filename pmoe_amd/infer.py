@@ -6,13 +6,19 @@ chain can be captured ONCE into a HIP graph (``torch.cuda.CUDAGraph`` is hipGrap
 new inputs copied into the captured input buffers.  Parameters are read through the captured packed-weight buffers; every
 replay first compares the engine's build / pointer-table / version keys with those taken at capture and re-captures
 (:meth:`GraphedMixture.refresh`) when a weight, a BatchNorm buffer, the compute dtype or the device has changed since.
+
+:class:`PolicyTick` is the agent's loop for every model type (frame and mask history on the device, the draw on the device);
+:class:`AgentStep` is the whole ``run_step`` around it (``image_agent.py:114-177``): the camera's BGRA bytes, the speed and the
+command in, (steer, throttle, brake) out.
 """
 import types
 
+import numpy as np
 import torch
 
 from . import hip, ops
 from .engine import r16
+from .preprocess import _coeffs
 from .model import moe as _moe
 from .model.moe import MixtureDistribution
 
@@ -214,9 +220,7 @@ class PolicyTick:
         the recording.  Runs by itself when the engines' plan key has changed."""
         dev = next(self.model.parameters()).device
         if dev != self.frames.device:            # the model moved: this object's buffers follow it
-            self.frames, self.state, self.raw, self.out = (t.to(dev) for t in (self.frames, self.state, self.raw, self.out))
-            self.static_in = [t.to(dev) for t in self.static_in]
-            self.masks = self.newest = None
+            self._follow(dev)
         with torch.no_grad(), torch.cuda.device(dev):
             if self.pun is not None:
                 eng, dtype, _ = self.pun.resolve_engine()
@@ -242,12 +246,21 @@ class PolicyTick:
                     dst.copy_(src)
             self.key = self._key()
 
+    def _follow(self, dev):
+        self.frames, self.state, self.raw, self.out = (t.to(dev) for t in (self.frames, self.state, self.raw, self.out))
+        self.static_in = [t.to(dev) for t in self.static_in]
+        self.masks = self.newest = None
+
     # ------------------------------------------------------------------ one tick
+    def _push(self):
+        """the first launch of a tick: the new frame into the ring (and, for the U-Nets, into ``newest``)"""
+        ops.history_push(self.frames, self.static_in[0], nhwc=self.newest)
+
     def _body(self):
         """the launches of one tick, in order: frame push, PU-Net expert (its mask push inside), mixture, draw (+ blend)"""
-        frame, speed, command = self.static_in
+        _, speed, command = self.static_in
         res = dict(probs=None, mean=None, std=None, speeds=None, punet_actions=None, pred_speed=None, raw=None)
-        ops.history_push(self.frames, frame, nhwc=self.newest)
+        self._push()
         if self.pun is not None:
             eng, dtype, _ = self.pun.resolve_engine()
             res["punet_actions"], res["pred_speed"] = eng.forward_cached(self.frames, self.newest, self.masks, speed, command, dtype)
@@ -272,8 +285,15 @@ class PolicyTick:
             if tuple(dst.shape) != tuple(src.shape):
                 raise ValueError(f"PolicyTick: {name} must be {tuple(dst.shape)}, got {tuple(src.shape)}")
             dst.copy_(src)
+        self._fresh()
+        return self._issue()
+
+    def _fresh(self):
         if self._key() != self.key:              # weights / buffers / dtype / device changed: cached masks and the plan are stale
             self.refresh()
+
+    def _issue(self):
+        """the launches of one tick on what the input buffers hold"""
         with torch.no_grad():
             if self.plan is not None:
                 self.plan.replay()
@@ -284,3 +304,146 @@ class PolicyTick:
         return actions
 
     __call__ = tick
+
+
+class _SensorTick(PolicyTick):
+    """the tick inside an :class:`AgentStep`: its first launch reads the camera's bytes, its last one writes the control"""
+
+    def __init__(self, agent, model, **kw):
+        self.agent = agent
+        super().__init__(model, **kw)
+
+    def refresh(self):
+        dev = next(self.model.parameters()).device
+        if dev != self.frames.device:
+            self._follow(dev)
+        self.agent._device_buffers(self, dev)    # (before the recording: the plan keeps their pointers)
+        super().refresh()
+
+    def _push(self):
+        a = self.agent
+        ops.sensor_push(a._frame_dev, self.frames, a.top, a.rows, a._htable, a._vtable, a.tile, nhwc=self.newest)
+
+    def _body(self):
+        actions, res = super()._body()
+        ops.control_postprocess(actions, self.agent._control_dev)
+        return actions, res
+
+
+class AgentStep:
+    """``run_step`` of the agent (``autoagents/image_agent.py:114-177``) as one object: ``agent.step(bgra, spd, cmd)`` takes what
+    CARLA hands over -- the camera's uint8 BGRA frame ``[H0,W0,4]`` (numpy or CPU tensor; ``[B,H0,W0,4]`` for a batch), the speed
+    (a float, or B of them) and the waypointer's ``RoadOption`` value (an int, or B) -- and returns float64 numpy ``[B,3]`` =
+    (steer, throttle, brake), the numbers of a ``carla.VehicleControl``.
+
+    It holds a :class:`PolicyTick` (``agent.tick``; ``reset()``, ``reseed()``, ``last`` and ``draws_done`` are the tick's) whose
+    first launch is ``pmoe_sensor_push`` -- Crop -> Resize -> ToTensor straight from the BGRA bytes into the frame ring, bit-exact
+    with the PIL chain -- and whose last one is ``pmoe_control_postprocess``.  Per step: the frame goes into one pinned uint8
+    buffer, speed / ``speed_factor`` (divided in double, rounded to f32 once) and the one-hot command (index ``cmd - 1``, or 3
+    when that is negative) into one pinned f32 buffer, two non-blocking uploads, the plan (``mode="eager"``: the same launches
+    through the engine's Python), one 24 B download per batch row, one event wait.  Nothing is allocated per step; the
+    coefficient tables are built once.  Weight, buffer, dtype and device changes are noticed like the tick notices them."""
+
+    def __init__(self, model, sensor=(600, 800), crop=(125, 90), size=(224, 224), batch=1, mode="plan", seed=0, speed_factor=10.0):
+        if mode not in ("eager", "plan"):
+            raise ValueError(f"AgentStep: mode must be 'eager' or 'plan', got {mode!r}")
+        if model.training:
+            raise RuntimeError("AgentStep runs the eval-mode chain: call model.eval() first")
+        self.H0, self.W0 = int(sensor[0]), int(sensor[1])
+        self.top, self.bottom = int(crop[0]), int(crop[1])
+        self.rows = self.H0 - self.top - self.bottom
+        h, w = int(size[0]), int(size[1])
+        if self.top < 0 or self.bottom < 0 or self.rows < 1 or self.W0 < 1:
+            raise ValueError(f"AgentStep: crop ({self.top}, {self.bottom}) leaves no rows of a {self.H0} x {self.W0} frame")
+        if batch < 1 or h < 1 or w < 1:
+            raise ValueError("AgentStep: batch and size must be positive")
+        self.model, self.B, self.speed_factor = model, int(batch), float(speed_factor)
+        self._hcoeffs, self._vcoeffs = _coeffs(self.W0, w), _coeffs(self.rows, h)
+        self.tile = ops.sensor_tile(self._vcoeffs[1], w)
+        self._frame_dev = self._control_dev = self._meas_dev = self._htable = self._vtable = None
+        self.tick = _SensorTick(self, model, batch=self.B, height=h, width=w, mode=mode, seed=seed)
+        # ---- the host side of a step: pinned, written in place
+        self._frame_host = torch.empty(self.B, self.H0, self.W0, 4, dtype=torch.uint8, pin_memory=True)
+        self._meas_host = torch.zeros(self._meas_dev.numel(), dtype=torch.float32, pin_memory=True)
+        self._control_host = torch.zeros(self.B, 3, dtype=torch.float64, pin_memory=True)
+        self._frame_np, self._meas_np, self._control_np = (t.numpy() for t in (self._frame_host, self._meas_host, self._control_host))
+        self._done = torch.cuda.Event()
+
+    _ALIGN = 64          # floats: the command rows start on a 256-byte boundary of the measurement buffer
+
+    def _device_buffers(self, tick, dev):
+        """the staging frame, the tables, the measurement buffer (``tick.static_in[1:]`` become two views of it: one upload) and
+        the control, on ``dev``"""
+        if self._frame_dev is not None and self._frame_dev.device == dev:
+            return
+        n_speed, n_cmd = tick.static_in[1].shape[1], tick.static_in[2].shape[1]
+        if n_speed != 1:
+            raise ValueError(f"AgentStep: the model's speed encoder takes {n_speed} numbers, the agent measures one")
+        self.n_commands = n_cmd
+        self._cmd_at = -(-self.B // self._ALIGN) * self._ALIGN
+        i32 = torch.int32
+        with torch.cuda.device(dev):
+            self._frame_dev = torch.zeros(self.B, self.H0, self.W0, 4, dtype=torch.uint8, device=dev)
+            self._htable, self._vtable = ((k, torch.tensor(b, dtype=i32, device=dev), torch.tensor(c, dtype=i32, device=dev))
+                                          for k, b, c in (self._hcoeffs, self._vcoeffs))
+            self._meas_dev = torch.zeros(self._cmd_at + self.B * n_cmd, dtype=torch.float32, device=dev)
+            self._control_dev = torch.zeros(self.B, 3, dtype=torch.float64, device=dev)
+        tick.static_in[1] = self._meas_dev[:self.B].view(self.B, 1)
+        tick.static_in[2] = self._meas_dev[self._cmd_at:].view(self.B, n_cmd)
+
+    @staticmethod
+    def measurements(spd, cmd, batch, speed_factor, n_commands):
+        """-> (speed f32 [B], one-hot command f32 [B, n_commands]) as ``image_agent.py:146-157`` builds them: the speed divided
+        in double and rounded to f32 once; the command's index is ``cmd - 1``, or 3 when that is negative; an index the one-hot
+        row does not have is a ``ValueError`` (the reference's ``scatter_`` fails there)."""
+        speed = np.asarray(spd, dtype=np.float64).reshape(-1)
+        command = np.asarray(cmd).reshape(-1)
+        if speed.size != batch or command.size != batch:
+            raise ValueError(f"AgentStep: {batch} speed(s) and command(s) expected, got {speed.size} and {command.size}")
+        if command.dtype.kind not in "iu":
+            raise TypeError("AgentStep: the command is the RoadOption's integer value")
+        index = command.astype(np.int64) - 1
+        index[index < 0] = 3
+        if (index >= n_commands).any():
+            raise ValueError(f"AgentStep: command {command.tolist()} has no place in a one-hot row of {n_commands}")
+        onehot = np.zeros((batch, n_commands), dtype=np.float32)
+        onehot[np.arange(batch), index] = 1.0
+        return (speed / float(speed_factor)).astype(np.float32), onehot
+
+    # ------------------------------------------------------------------ the tick's state
+    last = property(lambda self: self.tick.last)
+    draws_done = property(lambda self: self.tick.draws_done)
+
+    def reset(self):
+        self.tick.reset()
+
+    def reseed(self, seed):
+        self.tick.reseed(seed)
+
+    # ------------------------------------------------------------------ one step
+    def step(self, bgra, spd, cmd):
+        if self.model.training:
+            raise RuntimeError("AgentStep runs the eval-mode chain: call model.eval() first")
+        shape = (self.B, self.H0, self.W0, 4)
+        if not ((isinstance(bgra, np.ndarray) and bgra.dtype == np.uint8) or
+                (isinstance(bgra, torch.Tensor) and bgra.dtype == torch.uint8 and not bgra.is_cuda)):
+            raise TypeError("AgentStep: the frame is a uint8 numpy array or CPU tensor [H0,W0,4] (B, G, R, A)")
+        if tuple(bgra.shape) != shape and not (self.B == 1 and tuple(bgra.shape) == shape[1:]):
+            raise ValueError(f"AgentStep: the frame must be {shape[1:] if self.B == 1 else shape}, got {tuple(bgra.shape)}")
+        speed, onehot = self.measurements(spd, cmd, self.B, self.speed_factor, self.n_commands)
+        tick = self.tick
+        tick._fresh()                            # (first: a model that moved takes the device buffers with it)
+        if isinstance(bgra, torch.Tensor):
+            self._frame_host.copy_(bgra.reshape(shape))
+        else:
+            np.copyto(self._frame_np, bgra.reshape(shape))
+        self._meas_np[:self.B] = speed
+        self._meas_np[self._cmd_at:] = onehot.reshape(-1)
+        with torch.cuda.device(self._frame_dev.device):
+            self._frame_dev.copy_(self._frame_host, non_blocking=True)
+            self._meas_dev.copy_(self._meas_host, non_blocking=True)
+            tick._issue()
+            self._control_host.copy_(self._control_dev, non_blocking=True)
+            self._done.record()
+        self._done.synchronize()
+        return self._control_np.copy()

@@ -879,7 +879,58 @@ def mixture_draw(probs, mean, std, state, raw, punet_actions=None, blend=None, o
           "pmoe_mixture_draw")
 
 
+SENSOR_LDS_BYTES = 64 * 1024       # csrc/agent.hip: the staged rows of one tile of pmoe_sensor_push
+
+
+def sensor_tile(vbounds, wout):
+    """The tile of ``sensor_push`` for the vertical bound table ``vbounds`` (``[[first tap, taps], ...]`` per output row, from
+    ``preprocess._coeffs``) and ``wout`` output columns -> ``(tile_rows, tile_in_rows)``: the most output rows per workgroup, of
+    8, 4, 2, 1, whose source rows -- from the first tap of a tile's first row to the last tap of any of its rows -- fit the LDS
+    (``tile_in_rows * wout * 3 <= SENSOR_LDS_BYTES``); ``tile_rows = 1`` whether it fits or not (the entry point says so)."""
+    for tile_rows in (8, 4, 2, 1):
+        need = max(max(lo + n for lo, n in vbounds[y0:y0 + tile_rows]) - vbounds[y0][0] for y0 in range(0, len(vbounds), tile_rows))
+        if need * wout * 3 <= SENSOR_LDS_BYTES or tile_rows == 1:
+            return tile_rows, max(need, 1)
+
+
+def sensor_push(bgra, ring, row0, rows, htable, vtable, tile, nhwc=None):
+    """Camera frame into the history ring in one launch (``pmoe_sensor_push``): ``bgra`` uint8 [B,H0,W0,4] on the device (B, G,
+    R, A) -> Crop (rows ``row0 .. row0 + rows - 1``) -> Resize -> ToTensor becomes slot T-1 of ``ring`` f32 [B,T,3,h,w], the older
+    slots move down -- what ``history_push(ring, FramePreprocessor(...)(rgb), nhwc)`` gives, bit for bit.  ``htable`` / ``vtable``:
+    ``(ksize, bounds, coeffs)`` with the int32 device tensors of ``preprocess._coeffs(W0, w)`` / ``(rows, h)``; ``tile``:
+    ``sensor_tile`` of the vertical bounds."""
+    if bgra.dim() != 4 or bgra.shape[-1] != 4 or ring.dim() != 5 or ring.shape[0] != bgra.shape[0] or ring.shape[2] != 3:
+        raise ValueError(f"sensor_push: bgra [B,H0,W0,4] and ring [B,T,3,h,w], got {tuple(bgra.shape)} and {tuple(ring.shape)}")
+    b, h0, w0, _ = bgra.shape
+    t, h, w = ring.shape[1], ring.shape[3], ring.shape[4]
+    (hk, hb, hc), (vk, vb, vc) = htable, vtable
+    if tuple(hb.shape) != (w, 2) or tuple(hc.shape) != (w, hk) or tuple(vb.shape) != (h, 2) or tuple(vc.shape) != (h, vk):
+        raise ValueError(f"sensor_push: the tables are not those of a {w0} -> {w} / {rows} -> {h} resize")
+    cp = nd = 0
+    if nhwc is not None:
+        cp, nd = nhwc.shape[-1], dt(nhwc)
+        if tuple(nhwc.shape) != (b, h, w, cp) or cp < 3 or (cp * nhwc.element_size()) % 16:
+            raise ValueError(f"sensor_push: nhwc must be [{b},{h},{w},Cp >= 3] in whole 16-byte vectors, got {tuple(nhwc.shape)}")
+    i32 = torch.int32
+    rc = load().pmoe_sensor_push(ptr(bgra, "bgra", torch.uint8), ptr(ring, "ring", torch.float32), b, t, h0, w0, row0, rows, h, w,
+                                 ptr(hb, "hbounds", i32), ptr(hc, "hcoeffs", i32), hk, ptr(vb, "vbounds", i32),
+                                 ptr(vc, "vcoeffs", i32), vk, tile[0], tile[1], ptr(nhwc, "nhwc"), cp, nd, stream_ptr())
+    if rc == hip.ERR_UNSUPPORTED:
+        raise NotImplementedError(f"sensor_push: {rows} source rows -> {h} x {w}: a tile of {tile[0]} output row(s) reads {tile[1]} "
+                                  f"source rows, {tile[1] * w * 3} bytes of resampled rows where a workgroup keeps {SENSOR_LDS_BYTES}")
+    check(rc, "pmoe_sensor_push")
+
+
+def control_postprocess(actions, control):
+    """``actions`` f32 [B,2] -> ``control`` f64 [B,3] = (steer, throttle, brake): the rule of ``include/pmoe_hip.h``"""
+    if actions.dim() != 2 or actions.shape[1] != 2 or tuple(control.shape) != (actions.shape[0], 3):
+        raise ValueError(f"control_postprocess: actions [B,2] and control [B,3], got {tuple(actions.shape)} and {tuple(control.shape)}")
+    check(load().pmoe_control_postprocess(ptr(actions, "actions", torch.float32), ptr(control, "control", torch.float64),
+                                          actions.shape[0], stream_ptr()), "pmoe_control_postprocess")
+
+
 for _n in ("maxpool2_fwd", "pixel_shuffle2", "copy_window", "action_head_fwd", "action_head_bwd", "action_loss",
            "blend_fwd", "blend_bwd", "maxpool2_bwd", "pixel_unshuffle2", "add_window", "nhwc_to_nchw", "seg_loss_fwd",
-           "seg_loss_bwd", "cat_windows", "dice_score", "dropout2d_table", "channel_scale", "history_push", "mixture_draw"):
+           "seg_loss_bwd", "cat_windows", "dice_score", "dropout2d_table", "channel_scale", "history_push", "mixture_draw",
+           "sensor_push", "control_postprocess"):
     globals()[_n] = _timed(globals()[_n])
