@@ -35,6 +35,40 @@ def r64(c):
     return (c + 63) // 64 * 64
 
 
+class BNCoef:
+    """The coefficients of one BatchNorm evaluation: ONE f32 block [4, E, C] whose rows are, in this order, mean | invstd | scale |
+    shift -- the layout the fused launches read whole (``bn_coef=`` of conv2d_prepare, ``bn_fuse=`` of conv2d_wgrad) -- with the
+    rows as named [E, C] views for the pass kernels, and ``rpe``, the rows per expert the statistics were taken over."""
+    __slots__ = ("block", "mean", "invstd", "scale", "shift", "rpe")
+
+    def __init__(self, E, C_, rpe, dev):
+        self.block, self.rpe = torch.empty(4, E, C_, dtype=F32, device=dev), rpe
+        self.mean, self.invstd, self.scale, self.shift = self.block.unbind(0)
+
+
+class Partials(collections.namedtuple("Partials", "t rows E")):
+    """Partial sums of a streaming reduction: an f32 tensor of ``rows`` rows for each of ``E`` experts (images, for the GAP sums)."""
+    __slots__ = ()
+
+    @classmethod
+    def of_epilogue(cls, stats, E):
+        """the statistics buffer [E * rows, 2, C] a conv epilogue left (``run.stats`` of a prepared launch)"""
+        return cls(stats, stats.shape[0] // E, E)
+
+    def fold(self, width, cap=128):
+        """deterministic second stage: [E][rows][width] -> at most 128 rows where a finalize kernel folds only ``cap`` by itself"""
+        if self.rows <= cap:          # (the BatchNorm finalize kernels: cap = 2048, they take that many rows over 16 partial lanes)
+            return self
+        small = torch.empty(self.E, 128, width, dtype=F32, device=self.t.device)
+        ops.reduce_partials(self.t, small, self.E, self.rows, 128, width)
+        return Partials(small, 128, self.E)
+
+
+# the fusion hand-offs a Var carries besides Partials and BNCoef (DESIGN.md section 6 says who writes and who reads each)
+BNSource = collections.namedtuple("BNSource", "z layer coef")        # Var.bn_src
+BNFused = collections.namedtuple("BNFused", "g coef c1 c2")          # Var.bn_fused
+
+
 class Var:
     """A device activation [N,H,W,ld] (+ channel window) with its gradient slot."""
     __slots__ = ("t", "coff", "c", "g", "needs_grad", "act", "drop_p", "base", "gap_part", "bn_src", "bn_part", "f8", "bn_defer",
@@ -43,13 +77,13 @@ class Var:
     def __init__(self, t, c=None, coff=0, needs_grad=False, base=None):
         self.t, self.coff, self.c = t, coff, (c if c is not None else t.shape[-1])
         self.g, self.needs_grad, self.act, self.drop_p, self.base = None, needs_grad, hip.ACT_NONE, 0.0, base
-        self.gap_part = None                 # (part [N,nparts,C], nparts): channel sums left by the pass that wrote t (_bn, want_gap)
-        self.bn_src = None                   # (z, layer, coef [4,E,C], rpe): t = relu(BatchNorm(z)) in train mode (_bn)
-        self.bn_part = None                  # (part, nparts): that BatchNorm's backward reductions, left by the consumer's dgrad
+        self.gap_part = None                 # Partials [N,rows,C]: channel sums left by the pass that wrote t (_bn, want_gap)
+        self.bn_src = None                   # BNSource: t = relu(BatchNorm(z)) in train mode (_bn)
+        self.bn_part = None                  # Partials: that BatchNorm's backward reductions, left by the consumer's dgrad
         self.f8 = None                       # the same activation as e4m3(t * in_scale) bytes (fp8 policy: _bn, want_f8)
         self.bn_defer = False                # t feeds a BatchNorm and the ONLY consumer of dL/dt applies that BatchNorm's backward on load
-        self.bn_fused = None                 # (g, coef, c1, c2) left by _bn_bwd for that consumer instead of dL/dt (round 4: _stem_in_bwd)
-        self.pending_bn = None               # (coef [4,E,C], rpe): t is the PRE-activation z of a BatchNorm + ReLU that its one consumer
+        self.bn_fused = None                 # BNFused left by _bn_bwd_reduced for that consumer instead of dL/dt (_stem_in_bwd)
+        self.pending_bn = None               # BNCoef: t is the PRE-activation z of a BatchNorm + ReLU that its one consumer
                                              # applies on load (PMOE_RES_INBN) or engine_punet._materialize writes out (untaped U-Net forward)
 
     @property
@@ -69,8 +103,7 @@ class Var:
             self.g = g
 
     def window(self, coff, c):
-        v = Var(self.t, c, coff, self.needs_grad, base=self if self.base is None else self.base)
-        return v
+        return Var(self.t, c, coff, self.needs_grad, base=self if self.base is None else self.base)
 
 
 PackSinks = collections.namedtuple("PackSinks", "gen by_param")      # ExpertGroupEngine.pack_sinks
@@ -497,8 +530,8 @@ class ExpertGroupEngine:
 
     def _conv(self, x, layer, *, bias=True, act=hip.ACT_NONE, drop_p=0.0, out=None, out_coff=0, in_shared=False,
               want_stats=False, tape=True, in_bn=None):
-        """``in_bn``: x is the pre-activation z of a BatchNorm + ReLU and in_bn its [4, E, C] coefficient block -- the launch applies
-        them on load (PMOE_RES_INBN: untaped forward launches; the caller has asked whether such a launch is served)."""
+        """``in_bn``: x is the pre-activation z of a BatchNorm + ReLU and in_bn its BNCoef -- the launch applies them on load
+        (PMOE_RES_INBN: untaped forward; the caller has asked whether it is served).  ``want_stats``: -> (o, the epilogue's Partials)."""
         Ho, Wo, o = self._conv_out(x, layer, out, out_coff)
         f8 = layer.w_f8 is not None
         if f8 and (bias is not False or act != hip.ACT_NONE):
@@ -507,7 +540,7 @@ class ExpertGroupEngine:
         kw = dict(cin=layer.cinp, cout=layer.cout_st, coutp=layer.coutp, ipe=self.B, ks=layer.ks, stride=layer.stride,
                   pad=layer.pad, in_shared=in_shared, in_coff=x.coff, out_coff=o.coff, bias=layer.bias_packed if bias else None,
                   act=act, drop_p=drop_p, seed=seed, stats=True if want_stats else None, out_scale=layer.oscale if f8 else None,
-                  in_scale=self.fp8_in_scale, **(dict(res_mode=hip.RES_INBN, bn_coef=in_bn) if in_bn is not None else {}))
+                  in_scale=self.fp8_in_scale, **(dict(res_mode=hip.RES_INBN, bn_coef=in_bn.block) if in_bn is not None else {}))
         # e4m3 activations left by the producing BatchNorm pass: the block-scaled MFMA kernel (no conversion in the loader),
         # where it serves this launch; else the bf16 input through the converting loaders
         run = None
@@ -518,7 +551,6 @@ class ExpertGroupEngine:
         flop = 2.0 * self.N * Ho * Wo * layer.cout * layer.cin * layer.taps
         ops.set_meta(flop=flop, name=layer.name)
         run.launch()
-        stats = run.stats
         o.act, o.drop_p = act, drop_p
         if self.debug_acts is not None and act == hip.ACT_RELU:
             self.debug_acts[layer.name] = (o.t, o.coff, layer.cout)
@@ -527,7 +559,7 @@ class ExpertGroupEngine:
             out.needs_grad = True
         if tape and self.taping and o.needs_grad:
             self.tape.append(lambda: self._conv_bwd(x, layer, o, in_shared, flop))
-        return (o, stats) if want_stats else o
+        return (o, Partials.of_epilogue(run.stats, self.E)) if want_stats else o
 
     def _next_seed(self):
         """the seed of the next dropout site: a function of (base_seed, site order), see _begin"""
@@ -547,7 +579,6 @@ class ExpertGroupEngine:
         dy = o.grad
         if dy is None:
             return
-        E = self.E
         if layer.trainable and self.overlap_wgrad:
             # weight / bias gradients on a second HIP stream: they depend on nothing downstream, so the MFMA-bound
             # wgrad kernel overlaps the HBM-bound BatchNorm-backward passes and the next data gradient of the main stream
@@ -613,15 +644,14 @@ class ExpertGroupEngine:
         """per-expert column sums [E,C] (f32) of the channel window [coff, coff+C) of ``t``: partial rows over enough
         workgroups to stream at HBM rate, then fixed-order folds (bias gradients of conv layers with many pixels)."""
         E = self.E
-        nparts = self._nparts(rpe)
-        part = torch.empty(E, nparts, 2, C, dtype=F32, device=self.dev)
-        ops.colstats(rpe, t, E, C, part, nparts, ld=t.shape[-1], coff=coff)
-        if nparts > 1:
-            part, nparts = self._fold_parts(part, nparts, 2 * C)
+        part = self._new_partials(rpe, 2, C)
+        ops.colstats(rpe, t, E, C, part.t, part.rows, ld=t.shape[-1], coff=coff)
+        if part.rows > 1:
+            part = part.fold(2 * C)
             one = torch.empty(E, 1, 2, C, dtype=F32, device=self.dev)
-            ops.reduce_partials(part, one, E, nparts, 1, 2 * C)
-            part = one
-        return part[:, 0, 0]
+            ops.reduce_partials(part.t, one, E, part.rows, 1, 2 * C)
+            return one[:, 0, 0]
+        return part.t[:, 0, 0]
 
     def _dgrad_block(self, x, layer, o, dy, flop):
         if x.needs_grad:
@@ -652,66 +682,54 @@ class ExpertGroupEngine:
         if (src is None or x.grad is not None or x.act != hip.ACT_NONE or x.base is not None or x.coff != 0
                 or kw["ks"] != 3 or kw["dilate"] or x.t.dtype != torch.bfloat16):
             return False
-        z, bnl, coef, rpe = src
-        if bnl.C != kw["cout"] or bnl.C != kw["coutp"] or z.t.shape != x.t.shape:      # (the statistics rows are coutp wide)
+        if src.layer.C != kw["cout"] or src.layer.C != kw["coutp"] or src.z.t.shape != x.t.shape:    # (statistics rows: coutp wide)
             return False
-        run = ops.conv2d_prepare(dy, w_dg, g, res=z.t, res_mode=hip.RES_DBN, bn_coef=coef, bn_ipe=self.B, bias=bias, stats=True, **kw)
+        run = ops.conv2d_prepare(dy, w_dg, g, res=src.z.t, res_mode=hip.RES_DBN, bn_coef=src.coef.block, bn_ipe=self.B, bias=bias,
+                                 stats=True, **kw)
         if not run.served():
             return False
         ops.set_meta(flop=flop, name=name + ":dgrad+bnred")
         run.launch()
         x.set_grad(g)
-        x.bn_part = (run.stats, run.stats.shape[0] // self.E)
+        x.bn_part = Partials.of_epilogue(run.stats, self.E)
         return True
 
-    @staticmethod
-    def _nparts(rpe):
-        """partial-sum rows per expert of a streaming reduction: enough workgroups to keep HBM busy
-        (E * nparts blocks of 256 threads), at least 256 rows each."""
-        return min(1024, max(1, rpe // 256))
+    def _new_partials(self, rpe, k, C_):
+        """an unwritten Partials [E, rows, k, C] for a streaming reduction of k sums per channel over rpe rows per expert: enough
+        workgroups to keep HBM busy (E * rows blocks of 256 threads), at least 256 rows each"""
+        nparts = min(1024, max(1, rpe // 256))
+        return Partials(torch.empty(self.E, nparts, k, C_, dtype=F32, device=self.dev), nparts, self.E)
 
-    def _fold_parts(self, part, nparts, width, cap=128):
-        """deterministic second stage: [E][nparts][width] -> at most 128 rows before a finalize kernel (``cap``: what that
-        kernel folds by itself -- the BatchNorm finalize kernels take 2048 rows over 16 partial lanes)."""
-        if nparts <= cap:
-            return part, nparts
-        small = torch.empty(self.E, 128, width, dtype=F32, device=self.dev)
-        ops.reduce_partials(part, small, self.E, nparts, 128, width)
-        return small, 128
-
-    def _bn_coeffs(self, layer, rpe, part=None, nparts=0, z=None, shiftc=None):
-        """scale/shift/mean/invstd [E,C] of a BatchNorm: batch statistics from partial sums (train) or the
-        running buffers (eval); updates the running statistics in train mode (momentum, unbiased var)."""
+    def _bn_coeffs(self, layer, rpe, part=None, z=None, shiftc=None):
+        """-> the BNCoef of a BatchNorm: batch statistics from ``part`` (Partials; None: a colstats pass over z) in train mode or
+        the running buffers (eval); updates the running statistics in train mode (momentum, unbiased var)."""
         E, C_ = self.E, layer.C
-        # one block [mean | invstd | scale | shift][E][C]: the layout PMOE_RES_DBN's data-gradient epilogue reads
-        coef = self._last_coef = torch.empty(4, E, C_, dtype=F32, device=self.dev)
-        mean, invstd, scale, shift = coef[0], coef[1], coef[2], coef[3]
+        k = BNCoef(E, C_, rpe, self.dev)
         if self.training:
             if part is None:
-                nparts = self._nparts(rpe)
-                part = torch.empty(E, nparts, 2, C_, dtype=F32, device=self.dev)
+                part = self._new_partials(rpe, 2, C_)
                 shiftc = torch.empty(E, C_, dtype=F32, device=self.dev)
-                ops.colstats(rpe, z.t, E, C_, part, nparts, shiftc=shiftc)
-            part, nparts = self._fold_parts(part, nparts, 2 * C_, cap=2048)
-            ops.bn_finalize(part, nparts, rpe, self._tab("gamma", layer), self._tab("beta", layer),
-                            self._tab("rm", layer), self._tab("rv", layer), layer.momentum, layer.eps, True, scale,
-                            shift, mean, invstd, E, C_, shiftc)
+                ops.colstats(rpe, z.t, E, C_, part.t, part.rows, shiftc=shiftc)
+            part = part.fold(2 * C_, cap=2048)
+            ops.bn_finalize(part.t, part.rows, rpe, self._tab("gamma", layer), self._tab("beta", layer),
+                            self._tab("rm", layer), self._tab("rv", layer), layer.momentum, layer.eps, True, k.scale,
+                            k.shift, k.mean, k.invstd, E, C_, shiftc)
             self._bn_touched.append(layer)
         else:
-            ops.bn_finalize(scale, 0, rpe, self._tab("gamma", layer), self._tab("beta", layer), self._tab("rm", layer),
-                            self._tab("rv", layer), layer.momentum, layer.eps, False, scale, shift, mean, invstd, E, C_)
-        return scale, shift, mean, invstd
+            ops.bn_finalize(k.scale, 0, rpe, self._tab("gamma", layer), self._tab("beta", layer), self._tab("rm", layer),
+                            self._tab("rv", layer), layer.momentum, layer.eps, False, k.scale, k.shift, k.mean, k.invstd, E, C_)
+        return k
 
     def _bn(self, z, layer, relu, res=None, stats=None, out=None, out_coff=0, want_gap=False, want_f8=False, pool_to=None):
-        """y = [relu](bn(z) [+ res]); train mode: batch statistics (fused conv partials or a colstats pass).
-        want_gap: the pass also leaves the per-image channel sums of y in ``y.gap_part`` (part, nparts) for the ECA block that
-        follows (_eca_conv_folded), instead of a separate pass over y."""
+        """y = [relu](bn(z) [+ res]); train mode: batch statistics (``stats``: the conv epilogue's Partials, else a colstats pass).
+        want_gap: the pass also leaves the per-image channel sums of y in ``y.gap_part`` for the ECA block that follows
+        (_eca_conv_folded), instead of a separate pass over y."""
         E, C_ = self.E, layer.C
         n, h, w, _ = z.t.shape
         rpe = self.B * h * w
-        if stats is not None and stats.shape[2] != C_:
+        if stats is not None and stats.t.shape[2] != C_:
             raise RuntimeError("fused stats width mismatch")
-        scale, shift, mean, invstd = self._bn_coeffs(layer, rpe, stats, stats.shape[0] // E if stats is not None else 0, z)
+        k = self._bn_coeffs(layer, rpe, stats, z)
         # out: write into the channel window [out_coff, out_coff + C) of a wider buffer (U-Net skip concatenation)
         # taped: the window gets its OWN (dense) gradient slot -- its consumers' backward fills it (U-Net skip: the
         # max-pool backward adds the concatenation buffer's gradient window, engine_punet._maxpool2)
@@ -724,85 +742,89 @@ class ExpertGroupEngine:
         ops.set_meta(name=layer.name, bytes=z.t.numel() * z.t.element_size() * (3 if res is not None else 2))
         if want_gap and res is None and out is None:
             nparts = self._gap_parts(h * w)
-            part = torch.empty(n, nparts, C_, dtype=F32, device=self.dev)
-            ops.bn_apply_gap(z.t, y.t, scale, shift, mean, part, nparts, self.B, relu)
-            y.gap_part = (part, nparts)
+            y.gap_part = Partials(torch.empty(n, nparts, C_, dtype=F32, device=self.dev), nparts, n)
+            ops.bn_apply_gap(z.t, y.t, k.scale, k.shift, k.mean, y.gap_part.t, nparts, self.B, relu)
         elif pool_to is not None and res is None:
             # round 4: the pass also leaves MaxPool2d(2, 2) of its output in ``pool_to`` (U-Net down blocks, engine_punet._unet_fwd)
-            ops.bn_apply_pool2(z.t, y.t, pool_to, scale, shift, mean, self.B, E, C_, relu, y_coff=y.coff)
+            ops.bn_apply_pool2(z.t, y.t, pool_to, k.scale, k.shift, k.mean, self.B, E, C_, relu, y_coff=y.coff)
         else:
             if want_f8 and out is None and self.dtype == torch.bfloat16:
                 y.f8 = torch.empty(y.t.shape, dtype=torch.uint8, device=self.dev)      # e4m3(y * in_scale) for the fp8 consumer
-            ops.bn_apply(z.t, res.t if res is not None else None, y.t, scale, shift, mean, rpe, E, C_, relu, y_coff=y.coff,
+            ops.bn_apply(z.t, res.t if res is not None else None, y.t, k.scale, k.shift, k.mean, rpe, E, C_, relu, y_coff=y.coff,
                          y_fp8=y.f8, in_scale=self.fp8_in_scale)
         if self.debug_acts is not None and relu:
             self.debug_acts[layer.name] = (y.t, y.coff, C_)
         if relu and res is None and out is None and self.taping and self.training and self.dtype == torch.bfloat16 and z.needs_grad:
-            y.bn_src = (z, layer, self._last_coef, rpe)
+            y.bn_src = BNSource(z, layer, k)
         y.needs_grad = z.needs_grad or layer.trainable or (res is not None and res.needs_grad)
         if out is not None and y.needs_grad:
             out.needs_grad = True
         if self.taping and y.needs_grad:
             train = self.training
-            self.tape.append(lambda: self._bn_bwd(z, layer, y, res, relu, scale, shift, mean, invstd, rpe, train))
+            self.tape.append(lambda: self._bn_bwd(z, layer, y, res, relu, k, train))
         return y
 
-    def _bn_bwd(self, z, layer, y, res, relu, scale, shift, mean, invstd, rpe, train):
+    def _bn_bwd(self, z, layer, y, res, relu, k, train):
+        """backward of _bn: from the reductions the consumer's data gradient left in ``y.bn_part``, else with a reduce pass of its own"""
         dy = y.grad
-        if self.debug_grads is not None and dy is not None:
-            self.debug_grads[layer.name] = dy.detach().clone()      # gradient w.r.t. this BN's (post-activation) output
-        # without a residual the ReLU mask is a function of z alone: skip reading the saved output
-        ysrc = y.t if (res is not None or not relu) else None
         if dy is None:
             return
-        E, C_ = self.E, layer.C
-        nb = z.t.numel() * z.t.element_size()
-        if y.bn_part is not None:
-            # the consumer's data gradient (PMOE_RES_DBN) already masked dy and reduced it: finalize + apply only
-            part, nparts = y.bn_part
-            if part.shape[2] != C_:
-                raise RuntimeError("BatchNorm reductions from the data-gradient epilogue: channel count mismatch")
-            part, nparts = self._fold_parts(part.view(E, nparts, 2 * C_), nparts, 2 * C_, cap=2048)
-            c1, c2 = self._bn_bwd_finalize(layer, part, nparts, rpe, train)
-            if z.needs_grad:
-                if z.grad is not None:
-                    raise RuntimeError("BN input consumed twice")
-                if z.bn_defer:
-                    # the only consumer of dz evaluates it on load from (g, z): no apply pass, dz is never written
-                    z.bn_fused = (dy, y.bn_src[2], c1, c2)
-                    z.set_grad(dy)
-                    return
-                dz = torch.empty_like(z.t)
-                ops.set_meta(name=layer.name, bytes=nb * 3)
-                ops.bn_bwd_apply(dy, None, z.t, mean, invstd, scale, shift, c1, c2, dz, None, rpe, E, C_, False)
-                z.set_grad(dz)
-            return
-        nparts = self._nparts(rpe)
-        part = torch.empty(E, nparts, 2, C_, dtype=F32, device=self.dev)
-        want_res = res is not None and res.needs_grad
-        # residual blocks: the reduce pass also stores the masked gradient (the residual branch needs it anyway), and the
-        # apply pass then reads that instead of dy AND the saved output: one tensor pass less per block
-        gm = torch.empty_like(z.t) if (want_res and relu and ysrc is not None) else None
-        ops.set_meta(name=layer.name, bytes=nb * ((3 if ysrc is not None else 2) + (gm is not None)))
-        ops.bn_bwd_reduce(dy, ysrc, z.t, mean, invstd, scale, shift, rpe, E, C_, relu, part, nparts, gmask=gm)
-        part, nparts = self._fold_parts(part, nparts, 2 * C_, cap=2048)
-        c1, c2 = self._bn_bwd_finalize(layer, part, nparts, rpe, train)
-        dz = torch.empty_like(z.t) if z.needs_grad else None
-        if gm is not None:
-            if dz is not None:
-                ops.set_meta(name=layer.name, bytes=nb * 3)
-                ops.bn_bwd_apply(gm, None, z.t, mean, invstd, scale, shift, c1, c2, dz, None, rpe, E, C_, False)
-        else:
-            gm = torch.empty_like(z.t) if want_res else None
-            if dz is None and gm is None:
-                return
-            if dz is None:
-                dz = torch.empty_like(z.t)
-            ops.set_meta(name=layer.name, bytes=nb * (2 + (ysrc is not None) + 1 + (gm is not None)))
-            ops.bn_bwd_apply(dy, ysrc, z.t, mean, invstd, scale, shift, c1, c2, dz, gm, rpe, E, C_, relu)
         if self.debug_grads is not None:
+            self.debug_grads[layer.name] = dy.detach().clone()      # gradient w.r.t. this BN's (post-activation) output
+        if y.bn_part is not None:
+            return self._bn_bwd_reduced(z, layer, y, dy, k, train)
+        self._bn_bwd_own(z, layer, y, dy, res, relu, k, train)
+
+    def _bn_bwd_reduced(self, z, layer, y, dy, k, train):
+        """the consumer's data gradient (PMOE_RES_DBN, _dgrad_with_bn_reduce) already masked dy and reduced it: finalize + apply
+        only -- and not even the apply where dz's one consumer evaluates it on load (``z.bn_defer``: _stem_in_bwd)"""
+        E, C_ = self.E, layer.C
+        if y.bn_part.t.shape[2] != C_:
+            raise RuntimeError("BatchNorm reductions from the data-gradient epilogue: channel count mismatch")
+        part = y.bn_part.fold(2 * C_, cap=2048)
+        c1, c2 = self._bn_bwd_finalize(layer, part, k.rpe, train)
+        if not z.needs_grad:
+            return
+        if z.grad is not None:
+            raise RuntimeError("BN input consumed twice")
+        if z.bn_defer:
+            # the only consumer of dz evaluates it on load from (g, z): no apply pass, dz is never written
+            z.bn_fused = BNFused(dy, y.bn_src.coef, c1, c2)
+            z.set_grad(dy)
+            return
+        dz = torch.empty_like(z.t)
+        ops.set_meta(name=layer.name, bytes=z.t.numel() * z.t.element_size() * 3)
+        ops.bn_bwd_apply(dy, None, z.t, k.mean, k.invstd, k.scale, k.shift, c1, c2, dz, None, k.rpe, E, C_, False)
+        z.set_grad(dz)
+
+    def _bn_bwd_own(self, z, layer, y, dy, res, relu, k, train):
+        """reduce pass, finalize, apply pass (the route of every BatchNorm whose consumer left no reductions)"""
+        E, C_, rpe = self.E, layer.C, k.rpe
+        nb = z.t.numel() * z.t.element_size()
+        want_res = res is not None and res.needs_grad
+        # the one decision.  Saved output: read only where the ReLU mask is not a function of z alone (a residual was added) or
+        # there is no ReLU.  The shortcut's gradient gm, where wanted: behind a ReLU the REDUCE pass stores the masked gradient and
+        # the apply pass then reads that instead of dy AND the saved output (one tensor pass less per residual block); without a
+        # ReLU the APPLY pass writes it next to dz (into a scratch dz where z itself takes no gradient)
+        ysrc = y.t if (res is not None or not relu) else None
+        gm_by_reduce, gm_by_apply = want_res and relu, want_res and not relu
+        part = self._new_partials(rpe, 2, C_)
+        gm = torch.empty_like(z.t) if gm_by_reduce else None
+        ops.set_meta(name=layer.name, bytes=nb * ((3 if ysrc is not None else 2) + gm_by_reduce))
+        ops.bn_bwd_reduce(dy, ysrc, z.t, k.mean, k.invstd, k.scale, k.shift, rpe, E, C_, relu, part.t, part.rows, gmask=gm)
+        c1, c2 = self._bn_bwd_finalize(layer, part.fold(2 * C_, cap=2048), rpe, train)
+        dz = torch.empty_like(z.t) if z.needs_grad else None
+        if gm_by_apply:
+            gm = torch.empty_like(z.t)
+            dz = dz if dz is not None else torch.empty_like(z.t)
+        if dz is not None:
+            g_in, y_in, act = (gm, None, False) if gm_by_reduce else (dy, ysrc, relu)
+            ops.set_meta(name=layer.name, bytes=nb * (3 + (y_in is not None) + gm_by_apply))
+            ops.bn_bwd_apply(g_in, y_in, z.t, k.mean, k.invstd, k.scale, k.shift, c1, c2, dz, gm if gm_by_apply else None,
+                             rpe, E, C_, act)
+        if self.debug_grads is not None and dz is not None:
             self.debug_grads[layer.name + ":dz"] = dz.detach().clone()
-            self.debug_grads[layer.name + ":stats"] = (mean.clone(), invstd.clone(), c1.clone(), c2.clone())
+            self.debug_grads[layer.name + ":stats"] = (k.mean.clone(), k.invstd.clone(), c1.clone(), c2.clone())
         if z.needs_grad:
             if z.grad is not None:
                 raise RuntimeError("BN input consumed twice")
@@ -812,13 +834,13 @@ class ExpertGroupEngine:
                 raise RuntimeError("residual gradient slot already filled")
             res.set_grad(gm)
 
-    def _bn_bwd_finalize(self, layer, part, nparts, rpe, train, out=None):
-        """folded reductions of a BatchNorm backward -> d gamma / d beta in their slots and the two per-channel terms (c1, c2)
+    def _bn_bwd_finalize(self, layer, part, rpe, train, out=None):
+        """folded reductions (Partials) of a BatchNorm backward -> d gamma / d beta in their slots and the two per-channel terms (c1, c2)
         [E,C] of dz, written to ``out`` if the caller has already handed those tensors to a kernel"""
         E, C_ = self.E, layer.C
         c1, c2 = out or (torch.empty(E, C_, dtype=F32, device=self.dev) for _ in range(2))
         dgamma, dbeta, store = self._bn_grad_views(layer)
-        ops.bn_bwd_finalize(part, nparts, rpe, dgamma, dbeta, c1, c2, E, C_)
+        ops.bn_bwd_finalize(part.t, part.rows, rpe, dgamma, dbeta, c1, c2, E, C_)
         if store is not None:
             store()
         if not train:          # eval-mode BN is an affine map: no batch-statistics terms
@@ -837,22 +859,22 @@ class ExpertGroupEngine:
         E, C_ = self.E, self.bn_c2.C
         n, h, w, _ = z2.t.shape
         rpe = self.B * h * w
-        sc2, sh2, mu2, is2 = self._bn_coeffs(self.bn_c2, rpe, stats, stats.shape[0] // E if stats is not None else 0, z2)
-        nparts = self._nparts(rpe)
-        part = part_x = None
+        k2 = self._bn_coeffs(self.bn_c2, rpe, stats, z2)
+        part = part_x = shc = None
         if self.training:
-            part = torch.empty(E, nparts, 2, C_, dtype=F32, device=self.dev)
+            part = self._new_partials(rpe, 2, C_)
             shc = torch.empty(E, C_, dtype=F32, device=self.dev)
             if self.taping:      # channel moments of z2 for the pooled-pass backward (stem_tail.hip)
-                part_x = torch.empty(E, nparts, 3, C_, dtype=F32, device=self.dev)
-            ops.stem_tail_stats(z2.t, sc2, sh2, mu2, part, nparts, E, self.B, shiftc=shc, part_x=part_x)
+                part_x = self._new_partials(rpe, 3, C_)
+            ops.stem_tail_stats(z2.t, k2.scale, k2.shift, k2.mean, part.t, part.rows, E, self.B, shiftc=shc,
+                                part_x=part_x.t if part_x is not None else None)
             if part_x is not None:
-                part_x, npx = self._fold_parts(part_x, nparts, 3 * C_)
-        sc1, sh1, mu1, is1 = self._bn_coeffs(self.bn1, rpe, part, nparts, shiftc=shc if self.training else None)
+                part_x = part_x.fold(3 * C_)
+        k1 = self._bn_coeffs(self.bn1, rpe, part, shiftc=shc)
         ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
         y = Var(self._new(n, ho, wo, C_))
         am = torch.empty(n, ho, wo, C_, dtype=torch.uint8, device=self.dev)
-        ops.stem_tail_pool(z2.t, y.t, am, sc2, sh2, sc1, sh1, mu2, mu1, self.B)
+        ops.stem_tail_pool(z2.t, y.t, am, k2.scale, k2.shift, k1.scale, k1.shift, k2.mean, k1.mean, self.B)
         if self.debug_acts is not None:
             self.debug_acts["stem_tail"] = (am, y.t)      # winning tap | 0x80 if the winner's a2 > 0; a3 > 0 <=> y > 0
         y.needs_grad = z2.needs_grad or self.bn_c2.trainable or self.bn1.trainable
@@ -864,28 +886,25 @@ class ExpertGroupEngine:
                 if dp is None:
                     return
                 c11, c21, c12, c22 = (torch.empty(E, C_, dtype=F32, device=self.dev) for _ in range(4))
-                consts = [sc2, sh2, sc1, sh1, mu1, is1, mu2, is2, c11, c21, c12, c22]
-                p1 = torch.empty(E, nparts, 2, C_, dtype=F32, device=self.dev)
+                consts = [k2.scale, k2.shift, k1.scale, k1.shift, k1.mean, k1.invstd, k2.mean, k2.invstd, c11, c21, c12, c22]
+                p1 = self._new_partials(rpe, 2, C_)
                 if train and part_x is not None and self.pooled_stem_bwd:
                     # both reductions from ONE pass over the pooled tensors + the forward moments of z2
-                    np4 = self._nparts(self.B * ho * wo)
-                    p4 = torch.empty(E, np4, 4, C_, dtype=F32, device=self.dev)
-                    ops.stem_tail_pooled(y.t, dp, am, consts, p4, np4, E)
-                    p4, np4 = self._fold_parts(p4, np4, 4 * C_)
-                    o1, o2 = (torch.empty(E, 1, 2, C_, dtype=F32, device=self.dev) for _ in range(2))
-                    ops.stem_tail_combine(p4, np4, part_x, npx, consts, rpe, o1, o2, E, C_)
-                    self._bn_bwd_finalize(self.bn1, o1, 1, rpe, train, out=(c11, c21))
-                    self._bn_bwd_finalize(self.bn_c2, o2, 1, rpe, train, out=(c12, c22))
+                    p4 = self._new_partials(self.B * ho * wo, 4, C_)
+                    ops.stem_tail_pooled(y.t, dp, am, consts, p4.t, p4.rows, E)
+                    p4 = p4.fold(4 * C_)
+                    o1, o2 = (Partials(torch.empty(E, 1, 2, C_, dtype=F32, device=self.dev), 1, E) for _ in range(2))
+                    ops.stem_tail_combine(p4.t, p4.rows, part_x.t, part_x.rows, consts, rpe, o1.t, o2.t, E, C_)
+                    self._bn_bwd_finalize(self.bn1, o1, rpe, train, out=(c11, c21))
+                    self._bn_bwd_finalize(self.bn_c2, o2, rpe, train, out=(c12, c22))
                 else:
-                    ops.stem_tail_bwd(1, z2.t, dp, am, None, consts, p1, nparts, E, self.B)
-                    pf, nf = self._fold_parts(p1, nparts, 2 * C_)
-                    self._bn_bwd_finalize(self.bn1, pf, nf, rpe, train, out=(c11, c21))
-                    ops.stem_tail_bwd(2, z2.t, dp, am, None, consts, p1, nparts, E, self.B)
-                    pf, nf = self._fold_parts(p1, nparts, 2 * C_)
-                    self._bn_bwd_finalize(self.bn_c2, pf, nf, rpe, train, out=(c12, c22))
+                    ops.stem_tail_bwd(1, z2.t, dp, am, None, consts, p1.t, p1.rows, E, self.B)
+                    self._bn_bwd_finalize(self.bn1, p1.fold(2 * C_), rpe, train, out=(c11, c21))
+                    ops.stem_tail_bwd(2, z2.t, dp, am, None, consts, p1.t, p1.rows, E, self.B)
+                    self._bn_bwd_finalize(self.bn_c2, p1.fold(2 * C_), rpe, train, out=(c12, c22))
                 if z2.needs_grad:
                     dz = torch.empty_like(z2.t)
-                    ops.stem_tail_bwd(3, z2.t, dp, am, dz, consts, p1, nparts, E, self.B)
+                    ops.stem_tail_bwd(3, z2.t, dp, am, dz, consts, p1.t, p1.rows, E, self.B)
                     z2.set_grad(dz)
             self.tape.append(bwd)
         return y
@@ -915,16 +934,22 @@ class ExpertGroupEngine:
         want = max(16, -(-2048 // max(1, self.N)))
         return max(1, min(want, hw // 1024))
 
+    def _gap_sums(self, x):
+        """-> Partials [n, rows, c]: the per-image channel sums of x over rows partitions of its pixels (one gap_partial pass)"""
+        n, h, w, c = x.t.shape
+        nparts = self._gap_parts(h * w)
+        part = torch.empty(n, nparts, c, dtype=F32, device=self.dev)
+        ops.gap_partial(x.t, None, part, nparts)
+        return Partials(part, nparts, n)
+
     def _eca(self, x, layer, shared, tape=True):
         """y[n] = x[n or n % B] * sigmoid(conv1d(GAP(x)))  (EfficientBlock, basics.py:69-76)."""
         nx, h, w, c = x.t.shape
         hw = h * w
-        nparts = self._gap_parts(hw)
-        part = torch.empty(nx, nparts, c, dtype=F32, device=self.dev)
-        ops.gap_partial(x.t, None, part, nparts)
+        gap = self._gap_sums(x)
         gate = torch.empty(self.N, c, dtype=F32, device=self.dev)
         gapmean = torch.empty(self.N, c, dtype=F32, device=self.dev)
-        ops.eca_gate(part, nparts, hw, self._tab("eca", layer), layer.k, gate, gapmean, self.N, self.B,
+        ops.eca_gate(gap.t, gap.rows, hw, self._tab("eca", layer), layer.k, gate, gapmean, self.N, self.B,
                      self.B if shared else 0, c, layer.creal)
         y = Var(self._new(self.N, h, w, c))
         ops.eca_scale(x.t, gate, y.t, self.B if shared else 0)
@@ -936,10 +961,10 @@ class ExpertGroupEngine:
                 dy = y.grad
                 if dy is None:
                     return
-                dot = torch.empty(self.N, nparts, c, dtype=F32, device=self.dev)
-                ops.gap_partial(dy, x.t, dot, nparts, self.B if shared else 0)
+                dot = torch.empty(self.N, gap.rows, c, dtype=F32, device=self.dev)
+                ops.gap_partial(dy, x.t, dot, gap.rows, self.B if shared else 0)
                 dgap = torch.empty(self.N, c, dtype=F32, device=self.dev)
-                ops.eca_bwd_small(dot, nparts, gate, gapmean, self._tab("eca", layer), layer.k, dgap,
+                ops.eca_bwd_small(dot, gap.rows, gate, gapmean, self._tab("eca", layer), layer.k, dgap,
                                   self._grad_slot("eca", layer).view(self.E, layer.k), self.N, self.B, c, layer.creal)
                 if x.needs_grad:
                     dx = torch.empty_like(x.t)
@@ -957,15 +982,11 @@ class ExpertGroupEngine:
         nx, h, w, c = x.t.shape
         hw = h * w
         N, B_ = self.N, self.B
-        if getattr(x, "gap_part", None) is not None:          # left by the BatchNorm pass that wrote x (_bn, want_gap)
-            part, nparts = x.gap_part
-        else:
-            nparts = self._gap_parts(hw)
-            part = torch.empty(nx, nparts, c, dtype=F32, device=self.dev)
-            ops.gap_partial(x.t, None, part, nparts)
+        # (the sums: left by the BatchNorm pass that wrote x -- _bn, want_gap -- or a pass of their own)
+        gap = x.gap_part if x.gap_part is not None else self._gap_sums(x)
         gate = torch.empty(N, c, dtype=F32, device=self.dev)
         gapmean = torch.empty(N, c, dtype=F32, device=self.dev)
-        ops.eca_gate(part, nparts, hw, self._tab("eca", ecal), ecal.k, gate, gapmean, N, B_, 0, c, ecal.creal)
+        ops.eca_gate(gap.t, gap.rows, hw, self._tab("eca", ecal), ecal.k, gate, gapmean, N, B_, 0, c, ecal.creal)
         wf = torch.empty(N, layer.coutp, layer.taps, layer.cinp, dtype=self.dtype, device=self.dev)
         wd = torch.empty(N, layer.dg_rows, layer.taps, layer.dg_red, dtype=self.dtype, device=self.dev) if x.needs_grad else None
         ops.pack_conv_weights_gated(self._tab("w", layer), gate, wf, wd, N, B_, layer.cout, layer.cin, layer.ks, layer.coutp,
@@ -975,11 +996,11 @@ class ExpertGroupEngine:
         if self._epilogue_stats:
             rows = ops.conv2d_stat_rows(N, h, w, Ho, Wo, layer.cinp, layer.cout_st, layer.coutp, 1, layer.ks, layer.stride,
                                         layer.pad, self.dtype, in_ld=x.t.shape[-1], out_ld=o.t.shape[-1])
-            stats = torch.empty(rows, 2, layer.coutp, dtype=F32, device=self.dev)
+            stats = Partials.of_epilogue(torch.empty(rows, 2, layer.coutp, dtype=F32, device=self.dev), self.E)
         flop = 2.0 * N * Ho * Wo * layer.cout * layer.cin * layer.taps
         ops.set_meta(flop=flop, name=layer.name)
         ops.conv2d(x.t, wf, o.t, cin=layer.cinp, cout=layer.cout_st, coutp=layer.coutp, ipe=1, ks=layer.ks,
-                   stride=layer.stride, pad=layer.pad, stats=stats)
+                   stride=layer.stride, pad=layer.pad, stats=stats.t if stats is not None else None)
         o.needs_grad = x.needs_grad or layer.trainable or ecal.trainable
         if self.taping and o.needs_grad:
             def bwd():
@@ -1003,11 +1024,8 @@ class ExpertGroupEngine:
 
     def _gap_to(self, x, feat, coff):
         n, h, w, c = x.t.shape
-        hw = h * w
-        nparts = self._gap_parts(hw)
-        part = torch.empty(n, nparts, c, dtype=F32, device=self.dev)
-        ops.gap_partial(x.t, None, part, nparts)
-        ops.gap_finish(part, feat.t, n, c, nparts, hw, feat.t.shape[-1], coff)
+        part = self._gap_sums(x)
+        ops.gap_finish(part.t, feat.t, n, c, part.rows, h * w, feat.t.shape[-1], coff)
         if x.needs_grad:
             feat.needs_grad = True
         if self.taping and x.needs_grad:
@@ -1230,10 +1248,10 @@ class ExpertGroupEngine:
             v for m in bn.mods for v in (m.weight._version, m.bias._version, m.running_mean._version, m.running_var._version))
         cache = conv.__dict__.get("_bn_fold")
         if cache is None or cache[0] != key:
-            scale, shift, mean, _ = self._bn_coeffs(bn, 1)
+            k = self._bn_coeffs(bn, 1)
             wf = torch.empty(E, conv.coutp, conv.taps, conv.cinp, dtype=self.dtype, device=self.dev)
             bf = torch.empty(E, conv.coutp, dtype=F32, device=self.dev)
-            ops.pack_conv_weights_scaled(self._tab("w", conv), scale, shift, mean, wf, bf, E, conv.cout, conv.cin, conv.ks,
+            ops.pack_conv_weights_scaled(self._tab("w", conv), k.scale, k.shift, k.mean, wf, bf, E, conv.cout, conv.cin, conv.ks,
                                          conv.coutp, conv.cinp, self.dtype)
             cache = conv.__dict__["_bn_fold"] = (key, wf, bf)
         _, wf, bf = cache
@@ -1329,10 +1347,8 @@ class ExpertGroupEngine:
         layer = self.conv1
         ops.set_meta(flop=2.0 * self.N * dy.shape[1] * dy.shape[2] * layer.cout * layer.cin * layer.taps, name=layer.name,
                      bytes=(2 if z1.bn_fused is not None else 1) * dy.numel() * dy.element_size())
-        fuse = None
-        if z1.bn_fused is not None:                      # dy is g (masked gradient of the BatchNorm output): dz1 on load
-            g_, coef, c1, c2 = z1.bn_fused
-            fuse = (z1.t, coef, c1, c2)
+        f = z1.bn_fused                                  # dy is f.g (masked gradient of the BatchNorm output): dz1 on load
+        fuse = (z1.t, f.coef.block, f.c1, f.c2) if f is not None else None
         self._filter_grads(x0.t, dy, layer, self.eca1, gate, gapmean, x_shared=True, bn_fuse=fuse)
 
     def _filter_grads(self, xt, dy, layer, ecal, gate, gapmean, want_dgap=False, dgap_scale=1.0, **wgrad_kw):

@@ -188,8 +188,7 @@ class UNetOps(ExpertGroupEngine):
             if ops.conv2d_plan(n, h, w, ho, wo, c2.cinp, c2.cout_st, c2.coutp, self.B, c2.ks, c2.stride, c2.pad, self.dtype,
                                in_ld=c1.cout_st, out_ld=c2.cout_st, res_mode=hip.RES_INBN, stats=True) >= 0:
                 z1, st1 = self._conv_stats(x, c1)
-                self._bn_coeffs(bn1, self.B * h * w, st1, st1.shape[0] // self.E, z1)
-                z2, st2 = self._conv_stats(z1, c2, in_bn=self._last_coef)
+                z2, st2 = self._conv_stats(z1, c2, in_bn=self._bn_coeffs(bn1, self.B * h * w, st1, z1))
                 return self._last_bn(z2, st2, blk["bn2"], out, pool_to, defer)
         a = self._conv_bn(x, c1, bn1, relu=True)
         if defer and on_load:
@@ -203,19 +202,15 @@ class UNetOps(ExpertGroupEngine):
         consumer applies it on load (conv1x1_direct_kernel<MT, true>) or `_materialize` writes it after all."""
         if not defer or out is not None or pool_to is not None:
             return self._bn(z2, bn2, relu=True, stats=st2, out=out, pool_to=pool_to)
-        n, h, w, _ = z2.t.shape
-        rpe = self.B * h * w
-        self._bn_coeffs(bn2, rpe, st2, st2.shape[0] // self.E, z2)
-        z2.pending_bn = (self._last_coef, rpe)
+        z2.pending_bn = self._bn_coeffs(bn2, self.B * z2.t.shape[1] * z2.t.shape[2], st2, z2)
         return z2
 
     def _materialize(self, v):
         """v with a pending BatchNorm + ReLU (see _last_bn) -> the activation tensor, written by the pass the fused consumer avoids"""
         if v.pending_bn is None:
             return v
-        coef, rpe = v.pending_bn
-        y = Var(torch.empty_like(v.t))
-        ops.bn_apply(v.t, None, y.t, coef[2], coef[3], coef[0], rpe, self.E, v.t.shape[-1], True)
+        k, y = v.pending_bn, Var(torch.empty_like(v.t))
+        ops.bn_apply(v.t, None, y.t, k.scale, k.shift, k.mean, k.rpe, self.E, v.t.shape[-1], True)
         return y
 
     def _conv1x1_after_bn(self, h, layer, out=None):
@@ -224,7 +219,7 @@ class UNetOps(ExpertGroupEngine):
             n, hh, ww, _ = h.t.shape
             o = torch.empty(n, hh, ww, layer.cout_st, dtype=self.dtype, device=self.dev)
             run = ops.conv2d_prepare(h.t, layer.w_fwd, o, cin=layer.cinp, cout=layer.cout_st, coutp=layer.coutp, ipe=self.B, ks=1,
-                                     stride=1, pad=0, bias=layer.bias_packed, res_mode=hip.RES_INBN, bn_coef=h.pending_bn[0])
+                                     stride=1, pad=0, bias=layer.bias_packed, res_mode=hip.RES_INBN, bn_coef=h.pending_bn.block)
             if run.served():
                 ops.set_meta(flop=2.0 * n * hh * ww * layer.cout * layer.cin, name=layer.name + "+bn")
                 run.launch()
@@ -320,7 +315,7 @@ class UNetOps(ExpertGroupEngine):
         if h.t.dtype != torch.bfloat16 or up.cout_st != 4 * up.c_up:
             return False
         if h.pending_bn is not None:                      # (its BatchNorm + ReLU applied on load: conv1x1_direct_kernel<MT, true>)
-            kw.update(res_mode=hip.RES_INBN, bn_coef=h.pending_bn[0])
+            kw.update(res_mode=hip.RES_INBN, bn_coef=h.pending_bn.block)
         run = ops.conv2d_prepare(h.t, up.w_fwd, cat.t, **kw)
         if not run.served():
             return False

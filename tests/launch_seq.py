@@ -5,7 +5,12 @@ sequences with tests/golden/launch_sequences.json; the helper uses nothing but `
     python tests/launch_seq.py tests/golden/launch_sequences.json        (on an MI355X, from the repository root)
 
 writes the fixture from ANY revision of the package that is first on sys.path (the committed file: the revision before the
-prepared-launch API of pmoe_amd/ops.py)."""
+prepared-launch API of pmoe_amd/ops.py).
+
+tests/golden/launch_sequences_scalars.json holds the second reduction, ``reduce_scalars``: every ARGUMENT of every call, so that
+the row counts, partition counts, ReLU flags and element counts of the launches without a descriptor (the BatchNorm, GAP and
+stem-tail passes) are pinned too.  Written the same way, with PYTHONPATH naming a checkout of the other revision (the committed file:
+the revision before the engines' BatchNorm hand-offs became named records)."""
 import ctypes as C
 import json
 import sys
@@ -30,6 +35,24 @@ def reduce_calls(calls):
                 #  goes with its pointer)
                 rec.append([bool(getattr(d, f)) if t is C.c_void_p or f == "part_ws_floats" else getattr(d, f) for f, t in d._fields_])
         out.append(rec)
+    return out
+
+
+def reduce_scalars(calls):
+    """[(ctypes function, arguments)] of a LaunchRecorder -> [[name, argument ...]], every argument by the entry point's
+    ``argtypes``: integers and floats as their values, descriptors as in ``reduce_calls``, everything else -- pointers, pointer
+    tables, streams, and the 64-bit dropout seeds, which no case makes reproducible -- as null / non-null (zero / non-zero)"""
+    out = []
+    for (fn, args), rec in zip(calls, reduce_calls(calls)):
+        row = [rec[0]]
+        for a, t in zip(args, fn.argtypes):
+            if isinstance(getattr(a, "_obj", None), C.Structure):
+                row.append(rec[1])
+            elif t in (C.c_int32, C.c_int64):
+                row.append(int(a))
+            else:
+                row.append(float(a) if t is C.c_float else bool(a))
+        out.append(row)
     return out
 
 
@@ -138,7 +161,14 @@ def cases(tmp):
             "punet_untaped_train_forward_b1_64": lambda: _punet(tmp, 1, 64)}
 
 
-def record(make):
+def scalar_cases(tmp):
+    """name -> () -> (model, run): the passes of tests/golden/launch_sequences_scalars.json, taken from the two tables above"""
+    both = {**cases(tmp), **engine_cases(tmp)}
+    return {name: both[name] for name in ("mixture_train_bf16", "mixture_train_f32", "mixture_eval_bf16",
+                                          "punet_untaped_train_forward_b2_128", "punet_expert_train_taped", "stage1_train_taped")}
+
+
+def record(make, reduce=reduce_calls):
     """-> (model, run, reduced sequence of one run, its outputs)"""
     from pmoe_amd import hip
     hip.load()                          # (the call that loads the library would not be recorded)
@@ -146,14 +176,15 @@ def record(make):
     with hip.LaunchRecorder() as rec:
         outs = run()
     torch.cuda.synchronize()
-    return model, run, reduce_calls(rec.calls), [o.clone() for o in outs]
+    return model, run, reduce(rec.calls), [o.clone() for o in outs]
 
 
 if __name__ == "__main__":
     import tempfile
-    which = engine_cases if Path(sys.argv[1]).name == "launch_sequences_engines.json" else cases
+    which, reduce = {"launch_sequences_engines.json": (engine_cases, reduce_calls),
+                     "launch_sequences_scalars.json": (scalar_cases, reduce_scalars)}.get(Path(sys.argv[1]).name, (cases, reduce_calls))
     with tempfile.TemporaryDirectory() as tmp:
-        seqs = {name: record(make)[2] for name, make in which(tmp).items()}
+        seqs = {name: record(make, reduce)[2] for name, make in which(tmp).items()}
     body = ",\n".join(json.dumps(k) + ":[\n" + ",\n".join(json.dumps(r, separators=(",", ":")) for r in v) + "\n]" for k, v in seqs.items())
     Path(sys.argv[1]).write_text("{" + body + "}\n")
     import pmoe_amd

@@ -144,3 +144,20 @@ def test_engine_passes_issue_the_recorded_launches(tmp_path, name):
     assert len(seq) == len(want), (len(seq), len(want))
     for i, (a, b) in enumerate(zip(seq, want)):
         assert a == b, (name, i, a, b)
+
+
+# ---- every argument of every launch (tests/launch_seq.py reduce_scalars): the goldens above keep descriptor fields only, so the
+# partition counts, rows per expert, ReLU flags and element counts of the BatchNorm, GAP and stem-tail launches were unpinned.
+# Recorded from the revision before the engines' BatchNorm hand-offs became named records (BNCoef, Partials)
+SCALARS = json.loads((Path(__file__).resolve().parent / "golden" / "launch_sequences_scalars.json").read_text())
+
+
+@pytest.mark.parametrize("name", list(SCALARS))
+def test_every_launch_gets_the_recorded_scalar_arguments(tmp_path, name):
+    from tests.launch_seq import reduce_scalars, scalar_cases
+    _, _, seq, _ = record(scalar_cases(tmp_path)[name], reduce_scalars)
+    want = SCALARS[name]
+    assert {"pmoe_bn_finalize", "pmoe_gap_partial"} <= {r[0] for r in seq}
+    assert len(seq) == len(want), (len(seq), len(want))
+    for i, (a, b) in enumerate(zip(seq, want)):
+        assert a == b, (name, i, a, b)
