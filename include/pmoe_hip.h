@@ -387,7 +387,8 @@ int pmoe_eca_scale(const void* x, const float* gate, void* y, int32_t N, int64_t
                    int32_t dtype, void* stream);
 /* from dgate-sums (sum_hw dy*x, partials) -> dpre, dgap [N][C] (times dgap_scale: 1, or 1/HW when the result is used
  * directly as the per-image bias of the gate-folded data-gradient convolution) and dw [E][k] (written to the arena);
- * dw_scratch: [N][k] f32 caller-owned scratch (per-image partials, summed per expert in fixed order) */
+ * dw_scratch: [N][k] f32 caller-owned scratch (per-image partials, summed per expert in fixed order).
+ * k: odd, 1..9, as pmoe_eca_gate takes it (PMOE_ERR_ARG otherwise) */
 int pmoe_eca_bwd_small(const float* dot_part, int32_t nparts, const float* gate, const float* gapmean,
                        const void* const* w_ptrs, int32_t k, float* dgap, float* dw, float* dw_scratch, int32_t N,
                        int32_t ipe, int32_t C, int32_t creal, float dgap_scale, void* stream);

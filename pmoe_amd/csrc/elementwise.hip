@@ -946,7 +946,8 @@ int pmoe_eca_scale(const void* x, const float* gate, void* y, int32_t N, int64_t
 int pmoe_eca_bwd_small(const float* dot_part, int32_t nparts, const float* gate, const float* gapmean,
                        const void* const* w_ptrs, int32_t k, float* dgap, float* dw, float* dw_scratch, int32_t N,
                        int32_t ipe, int32_t C, int32_t creal, float dgap_scale, void* stream) {
-    if (C > 1024 || k > 9 || k < 1 || N % ipe || !dw_scratch) return PMOE_ERR_ARG;
+    // (an even k has no centre tap: Conv1d(padding = k / 2) would give C + 1 outputs; pmoe_eca_gate refuses it too)
+    if (C > 1024 || k > 9 || k < 1 || !(k & 1) || N % ipe || !dw_scratch) return PMOE_ERR_ARG;
     HIP_RET((launch<eca_bwd_small_kernel, 0>(dim3(N), dim3(256), 0, (hipStream_t)stream, dot_part, nparts, gate, gapmean,
                                              (const float* const*)w_ptrs, k, dgap, dw_scratch, ipe, C, creal, dgap_scale)));
     return launch<eca_bwd_dw_kernel, 0>(dim3(N / ipe), dim3(64), 0, (hipStream_t)stream, dw_scratch, dw, ipe, k);

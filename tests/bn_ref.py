@@ -8,7 +8,7 @@ constants are ``[E, C]``.  A partitioned sum comes with ``abs``: the sum of the 
 partition; a stored tensor comes with ``mag``: the sum of the absolute values of its addends with every difference expanded
 (|x| + |mean| for x - mean).  The float32 error bounds of tests/test_bn_gpu.py are multiples of these.
 
-Out of scope: the fp8 side output of bn_apply and the ECA kernels.  The convolution-fused forms (statistics epilogue, BatchNorm on
+Out of scope: the fp8 side output of bn_apply; the ECA kernels are in tests/eca_head_ref.py.  The convolution-fused forms (statistics epilogue, BatchNorm on
 load, PMOE_RES_DBN, the bn_fused weight gradient) are in tests/conv_ref.py, built on bn_apply / bn_bwd_apply of this file.
 """
 import functools
