@@ -745,6 +745,50 @@ int pmoe_gather_frames_to_f32(const uint8_t* store, const int64_t* idx, float* d
 int pmoe_gather_labels_to_i64(const uint8_t* store, const int64_t* idx, int64_t* dst, int64_t n_src, int32_t n, int64_t hw,
                               void* stream);
 
+/* ---- vision utilities (pmoe_amd/vision.py; the reference's utils/vision.py: decode_mask for the trainers' image logs,
+ * draw_on_image for train_2.py and the agent's run_step).  PMOE_ERR_ARG before any launch: a null or misaligned pointer (f32
+ * data to 4 bytes, int64 / f64 data to 8), an extent < 1, nc < 1, an unknown kind or dtype code, B > 65535. */
+#define PMOE_MASK_LOGITS_F32 0 /* mask f32 [B][C][H][W]: the class is the arg-max over C */
+#define PMOE_MASK_IDS_I64 1    /* mask int64 [B][H][W] */
+#define PMOE_MASK_IDS_U8 2     /* mask uint8 [B][H][W] */
+#define PMOE_VIS_U8 0          /* out uint8 [B][H][W][3] */
+#define PMOE_VIS_F32 1         /* out f32 [B][3][H][W] = (float)u8 / 255.0f */
+#define PMOE_VIS_F64 2         /* out f64 [B][3][H][W] = (double)u8 / 255.0: the reference's array, bit for bit */
+/* Class ids -> colours of `palette` (device data uint8 [nc][3]).  The arg-max is numpy's: the lowest index wins a tie, a NaN
+ * counts as the maximum and the first NaN wins.  An id outside [0, nc) is black (the reference loops over range(nc)).  C is read
+ * for PMOE_MASK_LOGITS_F32 only.  H * W <= 2^28. */
+int pmoe_decode_mask(const void* mask, int32_t kind, void* out, int32_t out_dtype, const uint8_t* palette, int32_t nc, int32_t B,
+                     int32_t C, int32_t H, int32_t W, void* stream);
+
+#define PMOE_TEXT_ROWS 8
+#define PMOE_TEXT_COLS 24
+/* draw_on_image (utils/vision.py:88-152) for B frames in one launch, one workgroup per frame.  Frame b is the f32 [3][H][W] at
+ * frames + b * frame_stride (in floats, >= 3 H W: a slot of a frame ring is served in place) and is written as uint8 [H][W][3]
+ * into slot (slot0 + b) % capacity of out [capacity][H][W][3]; B <= capacity, 0 <= slot0 < capacity, H * W <= 2^28.
+ *
+ * The frame: lo / hi = minimum / maximum over its 3 H W values by fminf / fmaxf (a NaN is ignored); the pixel is
+ * v = ((x - lo) / (-lo + hi)) * 255.0f -- four f32 operations, each rounded once, no contraction -- truncated to uint8 when
+ * 0 <= v <= 255 and 0 otherwise: a constant frame (0 / 0) and a NaN pixel write 0, where the reference is undefined.
+ *
+ * The text: PMOE_TEXT_ROWS strings of PMOE_TEXT_COLS char codes, space padded, in the reference's call order (a later string
+ * overwrites an earlier one), W2 = W / 2:
+ *   0 (5, 30) "Steer: %.3f" action[b][0]    1 (5, 50) "Throttle: %.3f"    2 (5, 70) "Brake: %.3f"     red   (255, 0, 0)
+ *   3 (W2, 10) "Command: %i" = the arg-max (as above) of command[b][0 .. n_cmd)                        green (0, 255, 0)
+ *   gt != 0 only (else empty): 4 (5, 10) "Speed: %.3f" speed[b]; 5 (W2, 30), 6 (W2, 50), 7 (W2, 70) steer, throttle, brake
+ *   of control_gt[b][0 .. 2), green.  speed and control_gt are read (and must be given) only when gt != 0.
+ * With pedal = action[b][1] (control_gt[b][1]): pedal > 0 prints throttle = pedal and brake "0.000" (the reference's integer
+ * 0); otherwise throttle "0.000" and brake = -pedal, so a pedal of 0.0 prints brake "-0.000" and a NaN pedal prints "nan".
+ * %.3f is computed in integers: |x| = m 2^e with a 24-bit m, m * 1000 is exact in 64 bits, the shift by -e rounds half to even
+ * on the remainder, the '-' follows the sign bit (also when the digits are 0.000).  The string equals C's / Python's "%.3f" for
+ * every finite f32 with |x| < 2^20, "nan" for a NaN, "inf" / "-inf"; a finite |x| >= 2^20 prints "big" / "-big".
+ * Glyphs are hard-edged 5 x 7 bitmaps in a 6-pixel advance, top-left corner at the string's position: font [128][7] bytes (device
+ * data), row mask bit 4 = the leftmost column; a char code is taken & 127.  No parity with a TrueType rendering is claimed.
+ * Everything is clipped to the frame.  text_out (may be NULL): uint8 [B][PMOE_TEXT_ROWS][PMOE_TEXT_COLS], the char codes.
+ * No atomics, no scratch: out is a function of the inputs alone. */
+int pmoe_frame_annotate(const float* frames, int64_t frame_stride, uint8_t* out, int32_t B, int32_t H, int32_t W, int32_t slot0,
+                        int32_t capacity, const float* action, const float* speed, const float* command, int32_t n_cmd,
+                        const float* control_gt, int32_t gt, const uint8_t* font, uint8_t* text_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -151,6 +151,8 @@ SIGNATURES = {
     "pmoe_gather_rows": [_P, _P, _P, _L, _L, _L, _P],
     "pmoe_gather_frames_to_f32": [_P, _P, _P, _L, _I, _I, _I, _I, _P],
     "pmoe_gather_labels_to_i64": [_P, _P, _P, _L, _I, _L, _P],
+    "pmoe_decode_mask": [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P],
+    "pmoe_frame_annotate": [_P, _L, _P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P],
     "pmoe_mt_grad_norm": [_P, _P, _P, _I, _F, _P, _P, _I, _P],
     "pmoe_mt_adam": [_P, _P, _P, _I, _F, _F, _F, _F, _F, _I, _F, _F, _P, _P],
     "pmoe_mt_adam_packs": [_P, _P, _P, _P, _P, _I, _F, _F, _F, _F, _F, _I, _F, _F, _P, _P],

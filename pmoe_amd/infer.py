@@ -342,11 +342,26 @@ class AgentStep:
     buffer, speed / ``speed_factor`` (divided in double, rounded to f32 once) and the one-hot command (index ``cmd - 1``, or 3
     when that is negative) into one pinned f32 buffer, two non-blocking uploads, the plan (``mode="eager"``: the same launches
     through the engine's Python), one 24 B download per batch row, one event wait.  Nothing is allocated per step; the
-    coefficient tables are built once.  Weight, buffer, dtype and device changes are noticed like the tick notices them."""
+    coefficient tables are built once.  Weight, buffer, dtype and device changes are noticed like the tick notices them.
 
-    def __init__(self, model, sensor=(600, 800), crop=(125, 90), size=(224, 224), batch=1, mode="plan", seed=0, speed_factor=10.0):
+    ``log``: a :class:`pmoe_amd.vision.FrameLog` of the step's size and device (anything else is a ``ValueError`` here) keeps the
+    reference's video log (``image_agent.py:162-173``: ``draw_on_image(rgb, measurements, action, False)`` per tick): after the
+    tick's launches and before the control download, ``step()`` itself issues one ``log.push`` on the same stream -- the newest
+    ring slot, the tick's action, the speed and one-hot command views -- so the recorded plan is the same with and without a
+    log.  With ``log=None`` there is no launch and nothing else differs."""
+
+    def __init__(self, model, sensor=(600, 800), crop=(125, 90), size=(224, 224), batch=1, mode="plan", seed=0, speed_factor=10.0,
+                 log=None):
         if mode not in ("eager", "plan"):
             raise ValueError(f"AgentStep: mode must be 'eager' or 'plan', got {mode!r}")
+        if log is not None:
+            from .vision import FrameLog
+            if not isinstance(log, FrameLog):
+                raise TypeError("AgentStep: log is a pmoe_amd.vision.FrameLog")
+            if log.size != (int(size[0]), int(size[1])):
+                raise ValueError(f"AgentStep: the FrameLog holds {log.size} frames, the step makes {tuple(size)} ones")
+            if log.capacity < batch:
+                raise ValueError(f"AgentStep: a FrameLog of capacity {log.capacity} cannot take {batch} frames per step")
         if model.training:
             raise RuntimeError("AgentStep runs the eval-mode chain: call model.eval() first")
         self.H0, self.W0 = int(sensor[0]), int(sensor[1])
@@ -362,6 +377,9 @@ class AgentStep:
         self.tile = ops.sensor_tile(self._vcoeffs[1], w)
         self._frame_dev = self._control_dev = self._meas_dev = self._htable = self._vtable = None
         self.tick = _SensorTick(self, model, batch=self.B, height=h, width=w, mode=mode, seed=seed)
+        if log is not None and log.device != self.tick.frames.device:
+            raise ValueError(f"AgentStep: the FrameLog is on {log.device}, the model on {self.tick.frames.device}")
+        self.log = log
         # ---- the host side of a step: pinned, written in place
         self._frame_host = torch.empty(self.B, self.H0, self.W0, 4, dtype=torch.uint8, pin_memory=True)
         self._meas_host = torch.zeros(self._meas_dev.numel(), dtype=torch.float32, pin_memory=True)
@@ -442,7 +460,9 @@ class AgentStep:
         with torch.cuda.device(self._frame_dev.device):
             self._frame_dev.copy_(self._frame_host, non_blocking=True)
             self._meas_dev.copy_(self._meas_host, non_blocking=True)
-            tick._issue()
+            actions = tick._issue()
+            if self.log is not None:             # (issued here, not recorded: the plan is the same with and without a log)
+                self.log.push(tick.frames[:, -1], actions, tick.static_in[1], tick.static_in[2])
             self._control_host.copy_(self._control_dev, non_blocking=True)
             self._done.record()
         self._done.synchronize()

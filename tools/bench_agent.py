@@ -10,7 +10,11 @@ one process:
 
 Host wall clock per step (each leg ends in a synchronisation): warm-up, then 5 rounds of 200 steps per leg, per round the median,
 minimum and maximum; then the device-event time of (b)'s launches alone.  ``--model moe|punet|pmoe`` (default moe; the expert count
-is the first argument, default 3).  The last line is the same as JSON."""
+is the first argument, default 3).  The last line is the same as JSON.
+
+``--log``: the cost of the video log instead (``main_log``): ``AgentStep`` without a log, with a ``pmoe_amd.vision.FrameLog``, and
+without one plus the newest frame brought to the host and normalised with numpy; then the device time of one
+``pmoe_frame_annotate`` launch."""
 import json
 import statistics
 import sys
@@ -68,11 +72,85 @@ class ParentPath:
         return self.postprocess(action)
 
 
+def main_log(kind, experts):
+    """``--log``: what the reference's video log (``image_agent.py:167-173``) costs per step, three legs alternating in one
+    process: (a) ``AgentStep`` without a log; (b) with a ``FrameLog``; (c) without a log plus what a caller does without one:
+    the newest frame of the ring to the host and the reference's numpy normalisation (no text)."""
+    from pmoe_amd import vision
+    from pmoe_amd.infer import AgentStep
+    model = build_model(kind, experts)
+    plain = AgentStep(model, sensor=SENSOR, crop=CROP, size=SIZE, batch=1, mode="plan", seed=0)
+    log = vision.FrameLog(capacity=1000, size=SIZE, device="cuda")
+    logged = AgentStep(model, sensor=SENSOR, crop=CROP, size=SIZE, batch=1, mode="plan", seed=0, log=log)
+    hosted = AgentStep(model, sensor=SENSOR, crop=CROP, size=SIZE, batch=1, mode="plan", seed=0)
+    rng = np.random.default_rng(0)
+    frames = [rng.integers(0, 256, SENSOR + (4,), dtype=np.uint8) for _ in range(8)]
+    inputs = [(frames[i % 8], float(rng.uniform(0.0, 9.0)), [-1, 1, 2, 3, 4][i % 5]) for i in range(STEPS)]
+    vizs = []
+
+    def host_log(bgra, spd, cmd):
+        control = hosted.step(bgra, spd, cmd)
+        img = hosted.tick.frames[:, -1].cpu()[0].permute(1, 2, 0).numpy()
+        vizs.append((((img - img.min()) / (-img.min() + img.max())) * 255).astype(np.uint8))
+        if len(vizs) > 1000:
+            vizs.clear()
+        return control
+
+    legs = {"a": plain.step, "b": logged.step, "c": host_log}
+    for i in range(WARMUP):
+        bgra, spd, cmd = inputs[i]
+        a, b, c = (legs[k](bgra, spd, cmd) for k in "abc")
+        assert np.array_equal(a, b) and np.array_equal(a, c), (i, a, b, c)
+    assert np.array_equal(log.frames()[-1][100:], vizs[-1][100:])            # (below the text rows: the same pixels)
+    rounds = {k: [] for k in legs}
+    for r in range(ROUNDS):
+        for name in ("abc"[r % 3:] + "abc"[:r % 3]):
+            step, times = legs[name], []
+            torch.cuda.synchronize()
+            for bgra, spd, cmd in inputs:
+                t0 = time.perf_counter()
+                step(bgra, spd, cmd)
+                times.append((time.perf_counter() - t0) * 1e3)
+            rounds[name].append(times)
+    label = kind if kind == "punet" else f"{kind} E={experts}"
+    print(f"{label}  600x800 BGRA -> 224x224, B=1, plan mode; host wall clock per step, ms: median (min .. max) of {STEPS} steps per round")
+    for r in range(ROUNDS):
+        print(f"  round {r + 1}: " + "   ".join(
+            f"({k}) {what} {statistics.median(rounds[k][r]):.3f} ({min(rounds[k][r]):.3f} .. {max(rounds[k][r]):.3f})"
+            for k, what in (("a", "no log"), ("b", "FrameLog"), ("c", "frame to host + numpy"))))
+    med = {k: statistics.median(statistics.median(t) for t in v) for k, v in rounds.items()}
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    tick = logged.tick
+
+    def push():
+        log.push(tick.frames[:, -1], tick.raw if tick.pun is None else tick._result[0], tick.static_in[1], tick.static_in[2])
+    from pmoe_amd import hip
+    push()
+    with hip.LaunchRecorder() as one:                         # the launch alone, re-issued without the Python above it
+        push()
+    assert [c[0].__name__ for c in one.calls] == ["pmoe_frame_annotate"]
+    e0.record()
+    for _ in range(STEPS):
+        one.replay()
+    e1.record()
+    e1.synchronize()
+    annotate_us = e0.elapsed_time(e1) / STEPS * 1e3
+    print(f"  median of the round medians: (a) {med['a']:.3f} ms  (b) {med['b']:.3f} ms  (c) {med['c']:.3f} ms;  "
+          f"(b) - (a) = {(med['b'] - med['a']) * 1e3:.1f} us,  (c) - (a) = {(med['c'] - med['a']) * 1e3:.1f} us")
+    print(f"  pmoe_frame_annotate {annotate_us:.1f} us per launch ({STEPS} launches back to back between two events); "
+          f"the log holds {len(log)} frames, {log.dropped} overwritten")
+    print(json.dumps({"model": label, "steps_per_round": STEPS, "rounds": ROUNDS,
+                      **{f"{k}_ms": [round(statistics.median(t), 4) for t in v] for k, v in rounds.items()},
+                      **{f"{k}_median_ms": round(v, 4) for k, v in med.items()}, "frame_annotate_us": round(annotate_us, 2)}), flush=True)
+
+
 def main():
     kind = sys.argv[sys.argv.index("--model") + 1] if "--model" in sys.argv else "moe"
     if kind not in ("moe", "punet", "pmoe"):
         raise SystemExit("--model moe|punet|pmoe")
     experts = int(sys.argv[1]) if len(sys.argv) > 1 and sys.argv[1].isdigit() else 3
+    if "--log" in sys.argv:
+        return main_log(kind, experts)
     from pmoe_amd.infer import AgentStep
     model = build_model(kind, experts)
     parent = ParentPath(model, seed=0)
