@@ -121,7 +121,7 @@ int pmoe_conv2d_igemm(const pmoe_conv_desc* d, void* stream);
 int pmoe_conv2d_stat_rows(const pmoe_conv_desc* d);
 /* which kernel instantiation pmoe_conv2d_igemm would run for this descriptor (nothing is launched; used by bench.py
  * to attribute measured launch times to kernel symbols that a rocprofv3 kernel trace shows):
- *   3000                     gemm_skinny_kernel<4|8>               (expert MLP layers / <= 2048 output pixels per expert, bf16)
+ *   3000                     gemm_skinny_kernel<4>                 (expert MLP layers / <= 3200 output rows per expert, bf16, no statistics; its one instantiation)
  *   1000 + LOG_RB            conv3x3_res_kernel<LOG_RB>            (resident-filter kernel, conv_res.hip)
  *   1400 + MT                conv1x1_direct_kernel<MT>             (1x1, stride 1 | 2, >= 8192 pixels per expert, 64..512 input channels, conv_c1x1.hip)
  *   1410 + MT | 1460 + MT    conv1x1_direct_kernel<MT, true>       (the same with PMOE_RES_INBN: BatchNorm + ReLU of the input applied to the operand registers; 1450 + MT / 1460 + MT: with shuffle_c)

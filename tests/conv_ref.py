@@ -5,16 +5,24 @@ Pure torch on the CPU, float64.  One function per entry point, taking what the d
 folded into the image index, channel windows (ld = the last dimension of the buffer, coff), the fused forms of include/pmoe_hip.h
 that tests/bn_ref.py leaves out -- the statistics epilogue, PMOE_RES_INBN (BatchNorm + ReLU on load, on bn_ref.bn_apply),
 PMOE_RES_DBN (masked gradient + the two reductions of the BatchNorm backward) and the bn_fused weight gradient (on
-bn_ref.bn_bwd_apply).
+bn_ref.bn_bwd_apply) -- and the epilogue of the expert MLP layers: PMOE_ACT_ELU | TANH | SIGMOID, PMOE_RES_DELU | DTANH | DSIGMOID
+and fused inverted dropout (mlp_epilogue, on tests/eca_head_ref.py's hash, keep_scale, activations and device-library allowances).
+pmoe_mlp_wgrad (csrc/gemm_skinny.hip, mlp_wgrad_kernel) has its reference, cases and generator at the end of the file.
 
-Two kinds of input (tests/test_conv_cpu.py checks on the CPU what the GPU tests assume of them):
+Three kinds of input (tests/test_conv_cpu.py checks on the CPU what the GPU tests assume of them):
   lattice  integers (BatchNorm coefficients: small dyadic numbers) with sum |x||w| < 2^24 per output element, so that every partial
            sum of a float32 accumulation is exact IN ANY ORDER and a kernel's accumulator IS the float64 one; wide enough that the
            bfloat16 output really rounds (inexactly and on exact ties).  What is left to a kernel is the order of its roundings:
            ROUNDING below.
   unit     {-1, 0, 1} with three quarters zeros: outputs below 256 (nothing rounds) and squared-output sums below 2^24, so that
            every fused statistic is exact too.
-Continuous data stays in tests/test_ops_gpu.py: a worst-case float32 bound over K = 4608 terms is looser than bfloat16 rounding.
+  dyadic   the cases that ask for an activation, its derivative or dropout, and only they: sparse small integers against
+           weights and biases that are multiples of 1/64, so that the accumulator is still exact in any order (64 sum |x||w| <
+           2^24) but the pre-activations spread over (-8, 8), where ELU, tanh and sigmoid are not saturated.  What is left to a
+           kernel there is the device library's expm1f / tanhf / expf and the float32 operations behind them: mlp_epilogue
+           returns that allowance next to the value, and zero wherever the value is a float32 product or nothing.
+Continuous data stays in tests/test_ops_gpu.py for the K-long float32 SUMS only: a worst-case float32 bound over K = 4608 terms
+is looser than bfloat16 rounding.
 """
 import collections
 import functools
@@ -23,12 +31,20 @@ import torch
 import torch.nn.functional as F
 
 from tests import bn_ref
+from tests import eca_head_ref as H
 from tests.stem_tail_ref import BF16, F32, F64, round_to
 
 EPS24 = bn_ref.EPS24
-RES_NONE, RES_ADD, RES_DRELU, RES_DBN, RES_INBN = 0, 1, 2, 6, 7          # include/pmoe_hip.h
-ACT_NONE, ACT_RELU = 0, 1
+RES_NONE, RES_ADD, RES_DRELU, RES_DELU, RES_DTANH, RES_DSIGMOID, RES_DBN, RES_INBN = range(8)          # include/pmoe_hip.h
+ACT_NONE, ACT_RELU, ACT_ELU, ACT_TANH, ACT_SIGMOID = range(5)
 KINDS = ("lattice", "unit")
+DYADIC = "dyadic"                    # the one kind of the cases that ask for an MLP epilogue form (kinds_of)
+DROP_P = 0.3
+ACT_FLAGS = {"elu": ACT_ELU, "tanh": ACT_TANH, "sigmoid": ACT_SIGMOID}
+DMODE_FLAGS = {"delu": RES_DELU, "dtanh": RES_DTANH, "dsigmoid": RES_DSIGMOID}
+ACT_OF_DMODE = {RES_DRELU: ACT_RELU, RES_DELU: ACT_ELU, RES_DTANH: ACT_TANH, RES_DSIGMOID: ACT_SIGMOID}
+DROP_FLAGS = ("drop", "dropL", "dropE")                                # SEED_OF below: seed 5, a seed above 2^32, edge_seed
+MLP_FLAGS = set(ACT_FLAGS) | set(DMODE_FLAGS) | set(DROP_FLAGS)
 
 
 def r16(c):
@@ -63,7 +79,7 @@ _NOADD = Order(None, None, "takes no side input")
 ROUNDING = {
     **{c: _TILE for c in (522, 541, 542, 622, 641, 642, 722, 741, 2007)},                       # conv_igemm_kernel / _lite_kernel
     **{4000 + c: _TILE for c in (522, 541, 542, 622, 641, 642, 722, 741, 2007)},                # ... as parity-class launches
-    3000: _TILE,                                                                                # gemm_skinny_kernel (the small data gradients of three cases)
+    3000: _TILE,                                        # gemm_skinny_kernel<4>: its four f32 partial tiles and the bias meet in registers, the same tail
     1005: _RES, 1007: _RES,                                                                     # conv3x3_res_kernel
     1107: _RES, 1117: _NOADD,                                                                   # conv3x3_resdma_kernel
     1207: _NOADD, 1217: _NOADD, 1227: _RES, 1247: _NOADD, 1257: _NOADD, 1267: _NOADD,          # conv3x3_respipe_kernel<b, m>
@@ -189,22 +205,28 @@ def _padded_source(xw, ks, stride, pad, ho, wo, dilate):
     return F.pad(x, (pad, max(pr, 0), pad, max(pb, 0)))
 
 
-def conv_acc(xw, w, *, ipe, in_shared, stride, pad, ho, wo, dilate=False, dtype=F64, taps=False):
+def conv_acc(xw, w, *, ipe, in_shared, stride, pad, ho, wo, dilate=False, dtype=F64, taps=False, shift_tap=False):
     """the accumulator: xw [Nin, H, W, cin] (the channel window), w [E, cout, cin, ks, ks] -> [N, ho, wo, cout], evaluated in
-    ``dtype``.  taps: a tap-by-tap loop (another summation order than F.conv2d's)"""
+    ``dtype``.  taps: a tap-by-tap loop (another summation order than F.conv2d's).  shift_tap (a mutant): the left tap of the
+    middle filter row reads the image's first column where it should read the zero border"""
     E, cout, _, ks, _ = w.shape
     x = _padded_source(xw.to(dtype), ks, stride, pad, ho, wo, dilate)
+    xm = x
+    if shift_tap and pad > 0:
+        xm = x.clone()
+        xm[:, :, :, pad - 1] = x[:, :, :, pad]
     outs = []
     for e in range(E):
         xe = x if in_shared else x[e * ipe:(e + 1) * ipe]
         we = w[e].to(dtype)
-        if not taps:
+        if not taps and not shift_tap:
             outs.append(F.conv2d(xe, we, stride=stride)[:, :, :ho, :wo])
             continue
         o = torch.zeros(xe.shape[0], cout, ho, wo, dtype=dtype)
         for ky in reversed(range(ks)):
             for kx in range(ks):
-                v = xe[:, :, ky:ky + (ho - 1) * stride + 1:stride, kx:kx + (wo - 1) * stride + 1:stride]
+                src = (xm if in_shared else xm[e * ipe:(e + 1) * ipe]) if (ky, kx) == (ks // 2, 0) else xe
+                v = src[:, :, ky:ky + (ho - 1) * stride + 1:stride, kx:kx + (wo - 1) * stride + 1:stride]
                 o = o + torch.einsum("nchw,oc->nohw", v, we[:, :, ky, kx])
         outs.append(o)
     return torch.cat(outs).permute(0, 2, 3, 1).contiguous()
@@ -215,14 +237,142 @@ def _per_image(coef, bn_ipe):
     return coef.repeat_interleave(bn_ipe, 0)[:, None, None, :]
 
 
+def _f32(t):
+    """one float32 rounding"""
+    return round_to(t, F32)
+
+
+_M64 = (1 << 64) - 1
+
+
+def edge_seed(idx, drop_p=DROP_P):
+    """a seed under which hash_uniform(seed, idx) == float32(drop_p) EXACTLY -- the one element that tells the keep test `>=` from
+    `>`.  float32(0.3) is a multiple of 2^-24, and the mix of csrc/common.h is a bijection of 64-bit words: run it backwards from
+    a word whose top 24 bits are that multiple."""
+    def unxorshift(y, s):
+        x = y
+        for _ in range(64 // s + 1):
+            x = y ^ (x >> s)
+        return x
+    top = int(torch.tensor(drop_p, dtype=F32).to(F64).item() * 16777216.0)
+    z = unxorshift((top << 40) | 0x5A5A5A5A5A, 31)
+    z = unxorshift(z * pow(0x94D049BB133111EB, -1, 1 << 64) & _M64, 27)
+    z = unxorshift(z * pow(0xBF58476D1CE4E5B9, -1, 1 << 64) & _M64, 30)
+    return (z - idx * 0x9E3779B97F4A7C15) & _M64
+
+
+EDGE_INDEX = 11
+SEED_OF = {"drop": H.SEEDS[0], "dropL": H.SEEDS[1], "dropE": edge_seed(EDGE_INDEX)}
+
+# deliberately wrong variants of the reference (``mut``); tests/test_conv_cpu.py proves that the cases tell each from the reference
+MUTANTS = ("kslice",              # the last k-slice of 16 input channels dropped
+           "tapshift",            # one tap reads the image's first column in place of the zero border
+           "bias_late",           # the bias added after a staging rounding
+           "drop_ld",             # the dropout index computed with out_ld in place of Cout
+           "drop_off1",           # ... off by one
+           "keep_gt",             # kept iff hash > p
+           "dmode_noscale",       # keep_scale left out of a D-mode
+           "dmode_unscaled")      # the saved output used unscaled in f'
+
+
+def _op(value, err):
+    """the error bound of one float32 operation whose exact result is ``value`` and whose operands carry ``err`` into it: nothing
+    new where the operands are exact and the result is a float32 value, else one rounding of the result"""
+    err = err + torch.zeros_like(value)
+    return err + torch.where((err > 0) | (value != _f32(value)), EPS24 * value.abs(), torch.zeros_like(value))
+
+
+def mlp_epilogue(v, rw, *, res_mode, act, drop_p, seed, out_ld=0, mut=""):
+    """The tail the three epilogue copies share (csrc/gemm_skinny.hip:136-166, conv_igemm.hip:333-363,
+    conv_dma_epilogue.inc:90-115): v [N, Ho, Wo, cout] = acc + bias, exact; rw = the residual window.  Residual mode, then
+    activation, then dropout.  -> value (float64; where ``allow`` is zero, the float32 value itself), allow (the allowance on
+    the float32 value), keep (the dropout mask), undropped (the value before the dropout).
+
+    EXACT (allow = 0): no activation and ReLU, with or without dropout; PMOE_RES_DRELU with keep_scale; ELU and its derivative
+    on the positive branch -- all a float32 product with the float32 keep_scale, or nothing: round_f32(v * keep_scale).
+    Allowances, in units of 2^-24 = one float32 rounding of the magnitude named (H.ULP = 2 units):
+      ELU, v <= 0   T_EXPM1 ULP |y|                        tanh   T_TANH ULP |y|
+      sigmoid       T_EXP ULP y (1 - y) + 2 |y|            (1 + e and the division, as eca_head_ref.act_fwd)
+      ... with dropout: times keep_scale, + 1 |y keep_scale| for the product `v[i] * keep_scale`
+    D-modes, u = rv * (1 / keep_scale), result dy f'(u) keep_scale: the error bound is carried operation by operation (_op) --
+    an operation whose operands are exact and whose exact result is a float32 value adds nothing, any other adds one unit of
+    its result on top of what its operands carry through it.  So a chain that float32 evaluates exactly (a bfloat16 saved
+    output without dropout: u = rv, u^2 has 16 bits, and the dyadic dy times a short f' often fits 24) must come out EXACT,
+    bfloat16 ties included, and only what really rounds gets an allowance:
+      `1.f / keep_scale`, `rv * (...)`     with dropout: u carries 2 units of |u|
+      DELU, u <= 0   `y + 1.f`, `v * d`           DSIGMOID   `1.f - y`, `y * (...)`, `v * d`
+      DTANH          `y * y`, `1.f - (...)`, `v * d`: the compiler may contract the first two into one rounding of 1 - u^2,
+                     which the two-step bound covers (it is never below one unit of the result)
+      `* keep_scale` with dropout
+    A saved output of exactly 0 under dropout counts as dropped."""
+    zero = torch.zeros((), dtype=F64)
+    allow = torch.zeros_like(v)
+    ks = H.keep_scale(drop_p, F64)                                      # float32(1 / (1 - float32(p))), or 1
+    drop = drop_p > 0
+    if res_mode == RES_ADD:
+        v = v + rw
+    elif res_mode == RES_DRELU:
+        v = torch.where(rw > 0, v if mut == "dmode_noscale" else _f32(v * ks), zero)
+    elif res_mode in (RES_DELU, RES_DTANH, RES_DSIGMOID):
+        assert act == ACT_NONE, "a derivative mode and an activation do not combine in the engine"
+        sc = 1.0 if mut == "dmode_noscale" else ks
+        u, eu = rw, torch.zeros_like(rw)
+        if drop and mut != "dmode_unscaled":
+            u = rw / ks
+            eu = _op(u, rw.abs() * _op(1 / ks, 0 * ks))
+        if res_mode == RES_DELU:
+            dv = u + 1
+            ed = _op(dv, eu)
+        elif res_mode == RES_DTANH:
+            dv = 1 - u * u
+            ed = _op(dv, _op(u * u, 2 * u.abs() * eu))
+        else:
+            t = 1 - u
+            et = _op(t, eu)
+            dv = u * t
+            ed = _op(dv, t.abs() * eu + u.abs() * et)
+        raw = v * dv
+        al = _op(raw, v.abs() * ed)
+        if drop and mut != "dmode_noscale":
+            raw = raw * sc
+            al = _op(raw, sc * al)
+        if res_mode == RES_DELU:
+            raw, al = torch.where(u > 0, _f32(v * sc), raw), torch.where(u > 0, zero, al)
+        dropped = (rw == 0) & drop
+        v, allow = torch.where(dropped, zero, raw), torch.where(dropped, zero, al)
+    if act == ACT_RELU:
+        v = v.clamp_min(0)
+    elif act != ACT_NONE:
+        assert res_mode in (RES_NONE, RES_ADD)
+        y = H.act_apply(act, v)
+        allow = {ACT_ELU: H.T_EXPM1 * H.ULP * torch.where(v > 0, zero, y.abs()), ACT_TANH: H.T_TANH * H.ULP * y.abs(),
+                 ACT_SIGMOID: H.T_EXP * H.ULP * y * (1 - y) + 2 * EPS24 * y.abs()}[act]
+        v = y
+    undropped, keep = v, torch.ones_like(v, dtype=torch.bool)
+    if drop and res_mode < RES_DRELU:
+        # element (opix, c) of the dense NHWC output draws hash_uniform(seed, opix * Cout + c)
+        cout = v.shape[-1]
+        ld = out_ld if mut == "drop_ld" else cout
+        idx = (torch.arange(v.numel() // cout)[:, None] * ld + torch.arange(cout)).reshape(v.shape) + (mut == "drop_off1")
+        u = H.hash_uniform(seed, int(idx.max()) + 1)[idx]
+        p = torch.tensor(drop_p, dtype=F32).to(F64)
+        keep = (u > p) if mut == "keep_gt" else (u >= p)
+        scaled = torch.where(allow > 0, v * ks, _f32(v * ks))
+        al = torch.where(allow > 0, allow * ks + EPS24 * (v * ks).abs(), zero)
+        v, allow = torch.where(keep, scaled, zero), torch.where(keep, al, zero)
+    return {"value": v, "allow": allow, "keep": keep, "undropped": undropped}
+
+
 def conv2d(inp, w, out_init, *, cin, cout, ipe, ks, stride, pad, dtype, in_shared=False, in_coff=0, out_coff=0, dilate=False,
            bias=None, res=None, res_coff=0, res_mode=RES_NONE, act=ACT_NONE, bn_coef=None, bn_ipe=0, shuffle_c=0, stats=False,
-           rounding="once"):
+           rounding="once", drop_p=0.0, seed=0, mut=""):
     """pmoe_conv2d_igemm.  inp [Nin, H, W, in_ld], w [E, cout, cin, ks, ks] (the launch's own orientation: a data gradient passes
     the flipped, transposed filter), out_init [N, Ho, Wo, out_ld] = the output buffer before the launch ([N, 2 Ho, 2 Wo, out_ld]
     with shuffle_c), bias [E, cout], res [N, Ho, Wo, res_ld], bn_coef [4, N / bn_ipe, C] = mean, invstd, gamma * invstd, beta.
     -> acc (the exact accumulator), stored (the rounded window), out (the whole buffer after the launch), and with ``stats`` the
-    per-expert totals ``sums`` [E, 2, cout] with ``sums_abs`` (the sums of the absolute values of the same terms)"""
+    per-expert totals ``sums`` [E, 2, cout] with ``sums_abs`` (the sums of the absolute values of the same terms).
+    act / res_mode beyond ReLU / DRELU and drop_p, seed: the MLP forms of mlp_epilogue, whose ``allow`` (the allowance on the
+    float32 value of the window; zero = the stored value is exact), ``keep`` and ``undropped`` come back too.  ``mut``: MUTANTS"""
     E = w.shape[0]
     n = out_init.shape[0]
     ho, wo = out_init.shape[1:3]
@@ -234,24 +384,25 @@ def conv2d(inp, w, out_init, *, cin, cout, ipe, ks, stride, pad, dtype, in_share
         mean, scale, shift = bn_coef[0], bn_coef[2], bn_coef[3]
         xw = bn_ref.bn_apply(xw, None, scale, shift, mean, mean.shape[0], True, dtype)["y"]
     assert not torch.isnan(xw).any()
-    acc = conv_acc(xw, w, ipe=ipe, in_shared=in_shared, stride=stride, pad=pad, ho=ho, wo=wo, dilate=dilate)
+    if mut == "kslice":
+        xw = torch.cat([xw[..., :-16], torch.zeros_like(xw[..., -16:])], -1)
+    acc = conv_acc(xw, w, ipe=ipe, in_shared=in_shared, stride=stride, pad=pad, ho=ho, wo=wo, dilate=dilate,
+                   shift_tap=mut == "tapshift")
+    if mut == "bias_late":
+        acc = round_to(acc, dtype)
     v = acc if bias is None else acc + bias.repeat_interleave(ipe, 0)[:, None, None, :]
     if rounding == "staged":
         v = round_to(v, dtype)
     xhat = None
-    if res_mode in (RES_ADD, RES_DRELU, RES_DBN):
-        rw = res[..., res_coff:res_coff + cout]
-        if res_mode == RES_ADD:
-            v = v + rw
-        elif res_mode == RES_DRELU:
-            v = torch.where(rw > 0, v, torch.zeros((), dtype=F64))
-        else:
-            mean, invstd, scale, shift = (_per_image(c, bn_ipe or ipe) for c in bn_coef)
-            d = rw - mean
-            v = torch.where(d * scale + shift > 0, v, torch.zeros((), dtype=F64))
-            xhat = d * invstd
-    if act == ACT_RELU:
-        v = v.clamp_min(0)
+    rw = res[..., res_coff:res_coff + cout] if res_mode not in (RES_NONE, RES_INBN) else None
+    if res_mode == RES_DBN:
+        mean, invstd, scale, shift = (_per_image(c, bn_ipe or ipe) for c in bn_coef)
+        d = rw - mean
+        v = torch.where(d * scale + shift > 0, v, torch.zeros((), dtype=F64))
+        xhat = d * invstd
+    ep = mlp_epilogue(v, rw, res_mode=RES_NONE if res_mode in (RES_DBN, RES_INBN) else res_mode, act=act, drop_p=drop_p, seed=seed,
+                      out_ld=out_init.shape[-1], mut=mut)
+    v, allow = ep["value"], ep["allow"]
     stored = round_to(v, dtype)
     out = out_init.clone()
     if shuffle_c:
@@ -260,7 +411,7 @@ def conv2d(inp, w, out_init, *, cin, cout, ipe, ks, stride, pad, dtype, in_share
             out[:, q >> 1::2, q & 1::2, out_coff:out_coff + c] = stored[..., q * c:(q + 1) * c]
     else:
         out[..., out_coff:out_coff + cout] = stored
-    r = {"acc": acc, "pre": v, "stored": stored, "out": out}
+    r = {"acc": acc, "pre": v, "stored": stored, "out": out, "allow": allow, "keep": ep["keep"], "undropped": ep["undropped"]}
     if stats:
         t1 = stored.reshape(E, -1, cout)
         t2 = t1 * (t1 if xhat is None else xhat.reshape(E, -1, cout))
@@ -314,6 +465,9 @@ def wgrad(x, dy, *, cin, cout, cinp, coutp, ipe, ks, stride, pad, dtype, x_share
 #       ipe = 1 under BatchNorm sets of ipe images, the ECA-gated stem)     -- stride 2: the zero-dilated form (`dilate`)
 #   w:  pimg (per_image) | bn (bn_fused) | shared (x_shared)
 #   win (any launch): input, output and residual are channel windows of wider rows, NaN outside
+#   the MLP forms (MLP_FLAGS; a case that names one runs on the dyadic kind alone):
+#   f:  elu | tanh | sigmoid, drop | dropL | dropE (drop_p = 0.3 under seed 5 | a seed above 2^32 | edge_seed: one element's
+#       hash EQUALS p)        d:  delu | dtanh | dsigmoid (and drelu), + drop: the saved output was dropped out under that seed
 # ``switches``: environment values the launch is planned and run under.
 Case = collections.namedtuple("Case", "E ipe cin cout H W ks stride dtype request switches codes")
 
@@ -545,18 +699,82 @@ CASES = [
     _case(1, 2, 8, 64, 16, 16, 3, 1, BF16, "f: d: w:pimg+bn", (None, None, 7209)),
     _case(2, 2, 64, 128, 20, 36, 3, 1, BF16, "f: d: w:pimg+win", (None, None, 7309)),
     _case(1, 2, 64, 64, 16, 16, 3, 1, F32, "f: d: w:", (None, None, 6912)),
+    # ---- gemm_skinny_kernel<4> (csrc/gemm_skinny.hip): bf16 launches without statistics of <= 3200 output rows per expert.  One
+    #      workgroup per 64 rows x 64 channels of one expert; wave w takes the 16-channel k-slices w, w + 4, ... of every tap.
+    #      The MLP form (1x1 images): one k-slice (waves 1-3 add zero tiles) and one valid channel vector of 64; a ragged second
+    #      row block, an idle fourth wave and a second column block with 8 valid channels; three row blocks with a fifth slice for
+    #      wave 0 (past the `#pragma unroll 4`); a shared input
+    _case(2, 5, 16, 8, 1, 1, 1, 1, BF16, "f:bias d: w:", (3000, None, None)),
+    _case(3, 70, 48, 72, 1, 1, 1, 1, BF16, "f:bias+relu+win d: w:", (3000, None, None)),
+    _case(1, 130, 272, 64, 1, 1, 1, 1, BF16, "f:add d:addin w:", (3000, 3000, None)),
+    _case(2, 7, 80, 24, 1, 1, 1, 1, BF16, "f:shared+bias d: w:", (3000, None, None)),
+    #      the tap loop: borders on all sides; odd sides at stride 2; 1x1 at stride 2; 75 and 196 rows, so that a 64-row block
+    #      spans image boundaries and ends ragged
+    _case(2, 1, 16, 16, 7, 5, 3, 1, BF16, "f:bias+relu d:add+win w:", (3000, 3000, None)),
+    _case(1, 3, 32, 64, 9, 7, 3, 2, BF16, "f:add+win d: w:", (3000, None, None)),
+    _case(2, 2, 48, 32, 10, 6, 1, 2, BF16, "f:addin d: w:", (3000, None, None)),
+    _case(1, 3, 16, 16, 5, 5, 3, 1, BF16, "f:drelu+win d:drelu w:", (3000, 3000, None)),
+    _case(1, 1, 16, 16, 14, 14, 3, 1, BF16, "f:shared d:bias w:", (3000, 3000, None)),
+    #      exactly 3200 rows per expert, the most the kernel takes (2 x 40 x 41: tests/test_conv_cpu.py, plan only)
+    _case(1, 2, 16, 16, 40, 40, 1, 1, BF16, "f:bias d: w:", (3000, None, None)),
+    #      the MLP epilogue forms (conv_ref.mlp_epilogue), on the dyadic kind: bias + elu + drop is the MLP layer, delu + drop its
+    #      data gradient (a data gradient reduces over the layer's outputs: whole k-slices of 16, so not on every shape)
+    _case(2, 5, 16, 8, 1, 1, 1, 1, BF16, "f:elu+bias+drop d: w:", (3000, None, None)),
+    _case(3, 70, 48, 72, 1, 1, 1, 1, BF16, "f:bias+tanh+dropL+win d: w:", (3000, None, None)),
+    _case(1, 130, 272, 64, 1, 1, 1, 1, BF16, "f:sigmoid d:dsigmoid+dropL w:", (3000, 3000, None)),
+    _case(1, 130, 272, 64, 1, 1, 1, 1, BF16, "f:elu+dropL d:delu+win w:", (3000, 3000, None)),
+    _case(2, 7, 80, 24, 1, 1, 1, 1, BF16, "f:shared+elu d: w:", (3000, None, None)),
+    _case(2, 1, 16, 16, 7, 5, 3, 1, BF16, "f:bias+sigmoid+dropE d:delu+drop w:", (3000, 3000, None)),
+    _case(2, 1, 16, 16, 7, 5, 3, 1, BF16, "f:tanh+drop d:dtanh w:", (3000, 3000, None)),
+    _case(1, 3, 16, 16, 5, 5, 3, 1, BF16, "f:drop+win d:dtanh+drop w:", (3000, 3000, None)),
+    _case(1, 1, 16, 16, 14, 14, 3, 1, BF16, "f:bias+relu+dropL d:drelu+drop+win w:", (3000, 3000, None)),
+    _case(1, 1, 16, 16, 14, 14, 3, 1, BF16, "f:sigmoid+win d:dsigmoid w:", (3000, 3000, None)),
+    _case(1, 3, 32, 64, 9, 7, 3, 2, BF16, "f:tanh d: w:", (3000, None, None)),
+    # ---- the other two copies of that epilogue (EPILOGUE_COPY): conv_igemm.hip -- a 1x1 launch just over 3200 rows in bf16, the
+    #      f32 MLP path -- and conv_dma_epilogue.inc (two-phase f32 read-out)
+    _case(1, 51, 16, 16, 8, 8, 1, 1, BF16, "f:bias+elu+drop d:delu+drop w:", (541, 541, None)),
+    _case(1, 51, 16, 16, 8, 8, 1, 1, BF16, "f:tanh+dropL+win d:dtanh+win w:", (541, 541, None)),
+    _case(1, 51, 16, 16, 8, 8, 1, 1, BF16, "f:sigmoid d:dsigmoid+dropL w:", (541, 541, None)),
+    _case(2, 5, 16, 8, 1, 1, 1, 1, F32, "f:elu+bias+dropE d: w:", (641, None, None)),
+    _case(3, 70, 48, 72, 1, 1, 1, 1, F32, "f:bias+tanh+win d: w:", (622, None, None)),
+    _case(1, 130, 272, 64, 1, 1, 1, 1, F32, "f:sigmoid+dropL d:dsigmoid w:", (641, 741, None)),
+    _case(1, 130, 272, 64, 1, 1, 1, 1, F32, "f: d:delu+drop w:", (None, 741, None)),
+    _case(1, 130, 272, 64, 1, 1, 1, 1, F32, "f: d:dtanh+drop+win w:", (None, 741, None)),
+    _case(1, 3, 64, 128, 40, 36, 3, 1, BF16, "f:bias+elu+drop d: w:", (5007, None, None)),
+    _case(1, 3, 64, 128, 40, 36, 3, 1, BF16, "f:tanh+dropL+win d: w:", (5007, None, None)),
+    _case(1, 3, 64, 128, 40, 36, 3, 1, BF16, "f:sigmoid d: w:", (5007, None, None)),
+    _case(1, 3, 128, 64, 40, 36, 3, 1, BF16, "f: d:delu+drop w:", (None, 5007, None)),
+    _case(1, 3, 128, 64, 40, 36, 3, 1, BF16, "f: d:dtanh+win w:", (None, 5007, None)),
+    _case(1, 3, 128, 64, 40, 36, 3, 1, BF16, "f: d:dsigmoid+dropL w:", (None, 5007, None)),
 ]
-# plan codes the coverage rules of tests/test_conv_cpu.py do not ask a case for, and why (3000 does run, as the data gradient of
-# three small cases, but not form by form)
+# plan codes the coverage rules of tests/test_conv_cpu.py do not ask a case for, and why
 EXCLUDED = {
-    3000: "gemm_skinny_kernel, the expert MLP GEMMs: with pmoe_mlp_wgrad",
     8000: "e4m3 operands (8000 + a generic-tile code, 8507): tests/test_fp8_gpu.py",
 }
 TILE_CODES = (522, 541, 542, 622, 641, 642, 722, 741, 2007)
 
 
 def is_excluded(code):
-    return code == 3000 or code == 8507 or code - 8000 in TILE_CODES
+    return code == 8507 or code - 8000 in TILE_CODES
+
+
+# The three copies of the MLP epilogue (mlp_epilogue), by plan code.  A code that is not here belongs to a kernel whose planner
+# refuses every MLP form (conv_res.hip, conv_c16.hip, conv_c1x1.hip, and the producer-wave / persistent instantiations of
+# conv_dma.hip, which take plain launches only): test_every_plan_code_of_the_grid_has_a_case asserts from the grid that no such
+# code ever answers a descriptor with one of the forms, and that every (copy, dtype, form) the grid reaches has a case.  The
+# LDS-DMA kernels do take them -- a 3x3 layer of >= 4096 pixels per expert with an activation or dropout runs on
+# conv_dma_epilogue.inc's two-phase read-out (5007 | 5017 | 5207; the parity-class launches 9207 take the forward forms only).
+EPILOGUE_COPY = {
+    3000: "gemm_skinny.hip",
+    **{c: "conv_igemm.hip" for c in TILE_CODES}, **{4000 + c: "conv_igemm.hip" for c in TILE_CODES},
+    **{c: "conv_dma_epilogue.inc" for c in (5007, 5017, 5207, 9207)},
+}
+
+
+def kinds_of(case):
+    """the kinds a case runs on: the MLP forms on the dyadic kind, everything else on the lattice and unit kinds"""
+    fl = flags(case)
+    return (DYADIC,) if any(fl[k] and fl[k] & MLP_FLAGS for k in "fd") else KINDS
 
 
 def case_id(case):
@@ -645,12 +863,94 @@ def _out_buffer(shape_c, cout, win, fill=None):
     return buf, coff
 
 
+def _sparse_ints(g, shape, K):
+    """integers of +-1 and +-2, non-zero with probability 4.8 / K: against weights uniform on the multiples of 1/64 in [-1, 1] a
+    sum over K terms has a standard deviation of about 2 -- pre-activations all over (-8, 8), on some thousand distinct
+    multiples of 1/64"""
+    t = torch.randint(1, 3, shape, generator=g) * (2 * torch.randint(0, 2, shape, generator=g) - 1)
+    return (t * (torch.rand(shape, generator=g) < min(1.0, 4.8 / K))).to(F64) + 0.0
+
+
+def _dyadic(g, shape):
+    """multiples of 1/64 in [-1, 1]: exact in bfloat16"""
+    return torch.randint(-64, 65, shape, generator=g).to(F64) / 64
+
+
+def saved_output(g, shape, mode, drop_p, seed, dtype):
+    """what a D-mode launch reads: the reference's own forward output of the matching activation (ReLU for PMOE_RES_DRELU) under
+    the same drop_p, in storage precision, of pre-activations on the multiples of 1/64 -- with exact zeros among them, kept and
+    dropped.  Standard deviation 1.5, narrower than the forward cases': 1 - u^2 and u (1 - u) of a SATURATED saved output cancel
+    to a few bfloat16 steps of u, the carried error of u is then a visible share of the result, and the stored value of every
+    such element is open between two neighbours -- few of them keep the launch under the cap on open elements"""
+    z = (torch.randn(shape, generator=g, dtype=F64) * 96).round().clamp(-511, 511) / 64
+    z.view(-1)[::37] = 0
+    ep = mlp_epilogue(z, None, res_mode=RES_NONE, act=ACT_OF_DMODE[mode], drop_p=drop_p, seed=seed)
+    return round_to(ep["value"], dtype), z
+
+
+def _dyadic_launches(case):
+    """launches() of a case that names an MLP form.  Forward: sparse integer activations, dyadic weights and biases; filter row 0
+    of expert 0 and its bias are zero, so that exact zeros are among the pre-activations.  Data gradient: the same for dy and
+    the filter, the residual is saved_output."""
+    E, ipe, cin, cout, H, W, ks, stride, dtype = case[:9]
+    fl = flags(case)
+    g = torch.Generator().manual_seed(sum(ord(ch) * (i + 1) for i, ch in enumerate(case_id(case) + DYADIC)))
+    N, pad = E * ipe, ks // 2
+    Ho, Wo = out_size(H, ks, stride, pad), out_size(W, ks, stride, pad)
+    out = {}
+
+    def dropout(f, kw):
+        for name in DROP_FLAGS:
+            if name in f:
+                kw.update(drop_p=DROP_P, seed=SEED_OF[name])
+
+    f = fl["f"]
+    if f is not None:
+        assert not f - MLP_FLAGS - {"bias", "relu", "shared", "win"}, f
+        shared, win = "shared" in f, "win" in f
+        w = _dyadic(g, (E, cout, cin, ks, ks))
+        w[0, 0] = 0
+        L = {"w": w, "bias": None, "res": None, "bn_coef": None, "res_is_out": False}
+        kw = dict(cin=cin, cout=cout, ipe=ipe, ks=ks, stride=stride, pad=pad, dtype=dtype, in_shared=shared, stats=False)
+        if "bias" in f:
+            L["bias"] = _dyadic(g, (E, cout))
+            L["bias"][0, 0] = 0
+        kw["act"] = ACT_RELU if "relu" in f else next((a for n, a in ACT_FLAGS.items() if n in f), ACT_NONE)
+        dropout(f, kw)
+        L["inp"], kw["in_coff"] = _window(_sparse_ints(g, (ipe if shared else N, H, W, cin), cin * ks * ks), win)
+        L["out_init"], kw["out_coff"] = _out_buffer((N, Ho, Wo), cout, win)
+        L["kw"] = kw
+        out["f"] = L
+
+    d = fl["d"]
+    if d is not None:
+        assert not d - MLP_FLAGS - {"bias", "drelu", "win"}, d
+        win = "win" in d
+        K = cout * ks * ks // (1 if stride == 1 else 4 if ks == 3 else 1)
+        L = {"w": _dyadic(g, (E, cin, cout, ks, ks)), "bias": None, "res": None, "bn_coef": None, "res_is_out": False}
+        kw = dict(cin=cout, cout=cin, ipe=ipe, ks=ks, stride=1, pad=ks - 1 - pad, dtype=dtype, dilate=stride == 2, stats=False)
+        kw["res_mode"] = RES_DRELU if "drelu" in d else next(m for n, m in DMODE_FLAGS.items() if n in d)
+        dropout(d, kw)
+        if "bias" in d:
+            L["bias"] = _dyadic(g, (E, cin))
+        L["inp"], kw["in_coff"] = _window(_sparse_ints(g, (N, Ho, Wo, cout), K), win)
+        L["out_init"], kw["out_coff"] = _out_buffer((N, H, W), cin, win)
+        y, L["saved_z"] = saved_output(g, (N, H, W, cin), kw["res_mode"], kw.get("drop_p", 0.0), kw.get("seed", 0), dtype)
+        L["res"], kw["res_coff"] = _window(y, win, 48, 32)
+        L["kw"] = kw
+        out["d"] = L
+    return out
+
+
 @functools.lru_cache(maxsize=4)
 def launches(case, kind):
     """{"f" | "d" | "w": launch}: the tensors (float64 values representable in the case's storage type) and keywords of the three
     launches of a case.  A conv launch: inp, w (logical, the launch's own orientation), out_init, bias, res, bn_coef and ``kw``
     (the keywords of conv_ref.conv2d = those of ops.conv2d, but for the tensors); ``res_is_out``: the residual IS the output
     buffer.  A weight-gradient launch: x, dy, bn and ``kw``."""
+    assert kind in kinds_of(case), (kind, case_id(case))
+    if kind == DYADIC:
+        return _dyadic_launches(case)
     E, ipe, cin, cout, H, W, ks, stride, dtype = case[:9]
     fl = flags(case)
     g = torch.Generator().manual_seed(sum(ord(ch) * (i + 1) for i, ch in enumerate(case_id(case) + kind)))
@@ -774,10 +1074,19 @@ def launches(case, kind):
     return out
 
 
-def conv_reference(L, rounding="once"):
+def conv_reference(L, rounding="once", mut=""):
     """conv2d of a launch of ``launches``"""
     res = L["out_init"] if L["res_is_out"] else L["res"]
-    return conv2d(L["inp"], L["w"], L["out_init"], bias=L["bias"], res=res, bn_coef=L["bn_coef"], rounding=rounding, **L["kw"])
+    return conv2d(L["inp"], L["w"], L["out_init"], bias=L["bias"], res=res, bn_coef=L["bn_coef"], rounding=rounding, mut=mut, **L["kw"])
+
+
+def stored_interval(ref, dtype):
+    """(lo, hi) of the stored window: a float32 value within ``allow`` of the reference's rounds into [round(pre - allow),
+    round(pre + allow)] -- rounding is monotonic -- which is one value wherever both ends round alike.  float32 storage:
+    pre -+ allow itself."""
+    if dtype == F32:
+        return ref["pre"] - ref["allow"], ref["pre"] + ref["allow"]
+    return round_to(ref["pre"] - ref["allow"], dtype), round_to(ref["pre"] + ref["allow"], dtype)
 
 
 def wgrad_reference(L, evaluate=F64):
@@ -802,3 +1111,62 @@ def abs_bound(L):
         res = L["out_init"] if L["res_is_out"] else L["res"]
         a = a + res[..., kw["res_coff"]:kw["res_coff"] + kw["cout"]].abs()
     return a.max().item()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# pmoe_mlp_wgrad (csrc/gemm_skinny.hip, mlp_wgrad_kernel): weight and bias gradient of a Linear layer of all experts
+
+WGRAD_MUTANTS = ("bias64",       # the bias gradient summed over the first 64 rows only
+                 "padleak")      # the first pad channel of x added into the last real input column of grads
+
+
+def mlp_wgrad(x, dy, *, cin, cout, cin_real, cout_real, ipe, x_shared=False, x_coff=0, dy_coff=0, evaluate=F64, reverse=False, mut=""):
+    """x [Nx, x_ld], dy [N, dy_ld] -> grads [E, cout_real, cin_real], bias_grads [E, cout_real] as include/pmoe_hip.h states them:
+    grads[e][o][i] = sum_m dy[e ipe + m][dy_coff + o] x[(x_shared ? m : e ipe + m)][x_coff + i], bias_grads[e][o] = sum_m dy[...].
+    Evaluated in ``evaluate``, row by row (``reverse``: from the last row down -- another summation order)"""
+    E = dy.shape[0] // ipe
+    g = dy[:, dy_coff:dy_coff + cout_real].to(evaluate).reshape(E, ipe, cout_real)
+    xs = x[:, x_coff:x_coff + cin_real].to(evaluate)
+    xs = xs[None].expand(E, ipe, cin_real) if x_shared else xs.reshape(E, ipe, cin_real)
+    assert not torch.isnan(g).any() and not torch.isnan(xs).any()
+    grads, bias = torch.zeros(E, cout_real, cin_real, dtype=evaluate), torch.zeros(E, cout_real, dtype=evaluate)
+    for m in (reversed(range(ipe)) if reverse else range(ipe)):
+        grads = grads + g[:, m, :, None] * xs[:, m, None, :]
+        if mut != "bias64" or m < 64:
+            bias = bias + g[:, m]
+    if mut == "padleak" and cin_real < cin:
+        xp = x[:, x_coff + cin_real].to(evaluate)
+        xp = xp[None].expand(E, ipe) if x_shared else xp.reshape(E, ipe)
+        grads[:, :, -1] += torch.einsum("emo,em->eo", g, xp)
+    return {"grads": grads, "bias_grads": bias}
+
+
+# (E, ipe, cin, cin_real, cout, cout_real, x_shared, x_coff, dy_coff): one row, one input tile; a shared input with one real
+# input column; whole 64 x 64 x 64 tiles; a second row chunk of ONE row and ragged tiles in both directions; three row chunks on
+# channel windows
+MLP_WGRAD_CASES = [
+    (2, 1, 8, 8, 8, 8, False, 0, 0),
+    (2, 7, 16, 1, 16, 5, True, 0, 0),
+    (3, 64, 64, 64, 64, 64, False, 0, 0),
+    (1, 65, 72, 70, 136, 130, False, 0, 0),
+    (2, 130, 96, 90, 80, 72, False, 16, 32),
+]
+PAD_FILL = 2.0 ** 60            # the staged pad channels [cin_real, cin) and [cout_real, cout): large and finite (130 products of
+#                                 two of them still are), so that one leaking into an output cannot hide
+GUARD = 8                       # sentinel elements past the end of grads and bias_grads
+
+
+@functools.lru_cache(maxsize=None)
+def mlp_wgrad_data(case, kind):
+    """x, dy (float64 values exact in bfloat16) and the keywords of mlp_wgrad: +-7 integers (unit: {-1, 0, 1}) -- at most 130 rows,
+    so every float32 sum is exact in any order; NaN outside the channel windows, PAD_FILL in the pad channels"""
+    E, ipe, cin, cin_real, cout, cout_real, shared, xc, dc = case
+    g = torch.Generator().manual_seed(sum((i + 1) * int(v) for i, v in enumerate(case)) + len(kind))
+
+    def rows(n, c, c_real, coff):
+        t = torch.full((n, coff + c + (8 if coff else 0)), float("nan"), dtype=F64)
+        t[:, coff:coff + c] = PAD_FILL * (2 * torch.randint(0, 2, (n, c), generator=g) - 1)
+        t[:, coff:coff + c_real] = _ints(g, (n, c_real), 7, kind)
+        return t
+    kw = dict(cin=cin, cout=cout, cin_real=cin_real, cout_real=cout_real, ipe=ipe, x_shared=shared, x_coff=xc, dy_coff=dc)
+    return {"x": rows(ipe if shared else E * ipe, cin, cin_real, xc), "dy": rows(E * ipe, cout, cout_real, dc), "kw": kw}

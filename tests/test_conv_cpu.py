@@ -1,8 +1,11 @@
 """The float64 convolution reference (tests/conv_ref.py) checked against float64 torch.autograd of F.conv2d / F.conv_transpose2d /
 F.batch_norm, its input generators checked for everything tests/test_conv_gpu.py assumes of them, and the case table checked
 against the planners: every case plans to the codes it names, and every code the planners can answer over a grid of shapes,
-requests and switches is in the table or on its short exclusion list.  No GPU: pmoe_conv2d_plan and pmoe_conv2d_wgrad_plan are
-host code."""
+requests and switches is in the table or on its short exclusion list.  The same for the MLP epilogue forms (activations, their
+derivatives from the saved output, fused dropout: conv_ref.mlp_epilogue on the dyadic kind, with a case for every copy of that
+epilogue the planner reaches) and for pmoe_mlp_wgrad with every refusal of its entry point; and the proof that the inputs
+discriminate: each deliberately wrong variant of the reference is told apart by some case.  No GPU: pmoe_conv2d_plan and
+pmoe_conv2d_wgrad_plan are host code, and a refused call launches nothing."""
 import ctypes as C
 import itertools
 
@@ -13,6 +16,7 @@ import torch.nn.functional as F
 from pmoe_amd import hip, ops
 from tests import bn_ref
 from tests import conv_ref as R
+from tests import eca_head_ref as H
 from tests.stem_tail_ref import bf16_boundary_distance
 
 F64, F32, BF16 = R.F64, R.F32, R.BF16
@@ -52,8 +56,8 @@ def conv_prepare(L, t, stats=None):
         stride=kw["stride"], pad=kw["pad"], dilate=kw.get("dilate", False), in_shared=kw.get("in_shared", False),
         in_coff=kw["in_coff"], out_coff=kw["out_coff"], res=t["res"], res_coff=kw.get("res_coff", 0),
         res_mode=kw.get("res_mode", hip.RES_NONE), bias=t["bias"], act=kw.get("act", hip.ACT_NONE),
-        stats=(True if stats is None else stats) if kw["stats"] else None, bn_coef=t["bn_coef"], bn_ipe=kw.get("bn_ipe", 0),
-        shuffle2_c=kw.get("shuffle_c", 0), shapes_only=t["x"].device.type == "meta")
+        drop_p=kw.get("drop_p", 0.0), seed=kw.get("seed", 0), stats=(True if stats is None else stats) if kw["stats"] else None,
+        bn_coef=t["bn_coef"], bn_ipe=kw.get("bn_ipe", 0), shuffle2_c=kw.get("shuffle_c", 0), shapes_only=t["x"].device.type == "meta")
 
 
 def wgrad_desc(L):
@@ -78,8 +82,8 @@ def set_switches(monkeypatch, case):
         monkeypatch.setenv(k, v)
 
 
-def planned_codes(case, kind="unit"):
-    ls = R.launches(case, kind)
+def planned_codes(case):
+    ls = R.launches(case, R.kinds_of(case)[-1])
     conv = lambda k: conv_prepare(ls[k], conv_tensors(ls[k], "meta")).plan() if k in ls else None
     return conv("f"), conv("d"), wgrad_plan(ls["w"])[0] if "w" in ls else None
 
@@ -115,6 +119,13 @@ REQUESTS = {
     "dgrad": ({}, True), "dgrad+bias": (dict(bias=True), True), "dgrad+add": (dict(res_mode=hip.RES_ADD), True),
     "dgrad+addin": (dict(res_mode=hip.RES_ADD), True), "dgrad+drelu": (dict(res_mode=hip.RES_DRELU), True),
     "dgrad+dbn": (dict(res_mode=hip.RES_DBN, stats=True), True), "dgrad+dbn+bias": (dict(res_mode=hip.RES_DBN, stats=True, bias=True), True),
+    # the MLP epilogue forms (conv_ref.mlp_epilogue)
+    "elu": (dict(act=hip.ACT_ELU), False), "tanh": (dict(act=hip.ACT_TANH), False), "sigmoid": (dict(act=hip.ACT_SIGMOID), False),
+    "drop": (dict(drop_p=R.DROP_P, seed=5), False), "bias+elu+drop": (dict(bias=True, act=hip.ACT_ELU, drop_p=R.DROP_P, seed=5), False),
+    "dgrad+delu": (dict(res_mode=hip.RES_DELU), True), "dgrad+dtanh": (dict(res_mode=hip.RES_DTANH), True),
+    "dgrad+dsigmoid": (dict(res_mode=hip.RES_DSIGMOID), True), "dgrad+delu+drop": (dict(res_mode=hip.RES_DELU, drop_p=R.DROP_P), True),
+    "delu": (dict(res_mode=hip.RES_DELU), False), "dtanh": (dict(res_mode=hip.RES_DTANH), False),
+    "dsigmoid": (dict(res_mode=hip.RES_DSIGMOID), False),
 }
 
 
@@ -122,6 +133,11 @@ REQUESTS = {
 # another descriptor, so a (code, dtype, form) counts as run whichever of a case's two conv launches carries it.
 FORM_OF = {"bias": "bias", "dgrad+bias": "bias", "bias+relu": "relu", "add": "add", "dgrad+add": "add", "dgrad+addin": "addin",
            "drelu": "drelu", "dgrad+drelu": "drelu", "shared": "shared", "stats": "stats"}
+# the second, coarser rule: the requests that carry an MLP epilogue form -> the forms.  The form's code exists in three copies
+# (conv_ref.EPILOGUE_COPY); every (copy, dtype, form) the planner lets a descriptor reach has a case, whichever tile code runs it.
+MLP_FORMS_OF = {"elu": ("elu",), "tanh": ("tanh",), "sigmoid": ("sigmoid",), "drop": ("drop",), "bias+elu+drop": ("elu", "drop"),
+                "dgrad+delu": ("delu",), "dgrad+dtanh": ("dtanh",), "dgrad+dsigmoid": ("dsigmoid",), "dgrad+delu+drop": ("delu",),
+                "delu": ("delu",), "dtanh": ("dtanh",), "dsigmoid": ("dsigmoid",)}
 
 
 def _grid_plan(lib, E, ipe, cin, cout, side, ks, stride, dtype, name):
@@ -144,7 +160,7 @@ def _grid_plan(lib, E, ipe, cin, cout, side, ks, stride, dtype, name):
 def test_every_plan_code_of_the_grid_has_a_case(monkeypatch):
     """plans only: channels x sides x images per expert x filter x stride x dtype x request x per-launch switch"""
     lib = hip.load()
-    seen, accepted = {"conv": set(), "wgrad": set()}, set()
+    seen, accepted, accepted_mlp, no_copy = {"conv": set(), "wgrad": set()}, set(), set(), set()
     for sw in CONV_SWITCHES:
         with monkeypatch.context() as m:
             if sw:
@@ -157,6 +173,10 @@ def test_every_plan_code_of_the_grid_has_a_case(monkeypatch):
                         seen["conv"].add(code)
                         if name in FORM_OF and not R.is_excluded(code):
                             accepted.add((code, dtype, FORM_OF[name]))
+                        if name in MLP_FORMS_OF:
+                            if code not in R.EPILOGUE_COPY:
+                                no_copy.add((code, name))
+                            accepted_mlp |= {(R.EPILOGUE_COPY.get(code), dtype, form) for form in MLP_FORMS_OF[name]}
     for sw in WGRAD_SWITCHES:
         with monkeypatch.context() as m:
             if sw:
@@ -174,7 +194,7 @@ def test_every_plan_code_of_the_grid_has_a_case(monkeypatch):
     covered = {"conv": {c for case in R.CASES for c in case.codes[:2] if c is not None},
                "wgrad": {case.codes[2] for case in R.CASES if case.codes[2] is not None}}
     excluded = R.is_excluded
-    assert sorted(R.EXCLUDED) == [3000, 8000], "the exclusion list is the skinny GEMM and the e4m3 codes, nothing else"
+    assert sorted(R.EXCLUDED) == [8000], "the exclusion list is the e4m3 codes, nothing else"
     for k in seen:
         missing = sorted(c for c in seen[k] - covered[k] if not excluded(c))
         assert not missing, f"{k} plan codes without a case: {missing}"
@@ -195,6 +215,22 @@ def test_every_plan_code_of_the_grid_has_a_case(monkeypatch):
     assert not missing, f"(code, dtype, form) accepted by the planner and run by no case: {missing}"
     unwindowed = sorted(c for c in covered["conv"] - windowed if not excluded(c))
     assert not unwindowed, f"plan codes no case runs on channel windows: {unwindowed}"
+    # the MLP epilogue forms: only the kernels that carry a copy of that epilogue ever answer a descriptor that asks for one, and
+    # every (copy, dtype, form) the grid reaches is run by a case
+    assert not no_copy, f"MLP forms planned onto codes outside conv_ref.EPILOGUE_COPY: {sorted(no_copy)}"
+    ran_mlp = set()
+    for case in R.CASES:
+        fl = R.flags(case)
+        for i, k in enumerate("fd"):
+            for form in (fl[k] or ()):
+                form = "drop" if form in R.DROP_FLAGS and k == "f" else form
+                if form in R.ACT_FLAGS or form in R.DMODE_FLAGS or form == "drop":
+                    assert case.codes[i] in R.EPILOGUE_COPY, (case, k)
+                    ran_mlp.add((R.EPILOGUE_COPY[case.codes[i]], case.dtype, form))
+    print("MLP forms reached on the grid:", sorted((c, str(d), f) for c, d, f in accepted_mlp))
+    assert {c for c, _, _ in accepted_mlp} == set(R.EPILOGUE_COPY.values()), "a copy of the epilogue that no MLP form reaches"
+    missing = sorted((c, str(d), f) for c, d, f in accepted_mlp - ran_mlp)
+    assert not missing, f"(epilogue copy, dtype, form) accepted by the planner and run by no case: {missing}"
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -204,8 +240,13 @@ def _representable(t, dtype):
     return torch.equal(t.to(dtype).to(F64)[~torch.isnan(t)], t[~torch.isnan(t)])
 
 
-@pytest.mark.parametrize("kind", R.KINDS)
-@pytest.mark.parametrize("case", R.CASES, ids=IDS)
+def case_kinds(cases, kinds=R.KINDS + (R.DYADIC,)):
+    """(case, kind) for every kind the case runs on, with the ids the two stacked parametrisations gave before the dyadic kind"""
+    return dict(argnames="case,kind", argvalues=[(c, k) for k in kinds for c in cases if k in R.kinds_of(c)],
+                ids=[f"{R.case_id(c)}-{k}" for k in kinds for c in cases if k in R.kinds_of(c)])
+
+
+@pytest.mark.parametrize(**case_kinds(R.CASES, R.KINDS))
 def test_generator_properties(case, kind):
     ls = R.launches(case, kind)
     dtype = case.dtype
@@ -415,3 +456,212 @@ def test_reference_scaled_and_gated_packs():
     want = R.conv2d(x * gate[:, None, None, :cin], w, blank, cin=cin, cout=cout, ipe=ipe, ks=ks, stride=1, pad=1, dtype=F64)["stored"]
     assert relerr(yg, want) < 1e-12
     assert torch.equal(gd, R.pack_weights(unpack(gf), cout, cin, F64, cin, cout)[1])
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the MLP epilogue forms: the dyadic generator, the reference against autograd, the skinny GEMM's row limit, the mutants
+
+DYADIC_CASES = [c for c in R.CASES if R.kinds_of(c) == (R.DYADIC,)]
+AMBIGUOUS_CAP = 0.02
+
+
+def test_edge_seed_makes_one_hash_equal_p():
+    p = torch.tensor(R.DROP_P, dtype=F32).to(F64)
+    u = H.hash_uniform(R.SEED_OF["dropE"], R.EDGE_INDEX + 2)
+    assert u[R.EDGE_INDEX] == p and (u != p).sum() == R.EDGE_INDEX + 1
+    assert R.SEED_OF["dropL"] > 2 ** 32 > R.SEED_OF["drop"] and R.SEED_OF["dropE"] > 2 ** 32
+
+
+@pytest.mark.parametrize(**case_kinds(DYADIC_CASES, (R.DYADIC,)))
+def test_dyadic_generator_properties(case, kind):
+    """what tests/test_conv_gpu.py assumes of the dyadic kind: representable, sums exact in any order, pre-activations spread over
+    the unsaturated range with exact zeros, saved outputs on both sides with dropped zeros, few outputs whose stored value the
+    allowance leaves open"""
+    ls = R.launches(case, kind)
+    dtype = case.dtype
+    for k in ("f", "d"):
+        if k not in ls:
+            continue
+        L = ls[k]
+        kw = L["kw"]
+        for name in ("inp", "w", "out_init", "res"):
+            assert L[name] is None or _representable(L[name], dtype), (k, name)
+        assert L["bias"] is None or _representable(L["bias"], F32)
+        bound = R.abs_bound(L)
+        assert bound * 64 < 2 ** 24, (k, bound)                               # (every term a multiple of 1/64)
+        ref = R.conv_reference(L)
+        xw = L["inp"][..., kw["in_coff"]:kw["in_coff"] + kw["cin"]]
+        ho, wo = ref["acc"].shape[1:3]
+        geo = dict(ipe=kw["ipe"], in_shared=kw.get("in_shared", False), stride=kw["stride"], pad=kw["pad"], ho=ho, wo=wo,
+                   dilate=kw.get("dilate", False))
+        for taps in (False, True):
+            assert torch.equal(R.conv_acc(xw, L["w"], dtype=F32, taps=taps, **geo).to(F64), ref["acc"]), (k, taps)
+        pre, allow = ref["pre"], ref["allow"]
+        assert (allow >= 0).all() and torch.equal(pre[allow == 0], R._f32(pre[allow == 0])), "an exact element is a float32 value"
+        lo, hi = R.stored_interval(ref, dtype)
+        nz = ref["stored"] != 0
+        open_ = ((lo != hi) & nz).sum().item() / max(nz.sum().item(), 1)
+        print(f"{k}: {nz.sum().item()} non-zero outputs, {100 * (allow[nz] == 0).float().mean().item():.1f} % exact, "
+              f"{100 * open_:.3f} % with two possible stored values; max sum|x||w| {bound:.1f}")
+        if dtype == BF16:
+            assert open_ <= AMBIGUOUS_CAP, (k, open_)
+        drop, act, mode = kw.get("drop_p", 0.0) > 0, kw.get("act", R.ACT_NONE), kw.get("res_mode", R.RES_NONE)
+        if k == "f":
+            v = ref["acc"] if L["bias"] is None else ref["acc"] + L["bias"].repeat_interleave(kw["ipe"], 0)[:, None, None, :]
+            if act >= R.ACT_ELU:
+                share = [((v > a) & (v <= b) if a < -1 else (v >= a) & (v < b) if a >= 1 else (v > a) & (v < b)).float().mean().item()
+                         for a, b in ((-8, -1), (-1, 0), (0, 1), (1, 8))]
+                print(f"f: pre-activations in (-8, -1], (-1, 0), (0, 1), [1, 8): {[round(s, 3) for s in share]}, "
+                      f"{torch.unique(v).numel()} distinct")
+                assert min(share) >= 0.10, share
+            assert (v == 0).any() and (v > 0).any() and (v < 0).any()
+            if drop:
+                assert 0.6 < ref["keep"].float().mean().item() < 0.8 and (ref["undropped"][~ref["keep"]] != 0).any()
+            if kw.get("seed") == R.SEED_OF["dropE"]:
+                e = R.EDGE_INDEX
+                assert ref["keep"].flatten()[e] and ref["stored"].flatten()[e] != 0, "the element whose hash equals p is kept and shows"
+        else:
+            r = L["res"][..., kw["res_coff"]:kw["res_coff"] + kw["cout"]]
+            u = r / H.keep_scale(kw.get("drop_p", 0.0), F64)
+            mid = 0.5 if mode == R.RES_DSIGMOID else 0.0
+            assert (u > mid).any() and ((u < mid) & (r != 0)).any() or mode == R.RES_DRELU and (r > 0).any(), k
+            assert (r == 0).any() or (mode == R.RES_DSIGMOID and not drop), k           # (a sigmoid is zero only where dropped)
+            if drop:
+                assert ((r == 0) & (L["saved_z"] != 0)).any() and ((r != 0) & (ref["stored"] != 0)).any(), k
+
+
+@pytest.mark.parametrize("p", [0.0, R.DROP_P])
+@pytest.mark.parametrize("act", ["relu", "elu", "tanh", "sigmoid"])
+def test_reference_mlp_forms_match_autograd(act, p):
+    """act(linear) * mask * keep_scale and its data gradient from the saved output, against float64 autograd under the
+    reference's own mask (continuous data: the float32 roundings of the exact paths stay below 1e-6)"""
+    E, ipe, cin, cout = 2, 9, 6, 8
+    g = torch.Generator().manual_seed(17)
+    rn = lambda *s: torch.randn(*s, generator=g, dtype=F64)
+    N = E * ipe
+    x, w, b, dy = rn(N, 1, 1, cin), rn(E, cout, cin, 1, 1), rn(E, cout), rn(N, 1, 1, cout)
+    geo = dict(ipe=ipe, ks=1, stride=1, pad=0, dtype=F64, drop_p=p, seed=5)
+    blank = torch.zeros(N, 1, 1, cout, dtype=F64)
+    f = R.conv2d(x, w, blank, cin=cin, cout=cout, bias=b, act=hip.ACT_BY_NAME[act], **geo)
+    xr = x.clone().requires_grad_(True)
+    z = torch.cat([F.linear(xr[e * ipe:(e + 1) * ipe], w[e, :, :, 0, 0], b[e]) for e in range(E)])
+    y = {"relu": F.relu, "elu": F.elu, "tanh": torch.tanh, "sigmoid": torch.sigmoid}[act](z) * f["keep"] * H.keep_scale(p, F64)
+    y.backward(dy)
+    assert relerr(f["stored"], y.detach()) < 1e-6
+    assert p == 0 or 0.5 < f["keep"].float().mean() < 0.9
+    # the launch the engine runs: the gradient w.r.t. z of layer l is the data gradient of layer l + 1 times act'(saved output)
+    up = rn(N, 1, 1, cin)
+    w2 = rn(E, cout, cin, 1, 1)
+    h = R.conv2d(up, w2, blank, cin=cin, cout=cout, res=f["stored"], res_mode=hip.RES_OF_ACT[hip.ACT_BY_NAME[act]], **geo)
+    lin = R.conv2d(up, w2, blank, cin=cin, cout=cout, ipe=ipe, ks=1, stride=1, pad=0, dtype=F64)["stored"]
+    zr = z.detach().clone().requires_grad_(True)
+    ({"relu": F.relu, "elu": F.elu, "tanh": torch.tanh, "sigmoid": torch.sigmoid}[act](zr) * f["keep"] * H.keep_scale(p, F64)).backward(lin)
+    assert relerr(h["stored"], zr.grad) < 1e-6 and (h["allow"] >= 0).all()
+
+
+def test_skinny_row_limit():
+    """3200 output rows per expert plan to the skinny GEMM, 3280 do not (conv_ref.CASES runs the first)"""
+    plan = lambda W: ops.conv2d_plan(2, 40, W, 40, W, 16, 16, 64, 2, 1, 1, 0, torch.bfloat16)
+    assert plan(40) == 3000
+    assert plan(41) >= 0 and plan(41) != 3000
+
+
+def test_every_mutant_is_told_apart():
+    """each deliberately wrong variant of conv_ref.MUTANTS leaves the reference's interval of stored values on at least one launch
+    of the skinny-GEMM and MLP-form cases: the inputs can tell it from the kernel's contract"""
+    cases = [c for c in R.CASES if 3000 in c.codes[:2] or c in DYADIC_CASES]
+    caught = {}
+    for case in cases:
+        for kind in R.kinds_of(case):
+            ls = R.launches(case, kind)
+            for k in ("f", "d"):
+                if k not in ls:
+                    continue
+                ref = R.conv_reference(ls[k])
+                lo, hi = R.stored_interval(ref, case.dtype)
+                for mut in R.MUTANTS:
+                    if mut in caught:
+                        continue
+                    got = R.conv_reference(ls[k], mut=mut)["stored"]
+                    n = int(((got < lo) | (got > hi)).sum())
+                    if n:
+                        caught[mut] = f"{R.case_id(case)}-{kind} {k}: {n} elements"
+        if len(caught) == len(R.MUTANTS):
+            break
+    print("\n".join(f"{m}: {w}" for m, w in caught.items()))
+    assert not set(R.MUTANTS) - set(caught), f"mutants no case tells apart: {sorted(set(R.MUTANTS) - set(caught))}"
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# pmoe_mlp_wgrad: the reference, its generator, its mutants, and every refusal of the entry point
+
+WG_IDS = ["-".join(str(int(v)) for v in c) for c in R.MLP_WGRAD_CASES]
+
+
+def test_mlp_wgrad_reference_matches_autograd():
+    E, ipe, cin, cout = 3, 5, 7, 4
+    g = torch.Generator().manual_seed(23)
+    x, dy = torch.randn(E * ipe, cin + 3, generator=g, dtype=F64), torch.randn(E * ipe, cout + 5, generator=g, dtype=F64)
+    w, b = torch.zeros(E, cout, cin, dtype=F64, requires_grad=True), torch.zeros(E, cout, dtype=F64, requires_grad=True)
+    torch.cat([F.linear(x[e * ipe:(e + 1) * ipe, 2:2 + cin], w[e], b[e]) for e in range(E)]).backward(dy[:, 1:1 + cout])
+    r = R.mlp_wgrad(x, dy, cin=cin + 1, cout=cout + 1, cin_real=cin, cout_real=cout, ipe=ipe, x_coff=2, dy_coff=1)
+    assert relerr(r["grads"], w.grad) < 1e-12 and relerr(r["bias_grads"], b.grad) < 1e-12
+    w2 = torch.zeros(E, cout, cin, dtype=F64, requires_grad=True)
+    torch.cat([F.linear(x[:ipe, 2:2 + cin], w2[e]) for e in range(E)]).backward(dy[:, 1:1 + cout])
+    rs = R.mlp_wgrad(x[:ipe], dy, cin=cin + 1, cout=cout + 1, cin_real=cin, cout_real=cout, ipe=ipe, x_shared=True, x_coff=2, dy_coff=1)
+    assert relerr(rs["grads"], w2.grad) < 1e-12
+
+
+@pytest.mark.parametrize("kind", R.KINDS)
+@pytest.mark.parametrize("case", R.MLP_WGRAD_CASES, ids=WG_IDS)
+def test_mlp_wgrad_generator_properties(case, kind):
+    E, ipe, cin, cin_real, cout, cout_real, shared, xc, dc = case
+    d = R.mlp_wgrad_data(case, kind)
+    for t, c, c_real, coff in ((d["x"], cin, cin_real, xc), (d["dy"], cout, cout_real, dc)):
+        assert _representable(t, BF16)
+        outside = torch.ones(t.shape[1], dtype=torch.bool)
+        outside[coff:coff + c] = False
+        assert torch.isnan(t[:, outside]).all() and not torch.isnan(t[:, ~outside]).any()
+        assert (t[:, coff + c_real:coff + c].abs() == R.PAD_FILL).all() and t[:, coff:coff + c_real].abs().max() <= 7
+        assert ipe * R.PAD_FILL ** 2 < 3e38, "sums over the pad channels stay finite in float32"
+    ref = R.mlp_wgrad(d["x"], d["dy"], **d["kw"])
+    assert ipe * 49 < 2 ** 24
+    for reverse in (False, True):
+        r32 = R.mlp_wgrad(d["x"], d["dy"], evaluate=F32, reverse=reverse, **d["kw"])
+        assert torch.equal(r32["grads"].to(F64), ref["grads"]) and torch.equal(r32["bias_grads"].to(F64), ref["bias_grads"])
+    assert ref["grads"].abs().max() > 0 and (kind == "unit" or ipe < 7 or ref["grads"].abs().max() > 49)
+
+
+def test_every_mlp_wgrad_mutant_is_told_apart():
+    for mut in R.WGRAD_MUTANTS:
+        caught = []
+        for case in R.MLP_WGRAD_CASES:
+            for kind in R.KINDS:
+                d = R.mlp_wgrad_data(case, kind)
+                ref, m = R.mlp_wgrad(d["x"], d["dy"], **d["kw"]), R.mlp_wgrad(d["x"], d["dy"], mut=mut, **d["kw"])
+                if not (torch.equal(ref["grads"], m["grads"]) and torch.equal(ref["bias_grads"], m["bias_grads"])):
+                    caught.append((case, kind))
+        assert caught, mut
+
+
+# pmoe_mlp_wgrad(x, dy, grads, bias_grads, n, ipe, x_shared, cin, cout, cin_real, cout_real, x_ld, x_coff, dy_ld, dy_coff, dtype,
+# stream): one accepted argument list (made-up pointers: a refused call dereferences nothing and launches nothing) and the single
+# change that trips each `return PMOE_ERR_*` of pmoe_mlp_wgrad and mlp_wgrad_launch (csrc/gemm_skinny.hip), check by check
+MLP_WGRAD_OK = [0x1000, 0x2000, 0x3000, 0x4000, 8, 4, 0, 16, 16, 12, 12, 32, 8, 32, 8, hip._TORCH_DT[torch.bfloat16], None]
+MLP_WGRAD_REFUSED = [
+    ("x null", {0: None}, -1), ("dy null", {1: None}, -1), ("grads null", {2: None}, -1),
+    ("ipe 0", {5: 0}, -1), ("ipe negative", {5: -4}, -1), ("n no multiple of ipe", {4: 9}, -1),
+    ("cin % 8", {7: 12}, -1), ("cout % 8", {8: 12}, -1), ("x_ld % 8", {11: 36}, -1), ("x_coff % 8", {12: 4}, -1),
+    ("dy_ld % 8", {13: 36}, -1), ("dy_coff % 8", {14: 4}, -1),
+    ("x window overhangs", {12: 24}, -1), ("dy window overhangs", {14: 24}, -1),
+    ("cin_real 0", {9: 0}, -1), ("cin_real > cin", {9: 17}, -1), ("cout_real 0", {10: 0}, -1), ("cout_real > cout", {10: 17}, -1),
+    ("float32 rows", {15: hip._TORCH_DT[torch.float32]}, -2), ("unknown dtype", {15: 7}, -2),
+]
+
+
+@pytest.mark.parametrize("what,change,code", MLP_WGRAD_REFUSED, ids=[r[0].replace(" ", "_") for r in MLP_WGRAD_REFUSED])
+def test_mlp_wgrad_refusals(what, change, code):
+    args = list(MLP_WGRAD_OK)
+    for i, v in change.items():
+        args[i] = v
+    assert hip.load().pmoe_mlp_wgrad(*args) == code, what

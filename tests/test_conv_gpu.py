@@ -1,14 +1,21 @@
 """Every convolution kernel (csrc/conv_igemm.hip, conv_dma.hip + conv_dma_epilogue.inc, conv_res.hip, conv_c1x1.hip,
-conv_c16.hip, conv_wgrad.hip) and the weight packs against the float64 reference of their own operation (tests/conv_ref.py), at
-the smallest shapes that reach each plan code (conv_ref.CASES; tests/test_conv_cpu.py proves that the table covers every code the
-planners answer), through pmoe_amd.ops, the binding the engines use.
+conv_c16.hip, gemm_skinny.hip, conv_wgrad.hip), pmoe_mlp_wgrad and the weight packs against the float64 reference of their own
+operation (tests/conv_ref.py), at the smallest shapes that reach each plan code (conv_ref.CASES; tests/test_conv_cpu.py proves
+that the table covers every code the planners answer), through pmoe_amd.ops, the binding the engines use.
 
-Two kinds of input (tests/test_conv_cpu.py checks on the CPU what is assumed of them here):
+Three kinds of input (tests/test_conv_cpu.py checks on the CPU what is assumed of them here):
   lattice  integers with sum |x||w| < 2^24: a float32 accumulation is exact in any order, so every STORED element must equal the
            reference's, rounded in the order conv_ref.ROUNDING names for the kernel -- one missing or doubled term, a truncation, a
            second rounding or a residual left out all show as unequal elements.  Fused statistics: per-expert totals within
            (L + 8) 2^-24 sum|term|, L = conv_ref.chain_stats.
   unit     {-1, 0, 1}: nothing rounds and the statistics are exact too.
+  dyadic   the cases with an MLP epilogue form (ELU / tanh / sigmoid, their derivatives from the saved output, fused dropout), in
+           all three copies of that epilogue: the accumulator is exact, the pre-activations are spread over (-8, 8).  Where the
+           reference's allowance is zero -- no activation, ReLU, ELU's positive branch, every dropout product, every derivative
+           chain that float32 evaluates without a rounding -- the stored element must EQUAL the reference's; elsewhere it lies
+           in [round(ref - allow), round(ref + allow)], which is one value for all but a per cent of the elements.  The dropout
+           mask is compared element for element with the hash wherever the undropped value is non-zero.
+           Continuous data stays in tests/test_ops_gpu.py for the K-long float32 sums only.
 Every buffer is compared WHOLE: outputs are sentinel-filled before the launch, so pad channels, the other columns of out_ld, the
 untouched half of a concatenation buffer and the odd pixels of the in-place stride-2 1x1 gradient must come back unchanged;
 everything outside an input's channel window is NaN, so a read outside it poisons the output.  The plan code is asserted before
@@ -23,7 +30,7 @@ pytestmark = pytest.mark.gpu
 from pmoe_amd import hip, ops  # noqa: E402
 from tests import conv_ref as R  # noqa: E402
 from tests.test_bn_gpu import same  # noqa: E402
-from tests.test_conv_cpu import conv_prepare, conv_tensors, set_switches, wgrad_plan  # noqa: E402
+from tests.test_conv_cpu import case_kinds, conv_prepare, conv_tensors, set_switches, wgrad_plan  # noqa: E402
 
 DEV = "cuda"
 F64, F32, BF16 = R.F64, R.F32, R.BF16
@@ -54,11 +61,13 @@ def check_conv_launch(L, code_expected, kind, what):
     order = R.rounding_of(code, kw.get("res_mode", R.RES_NONE), L["bias"] is not None, kw.get("act", R.ACT_NONE))
     ref = R.conv_reference(L, order)
     got = t["out"].cpu().to(F64)
-    if not (got == ref["out"]).all():
+    if kind == R.DYADIC:
+        check_mlp_forms(got, ref, L, code, what)
+    elif not (got == ref["out"]).all():
         other = R.conv_reference(L, "staged" if order == "once" else "once")["out"]
         hint = f" (it DOES equal the '{'staged' if order == 'once' else 'once'}' order)" if (got == other).all() else ""
         same(got, ref["out"], f"{what}: code {code}, rounding order '{order}'{hint}")
-    if kw.get("res_mode", R.RES_NONE) not in (R.RES_DRELU, R.RES_DBN):
+    if kw.get("res_mode", R.RES_NONE) not in (R.RES_DRELU, R.RES_DELU, R.RES_DTANH, R.RES_DSIGMOID, R.RES_DBN):
         # the sign of a zero is exempt in MASKED gradients only (+0 or -0 by how the mask is applied): bit for bit elsewhere
         neg = torch.signbit(t["out"].float().cpu()) != torch.signbit(ref["out"].to(F32))
         assert not neg.any(), f"{what}: code {code}: {int(neg.sum())} elements differ in sign only (a zero of the other sign); first {neg.nonzero()[:4].tolist()}"
@@ -85,8 +94,44 @@ def check_conv_launch(L, code_expected, kind, what):
                                f"{bad.nonzero()[:4].tolist()}, worst err {err.max().item():.3e}")
 
 
-@pytest.mark.parametrize("kind", R.KINDS)
-@pytest.mark.parametrize("case", CONV_CASES, ids=ids(CONV_CASES))
+def check_mlp_forms(got, ref, L, code, what):
+    """a launch with an MLP epilogue form: the window within the reference's interval of stored values (equal where the allowance
+    is zero), the dropout mask equal to the hash mask, everything outside the window untouched"""
+    kw = L["kw"]
+    dtype, c0, c1 = kw["dtype"], kw["out_coff"], kw["out_coff"] + kw["cout"]
+    outside = torch.ones(got.shape[-1], dtype=torch.bool)
+    outside[c0:c1] = False
+    same(got[..., outside], ref["out"][..., outside], f"{what}: code {code}: channels outside the output window")
+    win = got[..., c0:c1]
+    assert not torch.isnan(win).any(), f"{what}: code {code}: NaN in the output window (a read outside an input window?)"
+    if kw.get("drop_p", 0.0) > 0 and kw.get("res_mode", R.RES_NONE) < R.RES_DRELU:
+        seen = ref["undropped"] != 0
+        wrong = ((win != 0) != ref["keep"]) & seen
+        assert not wrong.any(), (f"{what}: code {code}: the dropout mask differs from hash_uniform(seed, opix * Cout + c) >= p in "
+                                 f"{int(wrong.sum())} elements; first {wrong.nonzero()[:4].tolist()}")
+    lo, hi = R.stored_interval(ref, dtype)
+    exact = ref["allow"] == 0
+    bad = (win < lo) | (win > hi)
+    nz = ref["stored"] != 0
+    off = (win - ref["pre"]).abs()
+    if dtype == BF16:
+        # the least error of the float32 value that explains the stored bfloat16: its distance to the reference beyond half a step
+        off_f32 = (off - torch.ldexp(torch.ones_like(win), torch.frexp(win)[1] - 9)).clamp_min(0)
+    else:
+        off_f32 = off
+    ratio = (off_f32[~exact] / ref["allow"][~exact]).max().item() if (~exact).any() else 0.0
+    print(f"{what}: code {code}: {int(exact.sum())} of {exact.numel()} elements exact (all equal: {bool((win == ref['stored'])[exact].all())}); "
+          f"{int(((lo != hi) & nz).sum())} open between two stored values, {int(((win != ref['stored']) & ~bad).sum())} of them on the "
+          f"neighbour of the rounded reference; worst error of the float32 value / allowance {ratio:.3f}; "
+          f"worst |got - ref| / |ref| {(off / ref['pre'].abs().clamp_min(1e-30))[nz].max().item() if nz.any() else 0.0:.3e}")
+    if bad.any():
+        i = bad.nonzero()[:6]
+        rows = [(tuple(j.tolist()), win[tuple(j)].item(), lo[tuple(j)].item(), hi[tuple(j)].item(), ref["allow"][tuple(j)].item()) for j in i]
+        raise AssertionError(f"{what}: code {code}: {int(bad.sum())} of {bad.numel()} elements outside [round(ref - allow), round(ref + allow)] "
+                             f"({int((bad & exact).sum())} of them where the allowance is zero); first (index, got, lo, hi, allow): {rows}")
+
+
+@pytest.mark.parametrize(**case_kinds(CONV_CASES))
 def test_conv_launches_match_reference(case, kind, monkeypatch):
     """forward and data gradient of the case, each under its request: stored output, untouched bytes, statistics"""
     set_switches(monkeypatch, case)
@@ -184,3 +229,34 @@ def test_weight_packs_match_reference(shape, dtype):
     ops.unpack_conv_wgrad(ws.to(F32).to(DEV), grads, E, cout, cin, ks, cop, cip)
     torch.cuda.synchronize()
     same(grads, R.unpack_wgrad(ws, cout, cin, ks), "pmoe_unpack_conv_wgrad")
+
+
+@pytest.mark.parametrize("kind", R.KINDS)
+@pytest.mark.parametrize("case", R.MLP_WGRAD_CASES, ids=["-".join(str(int(v)) for v in c) for c in R.MLP_WGRAD_CASES])
+def test_mlp_wgrad_matches_reference(case, kind):
+    """pmoe_mlp_wgrad with and without bias_grads: both outputs exact and whole (sentinels around them: the pad channels staged
+    with 2^60, the NaN outside the channel windows and the rows of the next expert reach nothing), grads bit-identical between
+    the two launches, inputs unmodified"""
+    E, ipe, cin, cin_real, cout, cout_real, shared, xc, dc = case
+    d = R.mlp_wgrad_data(case, kind)
+    ref = R.mlp_wgrad(d["x"], d["dy"], **d["kw"])
+    x = d["x"].to(BF16).to(DEV).reshape(-1, 1, 1, d["x"].shape[1])
+    dy = d["dy"].to(BF16).to(DEV).reshape(-1, 1, 1, d["dy"].shape[1])
+    ng, nb = E * cout_real * cin_real, E * cout_real
+    runs = []
+    for with_bias in (True, False):
+        gbuf = torch.full((ng + R.GUARD,), SENTINEL, dtype=F32, device=DEV)
+        bbuf = torch.full((nb + R.GUARD,), SENTINEL, dtype=F32, device=DEV)
+        ops.mlp_wgrad(x, dy, gbuf[:ng], bbuf[:nb] if with_bias else None, **d["kw"])
+        torch.cuda.synchronize()
+        want_g = torch.cat([ref["grads"].flatten(), torch.full((R.GUARD,), SENTINEL, dtype=F64)])
+        want_b = torch.cat([ref["bias_grads"].flatten() if with_bias else torch.full((nb,), SENTINEL, dtype=F64),
+                            torch.full((R.GUARD,), SENTINEL, dtype=F64)])
+        same(gbuf, want_g, f"grads with its guard (bias_grads {'set' if with_bias else 'null'})")
+        same(bbuf, want_b, f"bias_grads with its guard (bias_grads {'set' if with_bias else 'null'})")
+        runs.append(gbuf)
+    assert torch.equal(runs[0], runs[1]), "grads differ between the launches with and without bias_grads"
+    for name, t, src in (("x", x, d["x"]), ("dy", dy, d["dy"])):
+        back = t.cpu().to(F64).reshape(src.shape)
+        assert torch.equal(torch.isnan(back), torch.isnan(src)) and torch.equal(back.nan_to_num(), src.nan_to_num()), f"{name} modified"
+    print(f"mlp_wgrad {case} {kind}: grads {tuple(ref['grads'].shape)} and bias_grads exact, max |grad| {ref['grads'].abs().max().item():.0f}")
