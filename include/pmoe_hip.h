@@ -434,7 +434,8 @@ int pmoe_moe_loss(const float* probs, const float* mean, const float* std_, cons
 
 /* ---- PU-Net / PMoE model types.  The U-Nets are frozen on this path
  * (moe.py:280): forward only.
- * MaxPool2d(2,2) (blocks/unet.py:29): x is a channel window [x_coff, x_coff+C) of rows x_ld wide, y dense [N][H/2][W/2][C]. */
+ * MaxPool2d(2,2) (blocks/unet.py:29): x is a channel window [x_coff, x_coff+C) of rows x_ld wide, y dense [N][H/2][W/2][C].
+ * A NaN in a window gives NaN, as torch.max_pool2d and pmoe_maxpool2s2_bwd (which routes the gradient to it) have it. */
 int pmoe_maxpool2s2_fwd(const void* x, void* y, int32_t N, int32_t H, int32_t W, int32_t C, int32_t x_ld,
                         int32_t x_coff, int32_t dtype, void* stream);
 /* ConvTranspose2d(k=2, s=2) (unet.py:34-44) = one 1x1 GEMM with 4*C output rows (row (dy*2+dx)*C + c, packed by the
@@ -529,7 +530,7 @@ int pmoe_add_window(const void* src, int32_t src_ld, int32_t src_coff, void* dst
 int pmoe_cat_windows(const void* const* srcs, int32_t K, int32_t c, int32_t src_ld, int32_t src_coff, void* dst,
                      int32_t dst_ld, int32_t dst_c, int64_t rows, int32_t dtype, void* stream);
 /* module boundary of PredictiveUnet.forward (punet.py:117-120 returns NCHW f32): src T [N][HW][src_ld] channel window
- * -> dst f32 [N][C][HW] */
+ * -> dst f32 [N][C][HW].  C <= 639: 64 pixels x (C + 1) floats are staged in the 160 KiB of LDS of a CU. */
 int pmoe_nhwc_to_nchw(const void* src, int32_t src_ld, int32_t src_coff, float* dst, int32_t N, int64_t HW, int32_t C,
                       int32_t dtype, void* stream);
 /* AutoregressiveCriterion (trainer/loss.py:86-118).  logits f32 [B][F][C][H][W], target int64 [B][F][H][W], C <= 32.

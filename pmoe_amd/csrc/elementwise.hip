@@ -350,7 +350,10 @@ __global__ void __launch_bounds__(256) bn_apply_pool2_kernel(const T* __restrict
             float rr[VE];
             unpack16<T>(pk, rr);                     // the pooled value is the max of the STORED values
 #pragma unroll
-            for (int k = 0; k < VE; ++k) m[k] = q ? fmaxf(m[k], rr[k]) : rr[k];
+            for (int k = 0; k < VE; ++k) {           // (a NaN wins, as in maxpool2_kernel: fmaxf alone drops it)
+                if (q == 0) m[k] = rr[k];
+                else m[k] = (m[k] != m[k] || rr[k] != rr[k]) ? __builtin_nanf("") : fmaxf(m[k], rr[k]);
+            }
         }
         stg16(pooled + ((size_t)e * (rpe / 4) + ((size_t)n * Ho + oy) * Wo + ox) * C + (size_t)cv * VE, pack16<T>(m));
     }

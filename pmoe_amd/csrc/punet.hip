@@ -28,7 +28,10 @@ __global__ void __launch_bounds__(256) maxpool2_kernel(const T* __restrict__ x, 
         unpack16<T>(ldg16(p + (size_t)W * x_ld), c);
         unpack16<T>(ldg16(p + (size_t)W * x_ld + x_ld), d);
 #pragma unroll
-        for (int k = 0; k < VE; ++k) a[k] = fmaxf(fmaxf(a[k], b[k]), fmaxf(c[k], d[k]));
+        for (int k = 0; k < VE; ++k) {      // a NaN in the window wins, as in torch and in maxpool2_bwd_kernel (fmaxf drops it)
+            const float m = fmaxf(fmaxf(a[k], b[k]), fmaxf(c[k], d[k]));
+            a[k] = (a[k] != a[k] || b[k] != b[k] || c[k] != c[k] || d[k] != d[k]) ? __builtin_nanf("") : m;
+        }
         stg16(y + (size_t)i * VE, pack16<T>(a));
     }
 }

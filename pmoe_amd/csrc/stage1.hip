@@ -481,12 +481,15 @@ int pmoe_cat_windows(const void* const* srcs, int32_t K, int32_t c, int32_t src_
     });
 }
 
+constexpr int NCHW_MAX_C = 160 * 1024 / (64 * (int)sizeof(float)) - 1;      // 639
+
 int pmoe_nhwc_to_nchw(const void* src, int32_t src_ld, int32_t src_coff, float* dst, int32_t N, int64_t HW, int32_t C,
                       int32_t dtype, void* stream) {
-    if (N < 1 || HW < 1 || C < 1 || src_coff + C > src_ld || C > 1024) return PMOE_ERR_ARG;
+    /* the [64][C + 1] f32 tile must fit the 160 KiB of dynamic LDS that launch<> opts the kernel in to: C <= NCHW_MAX_C */
+    if (N < 1 || HW < 1 || C < 1 || src_coff + C > src_ld || C > NCHW_MAX_C) return PMOE_ERR_ARG;
     const long long nblk = (HW + 63) / 64 * N;
     if (nblk > 0x7fffffffLL) return PMOE_ERR_ARG;
-    DISPATCH_DT(dtype, return launch<nhwc_to_nchw_kernel<T>, 0>(dim3((unsigned)nblk), dim3(256), 64 * (C + 1) * sizeof(float),
+    DISPATCH_DT(dtype, return launch<nhwc_to_nchw_kernel<T>>(dim3((unsigned)nblk), dim3(256), 64 * (C + 1) * sizeof(float),
                                                                 (hipStream_t)stream, (const T*)src, src_ld, src_coff, dst, N,
                                                                 (long long)HW, C));
 }

@@ -26,7 +26,7 @@ holds them to the constants:
   (none above 4).  T_f = twice the measured worst, rounded up to a whole unit, never below 1.
 
 Left out on purpose: the grid-stride loops of maxpool_* and of the plain nchw_to_nhwc kernel (they need inputs of tens of millions
-of elements), the fp8 weight pack, and the U-Net kernels of csrc/punet.hip and csrc/stage1.hip.
+of elements) and the fp8 weight pack.  (The U-Net kernels of csrc/punet.hip, csrc/stage1.hip and csrc/stage0.hip: tests/unet_ref.py.)
 
 act_bwd works from the SAVED output: with dropout an element whose saved output is zero counts as dropped (for tanh and ELU that
 includes an input of exactly 0 that was kept); the reference follows the kernel's contract here, not torch's autograd.
