@@ -404,6 +404,26 @@ int pmoe_eca_stem_fold(const float* G, const float* gate, const void* const* w_p
 int pmoe_eca_bwd_apply(const void* dy, const float* gate, const float* dgap, void* dx, int32_t N, int64_t HW,
                        int32_t C, int32_t dtype, void* stream);
 
+/* ---- gradients with respect to the network's inputs.  images, speed and command are shared by the E experts of a mixture
+ * (moe.py:141-149 calls every expert on the same tensors), the gradients upstream of them are per expert: both entry points
+ * sum over the experts inside their reduction, in f32 and in a fixed order (no atomics: bit-reproducible).
+ *
+ * d loss / d images through the stem's gate and first convolution (backward of basics.py:61-76,86-106 on the frames that
+ * moe.py:90-92 concatenates along channels):
+ *   dx[b][c][h][w] = sum_e ( sum_{r,s,co} dz1[e*B+b][h-1+r][w-1+s][co] * wd[e*B+b][c][3r+s][co]  +  dgap[e*B+b][c] )
+ * dz1: T [E*B][H][W][64], the gradient of conv1's output.  wd: the data-gradient operand that pmoe_pack_conv_weights_gated
+ * writes, T [E*B][cinp2][9][coutp2] (gate folded in, taps flipped; cinp2 >= 16, coutp2 >= 64 and a multiple of 8).  dgap: f32
+ * [E*B][16], the gradient through the gate's pooled input already divided by H*W (pmoe_eca_bwd_small with dgap_scale), or NULL.
+ * dx: f32 [B][creal][H][W], the layout of images.view(B,-1,H,W) -- written whole; the padding channels creal..15 of the
+ * 16-channel rows have no plane and nothing else is written.  bf16: one MFMA kernel that reads dz1 once; f32: the parity form. */
+int pmoe_stem_input_grad(const void* dz1, const void* wd, const float* dgap, float* dx, int32_t E, int32_t B, int32_t H,
+                         int32_t W, int32_t creal, int32_t cinp2, int32_t coutp2, int32_t dtype, void* stream);
+/* d loss / d speed and d loss / d command through the first Linear of speed_encoder / command_encoder (moe.py:55-56,88-89;
+ * basics.py:30-42):  dx[b][j] = sum_e sum_o dh[e*B+b][dh_coff+o] * w[e][o][j].  dh: T [E*B][dh_ld], the gradient of the
+ * layer's pre-activation output; w: its forward pack T [E][coutp][cinp]; dx: f32 [B][cin]. */
+int pmoe_shared_linear_input_grad(const void* dh, int32_t dh_ld, int32_t dh_coff, const void* w, float* dx, int32_t E, int32_t B,
+                                  int32_t cout, int32_t coutp, int32_t cinp, int32_t cin, int32_t dtype, void* stream);
+
 /* ---- layout: images f32 [B][Cin][H][W] (images.view(B,-1,H,W), moe.py:90-92) -> T [B][H][W][Cp] */
 int pmoe_nchw_to_nhwc(const float* src, void* dst, int32_t B, int32_t C, int32_t H, int32_t W, int32_t Cp,
                       int32_t dtype, void* stream);

@@ -72,7 +72,7 @@ BNFused = collections.namedtuple("BNFused", "g coef c1 c2")          # Var.bn_fu
 class Var:
     """A device activation [N,H,W,ld] (+ channel window) with its gradient slot."""
     __slots__ = ("t", "coff", "c", "g", "needs_grad", "act", "drop_p", "base", "gap_part", "bn_src", "bn_part", "f8", "bn_defer",
-                 "bn_fused", "pending_bn")
+                 "bn_fused", "pending_bn", "sink")
 
     def __init__(self, t, c=None, coff=0, needs_grad=False, base=None):
         self.t, self.coff, self.c = t, coff, (c if c is not None else t.shape[-1])
@@ -85,6 +85,8 @@ class Var:
         self.bn_fused = None                 # BNFused left by _bn_bwd_reduced for that consumer instead of dL/dt (_stem_in_bwd)
         self.pending_bn = None               # BNCoef: t is the PRE-activation z of a BatchNorm + ReLU that its one consumer
                                              # applies on load (PMOE_RES_INBN) or engine_punet._materialize writes out (untaped U-Net forward)
+        self.sink = None                     # t is a padded copy of the caller's "speed" / "command", which wants its gradient: the
+                                             # first Linear's backward sums it over the experts (_shared_in_bwd)
 
     @property
     def grad(self):
@@ -255,6 +257,7 @@ class ExpertGroupEngine:
     pooled_stem_bwd = True        # stem-tail BatchNorm reductions from the pooled tensors (train mode)
     fold_eca_gate = True          # ECA gate folded into per-image conv weights (no gated activation in memory)
     overlap_wgrad = False         # weight gradients on a side HIP stream; the one option with an environment name (see __init__)
+    _in_grads = (False, False, False)      # this call's (images, speed, command) want their gradient: ``in_grads`` of forward
 
     def __init__(self, experts, alt=False, shared_k=0):
         """``shared_k`` > 0: MixtureOfExpertsShared (moe.py:180-233) -- ``experts`` is the one module that owns the
@@ -288,6 +291,9 @@ class ExpertGroupEngine:
         # ("maxpool").  tests/forced_masks.py hands them to its float64 checker so that both sides differentiate the SAME
         # piecewise-linear function (two f32 evaluations disagree on the sign of pre-activations within ~1e-7 of zero)
         self.debug_acts = None
+        # dict -> backward keeps the operands and the result of the stem-input-gradient launch: "dz1", "wd", "dgap", "dx"
+        # (tests/test_input_grad_gpu.py evaluates its float64 reference on exactly what the kernel read)
+        self.debug_input_grad = None
         self._collect()
 
     # ------------------------------------------------------------------ structure
@@ -590,7 +596,19 @@ class ExpertGroupEngine:
             dy.record_stream(side)
         elif layer.trainable:
             self._wgrad_block(x, layer, o, dy, in_shared, flop)
+        if x.sink is not None:
+            return self._shared_in_bwd(x, layer, o, dy)
         self._dgrad_block(x, layer, o, dy, flop)
+
+    def _shared_in_bwd(self, x, layer, o, dy):
+        """x is the (padded) speed or command, shared by the experts, and wants its gradient: sum_e dy_e W_e in one launch, f32
+        [B, cin] -- not the generic data gradient, which would write E*B rows into a tensor of B"""
+        if layer.w_fwd is None or x.t.shape[0] != self.B:
+            raise RuntimeError(f"{layer.name}: the gradient of a shared input needs the layer's forward pack")
+        dx = torch.empty(self.B, layer.cin, dtype=F32, device=self.dev)
+        ops.set_meta(name=layer.name + ":dinput")
+        ops.shared_linear_input_grad(dy, layer.w_fwd, dx, self.E, layer.cout, dh_coff=o.coff)
+        self._input_grads[x.sink] = dx
 
     def _side_stream(self):
         st = self.__dict__.get("_side")
@@ -1176,9 +1194,13 @@ class ExpertGroupEngine:
         self.tape = None
         return Bsz
 
-    def forward(self, images, speed, command, training, taping, dtype, base_seed=0):
+    def forward(self, images, speed, command, training, taping, dtype, base_seed=0, in_grads=None):
         """Returns probs [B,K], mean [B,K,2], std [B,K,2], speeds [B,K,1] ([B,1] for the shared trunk), f32, and
-        the tape."""
+        the tape.  ``in_grads``: which of (images, speed, command) want their gradient (taping must be on): backward leaves them,
+        summed over the experts, in ``state["input_grads"]`` under those names."""
+        self._in_grads = tuple(bool(w) for w in in_grads) if in_grads is not None else (False, False, False)
+        if any(self._in_grads) and not taping:
+            raise RuntimeError("input gradients need the backward tape")
         Bsz = self._begin(images, training, taping, dtype, base_seed)
         x0 = self._image_input(images)
         spd, cmd = self._measurement_inputs(speed, command)
@@ -1196,14 +1218,21 @@ class ExpertGroupEngine:
         H, W = x0.t.shape[1], x0.t.shape[2]
         hw_ok = H * W >= 256                                 # per-image filter gradients need one tile <= one image
         fold2 = self.fold_eca_gate and hw_ok and self.conv2.cin % 64 == 0
-        if self.fold_stem_input and self.taping and hw_ok and (self.conv1.trainable or self.eca1.trainable):
+        want_dx = self._in_grads[0]
+        if want_dx and not hw_ok:
+            raise NotImplementedError("the gradient with respect to images needs frames of at least 256 pixels (its gate term comes "
+                                      "from the per-image filter gradients)")
+        # (an image gradient takes the filter-gradient backward whatever fold_stem_input says: the gate's dgap is a reduction of
+        #  conv1's per-EXPERT data gradient, which the plain route would have to write first -- DESIGN.md section 2)
+        if self.taping and hw_ok and (want_dx or (self.fold_stem_input and (self.conv1.trainable or self.eca1.trainable))):
             # backward of (ECA gate -> conv1) from per-image filter gradients: no data-gradient conv (heads.hip)
             x0s, gate, gapmean = self._eca(x0, self.eca1, shared=True, tape=False)
             z1, st = self._conv_stats(x0s, self.conv1, tape=False)
             z1.needs_grad = True
             # round 4: bn_c1's backward apply happens inside conv1's per-image filter gradient (dz1, 2.15 GB at the headline shape,
             # is never written): possible because that launch is the only consumer of dz1
-            z1.bn_defer = (self.training and self.dtype == torch.bfloat16
+            # (not with an image gradient: dz1 then has a second consumer, the stem-input-gradient launch, and is written)
+            z1.bn_defer = (self.training and self.dtype == torch.bfloat16 and not want_dx
                            and fold2 and ops.conv2d_wgrad_bn_served(z1.t.shape[0], H, W, z1.t.shape[1], z1.t.shape[2], self.conv1.cinp,
                                                                     self.conv1.cout_st, 64, 64, self.B, 3, 1, self.conv1.pad, self.dtype,
                                                                     x_ld=x0.t.shape[-1], dy_ld=z1.t.shape[-1], x_shared=True,
@@ -1283,7 +1312,8 @@ class ExpertGroupEngine:
         ops.gate_mixture_fwd(head5.t.view(self.N, -1), sp.t.view(self.N, 16), probs, mean, std, speeds, Bsz, K,
                              self._alpha_mode(), self.shared)
         self._bump_batch_counters()
-        state = dict(tape=self.tape, tail=(head5, sp, probs), B=self.B, N=self.N, dev=self.dev, dtype=self.dtype)
+        state = dict(tape=self.tape, tail=(head5, sp, probs), B=self.B, N=self.N, dev=self.dev, dtype=self.dtype,
+                     in_names=[n for n, want in zip(("images", "speed", "command"), self._in_grads) if want])
         self.tape = None
         return probs, mean, std, speeds, state
 
@@ -1300,6 +1330,9 @@ class ExpertGroupEngine:
         ops.pad_rows(speed.contiguous().float(), spd.t.view(Bsz, 16))
         cmd = Var(self._new(Bsz, 1, 1, 16))
         ops.pad_rows(command.contiguous().float(), cmd.t.view(Bsz, 16))
+        for v, name, want in ((spd, "speed", self._in_grads[1]), (cmd, "command", self._in_grads[2])):
+            if want:
+                v.sink, v.needs_grad = name, True
         return spd, cmd
 
     def _bump_batch_counters(self):
@@ -1349,7 +1382,25 @@ class ExpertGroupEngine:
                      bytes=(2 if z1.bn_fused is not None else 1) * dy.numel() * dy.element_size())
         f = z1.bn_fused                                  # dy is f.g (masked gradient of the BatchNorm output): dz1 on load
         fuse = (z1.t, f.coef.block, f.c1, f.c2) if f is not None else None
-        self._filter_grads(x0.t, dy, layer, self.eca1, gate, gapmean, x_shared=True, bn_fuse=fuse)
+        want_dx = self._in_grads[0]
+        H, W = dy.shape[1], dy.shape[2]
+        if not want_dx:
+            self._filter_grads(x0.t, dy, layer, self.eca1, gate, gapmean, x_shared=True, bn_fuse=fuse)
+            return
+        dgap = self._filter_grads(x0.t, dy, layer, self.eca1, gate, gapmean, want_dgap=True, dgap_scale=1.0 / (H * W),
+                                  x_shared=True, bn_fuse=fuse)
+        # d loss / d images: the gated data-gradient packs of this call's (expert, image) pairs, then ONE launch that sums the
+        # experts inside its reduction and writes the caller's [B, T*C, H, W] planes (csrc/input_grad.hip)
+        wd = torch.empty(self.N, layer.dg_rows, layer.taps, layer.dg_red, dtype=self.dtype, device=self.dev)
+        ops.pack_conv_weights_gated(self._tab("w", layer), gate, None, wd, self.N, self.B, layer.cout, layer.cin, layer.ks,
+                                    layer.coutp, layer.cinp, layer.dg_rows, layer.dg_red, self.dtype)
+        dx = torch.empty(self.B, layer.cin, H, W, dtype=F32, device=self.dev)
+        ops.set_meta(flop=2.0 * self.N * H * W * layer.cout * layer.cinp * layer.taps, name=layer.name + ":dinput",
+                     bytes=dy.numel() * dy.element_size() + dx.numel() * 4)
+        ops.stem_input_grad(dy, wd, dgap, dx, self.E)
+        self._input_grads["images"] = dx
+        if self.debug_input_grad is not None:
+            self.debug_input_grad.update(dz1=dy, wd=wd, dgap=dgap, dx=dx)
 
     def _filter_grads(self, xt, dy, layer, ecal, gate, gapmean, want_dgap=False, dgap_scale=1.0, **wgrad_kw):
         """backward of conv(x * gate) through per-image filter gradients G[n] = dy (x) x (no gated activation, no data-gradient
@@ -1416,6 +1467,7 @@ class ExpertGroupEngine:
         self._layout_arena()
         self._arena = torch.zeros(self._arena_numel, dtype=F32, device=self.dev)
         self._filled, self._cursor = set(), 0
+        self._input_grads = tape_state["input_grads"] = {}      # per rank: never part of the data-parallel exchange
         reducer = None
         if self.dp_group is not None or (dist.is_initialized() and self.dp_enabled):
             reducer = BucketedAllReduce(self.dp_group, self.dp_buckets, self.dp_always)

@@ -111,6 +111,8 @@ SIGNATURES = {
     "pmoe_eca_bwd_small": [_P, _I, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _F, _P],
     "pmoe_eca_stem_fold": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "pmoe_eca_bwd_apply": [_P, _P, _P, _P, _I, _L, _I, _I, _P],
+    "pmoe_stem_input_grad": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    "pmoe_shared_linear_input_grad": [_P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "pmoe_nchw_to_nhwc": [_P, _P, _I, _I, _I, _I, _I, _I, _P],
     "pmoe_pad_rows": [_P, _P, _I, _I, _I, _I, _P],
     "pmoe_gate_mixture_fwd": [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],

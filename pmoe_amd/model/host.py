@@ -17,22 +17,32 @@ def set_default_compute_dtype(dtype):
 
 
 class EngineFn(torch.autograd.Function):
-    """A whole engine forward as one autograd node: ``args`` are the non-parameter arguments of ``engine.forward`` (none of them
-    takes a gradient), the differentiable inputs are the flat parameter list."""
+    """A whole engine forward as one autograd node: ``args`` are the non-parameter arguments of ``engine.forward``; the
+    differentiable inputs are the flat parameter list and, behind it, those input tensors (also held by ``args``) that want a
+    gradient -- the ones the engine's state names in ``state["in_names"]``, in that order.  The engine's backward leaves their
+    gradients in ``state["input_grads"]`` under those names; they are per rank, never reduced."""
 
     @staticmethod
-    def forward(ctx, engine, args, *params):
+    def forward(ctx, engine, args, *tensors):
         *outs, state = engine.forward(*args)
         ctx.engine, ctx.state = engine, state
         ctx.set_materialize_grads(False)      # an unused output (e.g. pred_speed under pmoe_loss) leaves its head's .grad None
-        ctx.param_ids = [id(p) for p in params]
+        names = tuple(state.get("in_names", ())) if isinstance(state, dict) else ()
+        n_par = len(tensors) - len(names)
+        ctx.param_ids = [id(p) for p in tensors[:n_par]]
+        ctx.inputs = [(name, t.shape, t.dtype) for name, t in zip(names, tensors[n_par:])]
         return tuple(outs)
 
     @staticmethod
     def backward(ctx, *douts):
         grads = ctx.engine.backward(ctx.state, *douts)
+        found = ctx.state.get("input_grads", {}) if ctx.inputs else {}
         ctx.state = None
         out = [grads.get(i) if need else None for i, need in zip(ctx.param_ids, ctx.needs_input_grad[2:])]
+        for (name, shape, dtype), need in zip(ctx.inputs, ctx.needs_input_grad[2 + len(ctx.param_ids):]):
+            if need and name not in found:
+                raise RuntimeError(f"pmoe_amd: the backward pass left no gradient for the input {name!r}")
+            out.append(found[name].view(shape).to(dtype) if need else None)
         return (None, None) + tuple(out)
 
 

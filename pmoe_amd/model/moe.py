@@ -55,11 +55,21 @@ class _Grouped(EngineHost, nn.Module):
     def _make_engine(self):
         return ExpertGroupEngine(self._expert_list(), alt=self._alt(), shared_k=self._shared_k())
 
+    input_grads = True        # images / speed / command that require grad get one (PUNetExpert: its frames pass a frozen PU-Net first)
+
     def _run(self, images, speed, command):
         eng, dtype, taping = self.resolve_engine()
         seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if self.training else 0
-        # -> (probs, mean, std, speeds) for the mixtures; (actions, pred_speed) for PUNetExpert
-        return EngineFn.apply(eng, (images, speed, command, self.training, taping, dtype, seed), *eng.flat_params)
+        args = (images, speed, command, self.training, taping, dtype, seed)
+        # grad mode is off inside Function.forward: which inputs want a gradient is read here, and such a call is taped even
+        # with every parameter frozen (saliency on an eval-mode, frozen policy)
+        want = tuple(self.input_grads and torch.is_grad_enabled() and torch.is_tensor(t) and t.requires_grad
+                     for t in (images, speed, command))
+        if not any(want):         # the default path: the same node, the same launches
+            # -> (probs, mean, std, speeds) for the mixtures; (actions, pred_speed) for PUNetExpert
+            return EngineFn.apply(eng, args, *eng.flat_params)
+        return EngineFn.apply(eng, args[:4] + (True,) + args[5:] + (want,), *eng.flat_params,
+                              *[t for t, w in zip((images, speed, command), want) if w])
 
 
 class BaseExpert(_Grouped):
@@ -188,6 +198,7 @@ class PUNetExpert(_Grouped):
     """``moe.py:268-323``: frozen PU-Net (future segmentation masks) -> ResNet18-ECA backbone over the
     ``future_frames * num_classes`` mask channels -> ``tanh`` action head; ``punet_inter`` feeds the PU-Net bottleneck
     vector instead of a backbone.  Loads ``params.punet_path`` (key ``"model"``) exactly like the reference."""
+    input_grads = False       # (INTEGRATION.md, limits: no gradient reaches the inputs of the PU-Net types)
 
     def __init__(self, params):
         super().__init__()
@@ -253,6 +264,7 @@ class PMoE(nn.Module):
         # SWA checkpoints carry extra keys, therefore strict=False (moe.py:336-337)
         self.moe.load_state_dict(torch.load(params.pmoe.moe_dir, map_location="cpu"), strict=False)
         self.moe = freeze(self.moe, params.exclude_freeze, params.verbose)
+        self.moe.input_grads = False      # (its actions are sampled: no gradient passes them, so nothing is taped for one)
         self.punet = PUNetExpert(params)
         if params.pmoe.punet_dir:
             self.punet.load_state_dict(torch.load(params.pmoe.punet_dir, map_location="cpu"), strict=False)

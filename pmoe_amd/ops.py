@@ -536,6 +536,40 @@ def eca_bwd_apply(dy, gate, dgap, dx):
                                     stream_ptr()), "pmoe_eca_bwd_apply")
 
 
+def stem_input_grad(dz1, wd, dgap, dx, E):
+    """d loss / d images through the stem's gate and first convolution, summed over the E experts that share the frames:
+    dz1 [E*B,H,W,64] (compute dtype), wd [E*B,cinp2,9,coutp2] the data-gradient operand of pack_conv_weights_gated, dgap f32
+    [E*B,16] (already divided by H*W) or None -> dx f32 [B,creal,H,W], written whole."""
+    n, h, w_, ld = _nhwc(dz1, "dz1")
+    if dx.dim() != 4 or E < 1 or n % E:
+        raise ValueError(f"stem_input_grad: dx must be [B,C,H,W] and dz1 hold E*B images, got {tuple(dx.shape)} / {n} for E={E}")
+    b, creal = n // E, dx.shape[1]
+    if ld != 64 or tuple(dx.shape) != (b, creal, h, w_) or not 1 <= creal <= 16:
+        raise ValueError(f"stem_input_grad: dz1 [E*B,H,W,64] and dx [B,<=16,H,W] expected, got {tuple(dz1.shape)} / {tuple(dx.shape)}")
+    if wd.dim() != 4 or wd.shape[0] != n or wd.shape[1] < 16 or wd.shape[2] != 9 or wd.shape[3] < 64 or wd.shape[3] % 8:
+        raise ValueError(f"stem_input_grad: wd must be [{n},>=16,9,>=64], got {tuple(wd.shape)}")
+    if dgap is not None and tuple(dgap.shape) != (n, 16):
+        raise ValueError(f"stem_input_grad: dgap must be [{n},16], got {tuple(dgap.shape)}")
+    check(load().pmoe_stem_input_grad(ptr(dz1, "dz1"), ptr(wd, "wd", dz1.dtype), ptr(dgap, "dgap", torch.float32),
+                                      ptr(dx, "dx", torch.float32), E, b, h, w_, creal, wd.shape[1], wd.shape[3], dt(dz1),
+                                      stream_ptr()), "pmoe_stem_input_grad")
+
+
+def shared_linear_input_grad(dh, w, dx, E, cout, dh_coff=0):
+    """d loss / d (an input row shared by the E experts) through a Linear: dh [E*B,...,dh_ld] the gradient of the layer's
+    pre-activation output (window [dh_coff, dh_coff + cout)), w [E,coutp,1,cinp] its forward pack -> dx f32 [B,cin]."""
+    dh_ld = dh.shape[-1]
+    rows = dh.numel() // dh_ld
+    if dx.dim() != 2 or E < 1 or rows != E * dx.shape[0]:
+        raise ValueError(f"shared_linear_input_grad: dx [B,cin] and dh with E*B rows expected, got {tuple(dx.shape)} / {rows} for E={E}")
+    if w.dim() != 4 or w.shape[0] != E or w.shape[2] != 1 or w.shape[1] < cout or w.shape[3] < dx.shape[1] or dh_coff < 0 or \
+            dh_coff + cout > dh_ld:
+        raise ValueError(f"shared_linear_input_grad: w must be [{E},>={cout},1,>={dx.shape[1]}], got {tuple(w.shape)}")
+    check(load().pmoe_shared_linear_input_grad(ptr(dh, "dh"), dh_ld, dh_coff, ptr(w, "w", dh.dtype), ptr(dx, "dx", torch.float32),
+                                               E, dx.shape[0], cout, w.shape[1], w.shape[3], dx.shape[1], dt(dh), stream_ptr()),
+          "pmoe_shared_linear_input_grad")
+
+
 def nchw_to_nhwc(src, dst):
     b, c, h, w_ = src.shape
     check(load().pmoe_nchw_to_nhwc(ptr(src, "src", torch.float32), ptr(dst, "dst"), b, c, h, w_, dst.shape[-1], dt(dst),
@@ -631,7 +665,7 @@ for _n in ("stem_tail_stats", "stem_tail_pool", "stem_tail_bwd", "stem_tail_pool
            "reduce_partials", "bn_finalize", "bn_apply", "bn_apply_gap", "bn_bwd_reduce", "bn_bwd_finalize", "bn_bwd_apply",
            "maxpool_fwd", "maxpool_bwd", "gap_partial", "gap_finish", "gap_bwd", "eca_gate", "eca_scale",
            "eca_bwd_small", "eca_bwd_apply", "eca_stem_fold", "nchw_to_nhwc", "pad_rows", "gate_mixture_fwd", "gate_mixture_bwd",
-           "moe_loss"):
+           "moe_loss", "stem_input_grad", "shared_linear_input_grad"):
     globals()[_n] = _timed(globals()[_n])
 _conv2d_launch = _timed(_conv2d_launch, "conv2d")        # every conv2d launch, however prepared: the records' op name stays "conv2d"
 
