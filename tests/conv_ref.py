@@ -21,8 +21,18 @@ Three kinds of input (tests/test_conv_cpu.py checks on the CPU what the GPU test
            2^24) but the pre-activations spread over (-8, 8), where ELU, tanh and sigmoid are not saturated.  What is left to a
            kernel there is the device library's expm1f / tanhf / expf and the float32 operations behind them: mlp_epilogue
            returns that allowance next to the value, and zero wherever the value is a float32 product or nothing.
+  select   the cases with e4m3 operands (flags f8 / a8), next to lattice and unit: every output channel has ONE non-zero weight,
+           +-2^j at a random (tap, input channel), so an output element is +-2^j times the CONVERTED input at the shifted pixel
+           (0 where the tap falls into the padding) -- one product, exact in bfloat16 in any order.  The inputs hold every e4m3
+           value, every exact tie with its bfloat16 neighbours, values that underflow and values that saturate (select_values).
 Continuous data stays in tests/test_ops_gpu.py for the K-long float32 SUMS only: a worst-case float32 bound over K = 4608 terms
 is looser than bfloat16 rounding.
+
+e4m3 operands (include/pmoe_hip.h, pmoe_conv_desc.w_fp8 / in_fp8; the policy: oracle/fp8_policy.py).  A launch with e4m3 weights
+computes conv(qdq_act(x), qdq_weight(w)): products of two e4m3 factors are exact in float32 and every scale is a power of two, so
+the accumulator is as exact as the bfloat16 one.  Integers up to 15 have four significant bits and a row of them scales to at most
+448: the lattice and unit generators are FIXED POINTS of both quantisers (tests/test_conv_cpu.py asserts it), the reference of
+such a launch is the reference itself, and an e4m3 kernel must store it bit for bit.
 """
 import collections
 import functools
@@ -30,6 +40,7 @@ import functools
 import torch
 import torch.nn.functional as F
 
+from oracle import fp8_policy as P
 from tests import bn_ref
 from tests import eca_head_ref as H
 from tests.stem_tail_ref import BF16, F32, F64, round_to
@@ -39,6 +50,10 @@ RES_NONE, RES_ADD, RES_DRELU, RES_DELU, RES_DTANH, RES_DSIGMOID, RES_DBN, RES_IN
 ACT_NONE, ACT_RELU, ACT_ELU, ACT_TANH, ACT_SIGMOID = range(5)
 KINDS = ("lattice", "unit")
 DYADIC = "dyadic"                    # the one kind of the cases that ask for an MLP epilogue form (kinds_of)
+SELECT = "select"                    # the third kind of the cases with e4m3 operands (kinds_of)
+F8_FLAGS = {"f8", "a8"}              # e4m3 weights with bfloat16 input | e4m3 weights and e4m3 input bytes
+IN_SCALE = P.IN_SCALE                # 16, the policy's; SCALE_FLAGS: the case that runs under another power of two
+SCALE_FLAGS = {"sc32": 32.0}
 DROP_P = 0.3
 ACT_FLAGS = {"elu": ACT_ELU, "tanh": ACT_TANH, "sigmoid": ACT_SIGMOID}
 DMODE_FLAGS = {"delu": RES_DELU, "dtanh": RES_DTANH, "dsigmoid": RES_DSIGMOID}
@@ -76,9 +91,16 @@ _RES = Order("staged", None, "conv_res.hip: `(bf16)acc` into the staging region,
 _DMA = Order("staged", "once", "conv_dma_epilogue.inc: fast_epi (add_fast under DMA_ZPRE) stages bf16; bias / act take the two-phase f32 path")
 _DMA2P = Order("once", "once", "conv_dma_epilogue.inc: no DMA_ZPRE in conv3x3s2_dma_kernel, RES_ADD takes the two-phase f32 path")
 _NOADD = Order(None, None, "takes no side input")
+# e4m3 operands on the generic tile: the same tail, `v[i] *= osc[i]` (a power of two: exact), then bias, then the residual, all in
+# float32 (conv_igemm.hip:327-338).  8507 (conv_dma.hip conv_dma_f8_plan: res_mode != PMOE_RES_NONE is refused) takes no side
+# input; its one-phase read-out applies the power-of-two out_scale to the bfloat16-staged accumulator, which is the rounding of the
+# scaled accumulator (conv_dma_epilogue.inc:69-73).
+_TILE8 = Order("once", "once", "conv_igemm.hip:327-338: `v[i] *= osc[i]`, `v[i] += bias[i]`, `v[i] += rv[i]` in f32 before pack16<T>")
 ROUNDING = {
-    **{c: _TILE for c in (522, 541, 542, 622, 641, 642, 722, 741, 2007)},                       # conv_igemm_kernel / _lite_kernel
-    **{4000 + c: _TILE for c in (522, 541, 542, 622, 641, 642, 722, 741, 2007)},                # ... as parity-class launches
+    **{c: _TILE for c in (522, 541, 542, 622, 641, 642, 722, 741, 742, 2007)},                  # conv_igemm_kernel / _lite_kernel
+    **{4000 + c: _TILE for c in (522, 541, 542, 622, 641, 642, 722, 741, 742, 2007)},           # ... as parity-class launches
+    **{8000 + c: _TILE8 for c in (622, 641, 642, 722, 741, 742, 2007)},                         # ... with e4m3 operands (64 | 128-channel chunks)
+    8507: _NOADD,                                                                               # conv3x3_dma_f8_kernel
     3000: _TILE,                                        # gemm_skinny_kernel<4>: its four f32 partial tiles and the bias meet in registers, the same tail
     1005: _RES, 1007: _RES,                                                                     # conv3x3_res_kernel
     1107: _RES, 1117: _NOADD,                                                                   # conv3x3_resdma_kernel
@@ -109,7 +131,11 @@ def rounding_of(code, res_mode, bias, act):
 # the stand-alone passes).  T = the tiles one workgroup walks = ceil(tiles per expert / rows per expert).
 #   conv_igemm.hip:312,370,393,411   one row per 256 | 128-pixel tile: BMH / PROWS <= 16 read-outs per thread, <= 3 xor-shuffles,
 #                                    <= 8 waves through LDS                                                  L = 16 + 3 + 8
+#                                    (the same body with e4m3 operands, 8000 + code: the statistics read the packed bfloat16
+#                                    back, conv_igemm.hip:364-370; <4, 2> = 742 | 8742: 256 / 32 = 8 read-outs, 2 shuffles)
 #   conv_dma_epilogue.inc:189,257,274 one row per tile: BM / PROWS = 8 (4: 64-cout tiles), 2 (3) shuffles, 8 waves    L = 8 + 3 + 8
+#                                    (8507, conv3x3_dma_f8_kernel, includes it under DMA_OSCALE, conv_dma.hip:1173-1175:
+#                                    BM / PROWS = 256 / 32 = 8 read-outs, shuffles over 16 and 32 lanes, 8 waves)
 #   conv_res.hip:214,242,261          conv3x3_res_kernel: 8 per tile, 3 shuffles, 8 waves                     L = 8 T + 11
 #   conv_res.hip:506,541,568          conv3x3_resdma_kernel: 4 per tile                                       L = 4 T + 11
 #   conv_res.hip:825,841,983,997      conv3x3_respipe_kernel: 2 per tile, 5 shuffles, 4 waves                 L = 2 T + 9
@@ -127,7 +153,7 @@ def chain_stats(code, tiles_per_expert, rows_per_expert):
         return 4 * bn_ref.cdiv(T, 4) + 32
     if 1400 <= code < 1500:
         return 8 * bn_ref.cdiv(T, 4) + 32
-    if 5000 <= code < 6000:
+    if 5000 <= code < 6000 or code == 8507:
         return 19
     return 27
 
@@ -465,6 +491,8 @@ def wgrad(x, dy, *, cin, cout, cinp, coutp, ipe, ks, stride, pad, dtype, x_share
 #       ipe = 1 under BatchNorm sets of ipe images, the ECA-gated stem)     -- stride 2: the zero-dilated form (`dilate`)
 #   w:  pimg (per_image) | bn (bn_fused) | shared (x_shared)
 #   win (any launch): input, output and residual are channel windows of wider rows, NaN outside
+#   f:  f8 (e4m3 weight bytes with their out_scale, bfloat16 input converted by the loader) | a8 (e4m3 input bytes too: 0x7f, the
+#       e4m3 NaN, outside the window), under in_scale 16 or sc32 (in_scale 32); such a case also runs on the select kind
 #   the MLP forms (MLP_FLAGS; a case that names one runs on the dyadic kind alone):
 #   f:  elu | tanh | sigmoid, drop | dropL | dropE (drop_p = 0.3 under seed 5 | a seed above 2^32 | edge_seed: one element's
 #       hash EQUALS p)        d:  delu | dtanh | dsigmoid (and drelu), + drop: the saved output was dropped out under that seed
@@ -746,16 +774,78 @@ CASES = [
     _case(1, 3, 128, 64, 40, 36, 3, 1, BF16, "f: d:delu+drop w:", (None, 5007, None)),
     _case(1, 3, 128, 64, 40, 36, 3, 1, BF16, "f: d:dtanh+win w:", (None, 5007, None)),
     _case(1, 3, 128, 64, 40, 36, 3, 1, BF16, "f: d:dsigmoid+dropL w:", (None, 5007, None)),
+    # ---- conv_igemm_kernel<T, 7, 4, 2> (742): >= 4096 pixels per expert on maps so small that the halo patch of a 256-pixel tile
+    #      (16 images of 6 x 6 pixels) no longer fits twice on a CU, so the LITE tile declines -- a 4 x 4 last stage at 256 images
+    #      per expert; one and two channel chunks (the second: chunk prefetch), and as a parity class of a stride-2 data gradient
+    _case(1, 256, 64, 128, 4, 4, 3, 1, BF16, "f:stats+win d: w:", (742, None, None)),
+    _case(1, 256, 64, 128, 4, 4, 3, 1, BF16, "f:bias+relu+add d: w:", (742, None, None)),
+    _case(2, 256, 64, 128, 4, 4, 3, 1, BF16, "f:shared+stats d: w:", (742, None, None)),
+    _case(1, 256, 128, 128, 4, 4, 3, 1, BF16, "f:drelu+stats d: w:", (742, None, None)),
+    _case(1, 256, 128, 64, 4, 4, 3, 1, BF16, "f: d:addin+win w:", (None, 742, None)),
+    _case(1, 256, 128, 64, 8, 8, 3, 2, BF16, "f: d:add+win w:", (None, 4742, None)),
+    _case(1, 256, 128, 64, 8, 8, 3, 2, BF16, "f: d:addin w:", (None, 4742, None)),
+    _case(1, 256, 128, 64, 8, 8, 3, 2, BF16, "f: d:bias w:", (None, 4742, None)),
+    _case(1, 256, 128, 64, 8, 8, 3, 2, BF16, "f: d:drelu w:", (None, 4742, None)),
+    # ---- float32 522 and 541 as PLAIN launches (8-channel reductions; the rows above reach them as parity classes only)
+    _case(2, 2, 8, 128, 7, 7, 3, 1, F32, "f:stats+win d: w:", (522, None, None)),
+    _case(2, 2, 8, 128, 7, 7, 3, 1, F32, "f:bias+relu+add d: w:", (522, None, None)),
+    _case(2, 2, 8, 128, 7, 7, 3, 1, F32, "f:drelu+shared+stats d: w:", (522, None, None)),
+    _case(2, 2, 8, 16, 7, 7, 3, 1, F32, "f:stats+win d: w:", (541, None, None)),
+    _case(2, 2, 8, 16, 7, 7, 3, 1, F32, "f:bias+relu+add d: w:", (541, None, None)),
+    _case(2, 2, 8, 16, 7, 7, 3, 1, F32, "f:drelu+shared+stats d: w:", (541, None, None)),
+    #      ... and as data gradients of layers with 8 outputs, accumulated in place; the float32 forms of their parity classes
+    _case(2, 2, 128, 8, 7, 7, 3, 1, F32, "f: d:addin w:", (None, 522, None)),
+    _case(2, 2, 16, 8, 7, 7, 3, 1, F32, "f: d:addin+win w:", (None, 541, None)),
+    _case(1, 2, 128, 8, 9, 7, 3, 2, F32, "f: d:add w:", (None, 4522, None)),
+    _case(1, 2, 128, 8, 9, 7, 3, 2, F32, "f: d:bias w:", (None, 4522, None)),
+    _case(1, 2, 128, 8, 9, 7, 3, 2, F32, "f: d:drelu w:", (None, 4522, None)),
+    _case(1, 2, 16, 8, 9, 7, 3, 2, F32, "f: d:addin w:", (None, 4541, None)),
+    _case(1, 2, 16, 8, 9, 7, 3, 2, F32, "f: d:bias w:", (None, 4541, None)),
+    _case(1, 2, 16, 8, 9, 7, 3, 2, F32, "f: d:drelu w:", (None, 4541, None)),
+    # ---- e4m3 weights, bfloat16 input converted by the patch loader (conv_igemm_body<bf16, ..., fp8>): 8000 + the tile code, in
+    #      64- and 128-channel chunks.  Per code: statistics on channel windows; bias + ReLU + side input; the ReLU' mask on a
+    #      shared input.  Each also on the select kind: every converting loader, chunk width and tap meets every e4m3 value, tie
+    #      and overflow.  One case under in_scale 32.
+    _case(2, 3, 64, 48, 9, 7, 3, 2, BF16, "f:f8+stats+win d: w:", (8641, None, None)),
+    _case(2, 3, 64, 48, 9, 7, 3, 2, BF16, "f:f8+bias+relu+add d: w:", (8641, None, None)),
+    _case(2, 3, 64, 48, 9, 7, 3, 2, BF16, "f:f8+drelu+shared+stats d: w:", (8641, None, None)),
+    _case(1, 3, 128, 64, 7, 7, 3, 1, BF16, "f:f8+sc32+stats+win d: w:", (8741, None, None)),
+    _case(1, 3, 128, 64, 7, 7, 3, 1, BF16, "f:f8+bias+relu+add d: w:", (8741, None, None)),
+    _case(2, 3, 128, 64, 7, 7, 3, 1, BF16, "f:f8+drelu+shared+stats d: w:", (8741, None, None)),
+    _case(2, 1, 64, 128, 8, 8, 3, 1, BF16, "f:f8+stats+win d: w:", (8622, None, None)),
+    _case(2, 1, 64, 128, 8, 8, 3, 1, BF16, "f:f8+bias+relu+add d: w:", (8622, None, None)),
+    _case(2, 1, 64, 128, 8, 8, 3, 1, BF16, "f:f8+drelu+shared+stats d: w:", (8622, None, None)),
+    _case(1, 2, 128, 128, 9, 9, 3, 2, BF16, "f:f8+stats+win d: w:", (8722, None, None)),
+    _case(1, 2, 128, 128, 9, 9, 3, 2, BF16, "f:f8+bias+relu+add d: w:", (8722, None, None)),
+    _case(2, 2, 128, 128, 9, 9, 3, 2, BF16, "f:f8+drelu+shared+stats d: w:", (8722, None, None)),
+    _case(1, 1, 64, 128, 64, 66, 1, 1, BF16, "f:f8+stats+win d: w:", (8642, None, None)),
+    _case(1, 1, 64, 128, 128, 130, 3, 2, BF16, "f:f8+bias+relu+add d: w:", (8642, None, None)),
+    _case(2, 1, 64, 128, 64, 66, 1, 1, BF16, "f:f8+drelu+shared+stats d: w:", (8642, None, None)),
+    _case(1, 1, 128, 128, 64, 66, 1, 1, BF16, "f:f8+stats+win d: w:", (10007, None, None)),
+    _case(1, 3, 128, 128, 40, 36, 3, 1, BF16, "f:f8+bias+relu+add d: w:", (10007, None, None)),
+    _case(2, 1, 128, 128, 64, 66, 1, 1, BF16, "f:f8+drelu+shared+stats d: w:", (10007, None, None)),
+    _case(1, 256, 128, 128, 4, 4, 3, 1, BF16, "f:f8+stats+win d: w:", (8742, None, None)),
+    _case(1, 256, 128, 128, 4, 4, 3, 1, BF16, "f:f8+bias+relu+add d: w:", (8742, None, None)),
+    _case(2, 256, 128, 72, 4, 4, 3, 1, BF16, "f:f8+drelu+shared+stats d: w:", (8742, None, None)),
+    #      ... accumulated in place (res == out)
+    _case(2, 3, 64, 48, 9, 7, 3, 2, BF16, "f:f8+addin d: w:", (8641, None, None)),
+    _case(1, 3, 128, 64, 7, 7, 3, 1, BF16, "f:f8+addin+win d: w:", (8741, None, None)),
+    _case(2, 1, 64, 128, 8, 8, 3, 1, BF16, "f:f8+addin d: w:", (8622, None, None)),
+    _case(1, 2, 128, 128, 9, 9, 3, 2, BF16, "f:f8+addin+stats d: w:", (8722, None, None)),
+    _case(1, 1, 64, 128, 64, 66, 1, 1, BF16, "f:f8+addin d: w:", (8642, None, None)),
+    _case(1, 1, 128, 128, 64, 66, 1, 1, BF16, "f:f8+addin d: w:", (10007, None, None)),
+    _case(1, 256, 128, 72, 4, 4, 3, 1, BF16, "f:f8+addin+win d: w:", (8742, None, None)),
+    # ---- e4m3 weights AND e4m3 input bytes on the block-scaled MFMA (conv3x3_dma_f8_kernel, 8507; it takes no side input): one and
+    #      two 128-channel chunks, image groups of 16 x 16 maps, a ragged last channel vector block (120), channel windows on both
+    #      sides (in_ld > cin: the 0x7f bytes beside the window are NaN).  On the select kind: all 254 non-NaN byte codes, which
+    #      proves the byte decoding and the lane-half split of the instruction's operands
+    _case(1, 3, 128, 128, 40, 36, 3, 1, BF16, "f:a8+stats d: w:", (8507, None, None)),
+    _case(1, 17, 128, 128, 16, 16, 3, 1, BF16, "f:a8+bias+relu+stats+win d: w:", (8507, None, None)),
+    _case(1, 3, 256, 128, 40, 36, 3, 1, BF16, "f:a8 d: w:", (8507, None, None)),
+    _case(1, 3, 128, 120, 40, 36, 3, 1, BF16, "f:a8+bias+win d: w:", (8507, None, None)),
 ]
-# plan codes the coverage rules of tests/test_conv_cpu.py do not ask a case for, and why
-EXCLUDED = {
-    8000: "e4m3 operands (8000 + a generic-tile code, 8507): tests/test_fp8_gpu.py",
-}
-TILE_CODES = (522, 541, 542, 622, 641, 642, 722, 741, 2007)
-
-
-def is_excluded(code):
-    return code == 8507 or code - 8000 in TILE_CODES
+TILE_CODES = (522, 541, 542, 622, 641, 642, 722, 741, 742, 2007)
+TILE_CODES_F8 = tuple(8000 + c for c in (622, 641, 642, 722, 741, 742, 2007))      # (e4m3 operands: 64- and 128-channel chunks only)
 
 
 # The three copies of the MLP epilogue (mlp_epilogue), by plan code.  A code that is not here belongs to a kernel whose planner
@@ -764,17 +854,24 @@ def is_excluded(code):
 # code ever answers a descriptor with one of the forms, and that every (copy, dtype, form) the grid reaches has a case.  The
 # LDS-DMA kernels do take them -- a 3x3 layer of >= 4096 pixels per expert with an activation or dropout runs on
 # conv_dma_epilogue.inc's two-phase read-out (5007 | 5017 | 5207; the parity-class launches 9207 take the forward forms only).
+# The kernels with e4m3 operands run the same two copies (8000 + a tile code: conv_igemm_body; 8507: conv_dma_epilogue.inc under
+# DMA_OSCALE) and their planners accept the forms, but no case runs an MLP form on e4m3 operands: the dyadic inputs are not
+# e4m3-exact, and the code is the copy the bfloat16 cases run.
 EPILOGUE_COPY = {
     3000: "gemm_skinny.hip",
     **{c: "conv_igemm.hip" for c in TILE_CODES}, **{4000 + c: "conv_igemm.hip" for c in TILE_CODES},
-    **{c: "conv_dma_epilogue.inc" for c in (5007, 5017, 5207, 9207)},
+    **{c: "conv_igemm.hip" for c in TILE_CODES_F8},
+    **{c: "conv_dma_epilogue.inc" for c in (5007, 5017, 5207, 9207, 8507)},
 }
 
 
 def kinds_of(case):
-    """the kinds a case runs on: the MLP forms on the dyadic kind, everything else on the lattice and unit kinds"""
+    """the kinds a case runs on: the MLP forms on the dyadic kind, everything else on the lattice and unit kinds -- and a case
+    with e4m3 operands on the select kind too"""
     fl = flags(case)
-    return (DYADIC,) if any(fl[k] and fl[k] & MLP_FLAGS for k in "fd") else KINDS
+    if any(fl[k] and fl[k] & MLP_FLAGS for k in "fd"):
+        return (DYADIC,)
+    return KINDS + (SELECT,) if fl["f"] and fl["f"] & F8_FLAGS else KINDS
 
 
 def case_id(case):
@@ -942,6 +1039,100 @@ def _dyadic_launches(case):
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------------------------------
+# e4m3 operands
+
+def qdq_act(x, in_scale=IN_SCALE):
+    """the policy's activation quantiser on float64 values (NaN, the outside of a channel window, stays NaN)"""
+    return P.qdq_act(x.to(F32), in_scale).to(F64)
+
+
+def qdq_weight(w):
+    """the policy's weight quantiser, expert by expert: w [E, cout, cin, ks, ks]"""
+    return torch.stack([P.qdq_weight(we.to(F32)) for we in w]).to(F64)
+
+
+def operands(L):
+    """(inp, w) as the kernel's arithmetic sees them: the launch's own, or -- e4m3 operands -- what the two quantisers of
+    oracle/fp8_policy.py make of them"""
+    if not L.get("f8"):
+        return L["inp"], L["w"]
+    return qdq_act(L["inp"], L["in_scale"]), qdq_weight(L["w"])
+
+
+def e4m3_operands(L, coutp):
+    """the operands of an e4m3 launch from the reference's own statement: weight bytes [E, coutp, taps, cin] =
+    e4m3(w / row_scale) with zero pad rows, out_scale [E, coutp] = row_scale / in_scale with NaN in [cout, coutp) (the kernels
+    must not read it) and -- a8 -- the input bytes e4m3(x * in_scale) with 0x7f, the e4m3 NaN, outside the channel window
+    (None: the input stays bfloat16)"""
+    kw, w, s_in = L["kw"], L["w"], L["in_scale"]
+    E, cout, cin, ks, _ = w.shape
+    wb = torch.zeros(E, coutp, ks * ks, cin, dtype=torch.uint8)
+    osc = torch.full((E, coutp), float("nan"), dtype=F32)
+    for e in range(E):
+        rs = P.row_scale(w[e].to(F32))
+        wb[e, :cout] = P.e4m3_bytes((w[e].to(F32) / rs.view(-1, 1, 1, 1))).reshape(cout, cin, ks * ks).permute(0, 2, 1)
+        osc[e, :cout] = rs / s_in
+    xb = None
+    if L["a8"]:
+        c0 = kw["in_coff"]
+        xb = torch.full(L["inp"].shape, 0x7f, dtype=torch.uint8)
+        xb[..., c0:c0 + cin] = P.e4m3_bytes(L["inp"][..., c0:c0 + cin].to(F32) * s_in)
+    return wb, osc, xb
+
+
+def e4m3_values():
+    """the 127 non-negative finite e4m3 values, ascending: byte codes 0x00 .. 0x7e (seven subnormals k 2^-9, then 2^e (1 + m / 8)
+    up to 448)"""
+    return torch.arange(127, dtype=torch.uint8).view(torch.float8_e4m3fn).to(F64)
+
+
+def bf16_neighbour(t, d):
+    """the bfloat16 value d steps above (d > 0) or below a positive bfloat16 value"""
+    return (t.to(BF16).view(torch.int16) + d).view(BF16).to(F64)
+
+
+def select_values(a8):
+    """the inputs of the select kind TIMES in_scale, every one exact in bfloat16.  a8: the 254 non-NaN byte codes.  bfloat16 input
+    (the converting loaders): both signs of
+      every e4m3 value, the seven subnormals and the zero (so -0 too) among them;
+      every exact tie -- the midpoint of two neighbouring e4m3 values, normal and subnormal, 2^-10 between 0 and the smallest
+      subnormal among them -- and its two bfloat16 neighbours;
+      values below half the smallest subnormal (they convert to zero);
+      values beyond 448 up to 1e4 x 16 (they saturate to 448; 464, halfway to the 480 that e4m3fn does not have, among them)"""
+    if a8:
+        return torch.cat([torch.arange(0, 127), torch.arange(128, 255)]).to(torch.uint8).view(torch.float8_e4m3fn).to(F64)
+    v = e4m3_values()
+    ties = (v[:-1] + v[1:]) / 2
+    small = torch.tensor([2.0 ** -11, 2.0 ** -14, 2.0 ** -20, 3 * 2.0 ** -12], dtype=F64)
+    big = round_to(torch.tensor([450.0, 464.0, 466.0, 480.0, 512.0, 1000.0, 65536.0, 1e4 * 16], dtype=F64), BF16)
+    pos = torch.cat([v, ties, bf16_neighbour(ties, 1), bf16_neighbour(ties, -1), small, big])
+    return torch.cat([pos, -pos])
+
+
+def _select_input(g, shape, a8, in_scale):
+    """select_values / in_scale, each value as often as any other, in random order"""
+    vals = select_values(a8) / in_scale
+    n = 1
+    for d in shape:
+        n *= d
+    assert n >= len(vals), (shape, len(vals))
+    return vals[torch.arange(n) % len(vals)][torch.randperm(n, generator=g)].reshape(shape)
+
+
+def _select_weights(g, E, cout, cin, ks):
+    """one non-zero per output channel: +-2^j, j in -2 .. 2, at a random input channel; the taps in turn from a random first one,
+    so that every tap is some channel's.  Channel 0 of every expert takes the LAST input channel at the left tap of the middle
+    filter row: the element the kslice and tapshift mutants get wrong"""
+    w = torch.zeros(E, cout, cin * ks * ks, dtype=F64)
+    tap = (torch.arange(cout) + torch.randint(0, ks * ks, (E, 1), generator=g)) % (ks * ks)
+    at = torch.randint(0, cin, (E, cout), generator=g) * (ks * ks) + tap
+    at[:, 0] = (cin - 1) * ks * ks + (ks // 2) * ks
+    val = torch.ldexp(torch.ones(E, cout, dtype=F64), torch.randint(-2, 3, (E, cout), generator=g)) * (2 * torch.randint(0, 2, (E, cout), generator=g) - 1)
+    w.scatter_(2, at[..., None], val[..., None])
+    return w.reshape(E, cout, cin, ks, ks)
+
+
 @functools.lru_cache(maxsize=4)
 def launches(case, kind):
     """{"f" | "d" | "w": launch}: the tensors (float64 values representable in the case's storage type) and keywords of the three
@@ -953,6 +1144,10 @@ def launches(case, kind):
         return _dyadic_launches(case)
     E, ipe, cin, cout, H, W, ks, stride, dtype = case[:9]
     fl = flags(case)
+    # the select kind: its own weights and input; bias and side input small integers (every float32 sum of the tail stays exact)
+    sel = kind == SELECT
+    side = "lattice" if sel else kind
+    assert not sel or (fl["d"] is None and fl["w"] is None), "a case with e4m3 operands is a forward launch alone"
     g = torch.Generator().manual_seed(sum(ord(ch) * (i + 1) for i, ch in enumerate(case_id(case) + kind)))
     N, pad = E * ipe, ks // 2
     Ho, Wo = out_size(H, ks, stride, pad), out_size(W, ks, stride, pad)
@@ -964,17 +1159,25 @@ def launches(case, kind):
     if f is not None:
         shared, win = "shared" in f, "win" in f
         nin = ipe if shared else N
-        w = _ints(g, (E, cout, cin, ks, ks), Rf, kind)
-        L = {"w": w, "bias": None, "res": None, "bn_coef": None, "res_is_out": False}
+        f8, a8 = bool(f & F8_FLAGS), "a8" in f
+        in_scale = next((v for n, v in SCALE_FLAGS.items() if n in f), IN_SCALE)
+        assert f8 or (not sel and not f & set(SCALE_FLAGS)), case
+        w = _select_weights(g, E, cout, cin, ks) if sel else _ints(g, (E, cout, cin, ks, ks), Rf, kind)
+        L = {"w": w, "bias": None, "res": None, "bn_coef": None, "res_is_out": False, "f8": f8, "a8": a8, "in_scale": in_scale}
         kw = dict(cin=cin, cout=cout, ipe=ipe, ks=ks, stride=stride, pad=pad, dtype=dtype, in_shared=shared)
+        Rs = 3 if sel else Rf
         if "inbn" in f:
             coef = bn_coefficients(g, E, cin, kind)
             x = planted_z(g, (nin, H, W, cin), coef, ipe, kind)
             L["bn_coef"] = coef
             kw.update(res_mode=RES_INBN, bn_ipe=ipe)
+        elif sel:
+            x = _select_input(g, (nin, H, W, cin), a8, in_scale)
         else:
             x = _ints(g, (nin, H, W, cin), Rf, kind)
-        if "relu" in f:
+        if "relu" in f and sel:
+            kw["act"] = ACT_RELU
+        elif "relu" in f:
             # one pixel of image 0 sees a single non-zero input element: with bias[c] = -w[c, 0, centre] + {0, 1, -1} its
             # pre-activations are exactly on the ReLU edge and one step either side, channel by channel
             py, px = min(2, H - 1), min(2, W - 1)
@@ -982,8 +1185,8 @@ def launches(case, kind):
             x[0, py, px, 0] = 1
             kw["act"] = ACT_RELU
         if "bias" in f:
-            b = _ints(g, (E, cout), max(Rf, 3), kind)
-            if "relu" in f:
+            b = _ints(g, (E, cout), max(Rs, 3), side)
+            if "relu" in f and not sel:
                 b[0] = -w[0, :, 0, ks // 2, ks // 2] + (torch.arange(cout) % 3 - 1).to(F64)
             L["bias"] = b
         L["inp"], kw["in_coff"] = _window(x, win)
@@ -994,12 +1197,12 @@ def launches(case, kind):
         else:
             L["out_init"], kw["out_coff"] = _out_buffer((N, Ho, Wo), cout, win)
         if "addin" in f:
-            prev = _ints(g, (N, Ho, Wo, cout), 8 * max(Rf, 2), kind)
+            prev = _ints(g, (N, Ho, Wo, cout), 8 * max(Rs, 2), side)
             L["out_init"][..., kw["out_coff"]:kw["out_coff"] + cout] = prev
             kw.update(res_mode=RES_ADD, res_coff=kw["out_coff"])
             L["res_is_out"] = True
         if "add" in f:
-            res = _ints(g, (N, Ho, Wo, cout), 8 * max(Rf, 2), kind)
+            res = _ints(g, (N, Ho, Wo, cout), 8 * max(Rs, 2), side)
             if "relu" in f:
                 res[0, min(2, H - 1) // stride, min(2, W - 1) // stride] = 0          # the planted pixel stays on the ReLU edge
             L["res"], kw["res_coff"] = _window(res, win, 48, 32)
@@ -1077,7 +1280,8 @@ def launches(case, kind):
 def conv_reference(L, rounding="once", mut=""):
     """conv2d of a launch of ``launches``"""
     res = L["out_init"] if L["res_is_out"] else L["res"]
-    return conv2d(L["inp"], L["w"], L["out_init"], bias=L["bias"], res=res, bn_coef=L["bn_coef"], rounding=rounding, mut=mut, **L["kw"])
+    inp, w = operands(L)
+    return conv2d(inp, w, L["out_init"], bias=L["bias"], res=res, bn_coef=L["bn_coef"], rounding=rounding, mut=mut, **L["kw"])
 
 
 def stored_interval(ref, dtype):
@@ -1096,14 +1300,15 @@ def wgrad_reference(L, evaluate=F64):
 def abs_bound(L):
     """max over the output elements of sum |x||w| (+ |bias| + |res|): below 2^24 every float32 partial sum is exact"""
     kw = L["kw"]
-    xw = L["inp"][..., kw["in_coff"]:kw["in_coff"] + kw["cin"]]
+    inp, w = operands(L)
+    xw = inp[..., kw["in_coff"]:kw["in_coff"] + kw["cin"]]
     if kw.get("res_mode") == RES_INBN:
         c = L["bn_coef"]
         xw = bn_ref.bn_apply(xw, None, c[2], c[3], c[0], c.shape[1], True, kw["dtype"])["y"]
     ho, wo = L["out_init"].shape[1:3]
     if kw.get("shuffle_c"):
         ho, wo = ho // 2, wo // 2
-    a = conv_acc(xw.abs(), L["w"].abs(), ipe=kw["ipe"], in_shared=kw.get("in_shared", False), stride=kw["stride"], pad=kw["pad"],
+    a = conv_acc(xw.abs(), w.abs(), ipe=kw["ipe"], in_shared=kw.get("in_shared", False), stride=kw["stride"], pad=kw["pad"],
                  ho=ho, wo=wo, dilate=kw.get("dilate", False))
     if L["bias"] is not None:
         a = a + L["bias"].abs().repeat_interleave(kw["ipe"], 0)[:, None, None, :]

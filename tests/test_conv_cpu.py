@@ -1,11 +1,12 @@
 """The float64 convolution reference (tests/conv_ref.py) checked against float64 torch.autograd of F.conv2d / F.conv_transpose2d /
 F.batch_norm, its input generators checked for everything tests/test_conv_gpu.py assumes of them, and the case table checked
 against the planners: every case plans to the codes it names, and every code the planners can answer over a grid of shapes,
-requests and switches is in the table or on its short exclusion list.  The same for the MLP epilogue forms (activations, their
-derivatives from the saved output, fused dropout: conv_ref.mlp_epilogue on the dyadic kind, with a case for every copy of that
-epilogue the planner reaches) and for pmoe_mlp_wgrad with every refusal of its entry point; and the proof that the inputs
-discriminate: each deliberately wrong variant of the reference is told apart by some case.  No GPU: pmoe_conv2d_plan and
-pmoe_conv2d_wgrad_plan are host code, and a refused call launches nothing."""
+requests and switches -- e4m3 operands among them -- is in the table: there is no exclusion list.  The same for the MLP epilogue
+forms (activations, their derivatives from the saved output, fused dropout: conv_ref.mlp_epilogue on the dyadic kind, with a
+case for every copy of that epilogue the planner reaches), for the operands of the e4m3 launches (the lattice and unit kinds are
+fixed points of the quantisers of oracle/fp8_policy.py; the select kind) and for pmoe_mlp_wgrad with every refusal of its entry
+point; and the proof that the inputs discriminate: each deliberately wrong variant of the reference is told apart by some case.
+No GPU: pmoe_conv2d_plan and pmoe_conv2d_wgrad_plan are host code, and a refused call launches nothing."""
 import ctypes as C
 import itertools
 
@@ -31,19 +32,28 @@ def conv_tensors(L, device):
     kw = L["kw"]
     dtype, E, ks = kw["dtype"], L["w"].shape[0], kw["ks"]
     coutp = R.r64(kw["cout"])
+    f8, a8 = L.get("f8", False), L.get("a8", False)
+    x8 = oscale = None
     if device == "meta":
         mk = lambda t, dt: None if t is None else torch.empty(t.shape, dtype=dt, device="meta")
-        wp = torch.empty(E, coutp, ks * ks, kw["cin"], dtype=dtype, device="meta")
+        wp = torch.empty(E, coutp, ks * ks, kw["cin"], dtype=torch.uint8 if f8 else dtype, device="meta")
         bias = None if L["bias"] is None else torch.empty(E, coutp, dtype=F32, device="meta")
+        if f8:
+            oscale, x8 = torch.empty(E, coutp, dtype=F32, device="meta"), mk(L["inp"], torch.uint8) if a8 else None
     else:
         mk = lambda t, dt: None if t is None else t.to(dt).to(device).contiguous()
-        wp = mk(R.pack_weights(L["w"], coutp, kw["cin"], dtype), dtype)
+        if f8:
+            # e4m3 operands, built from the reference's statement (conv_ref.e4m3_operands), never by another kernel
+            wp, oscale, x8 = (None if v is None else v.to(device).contiguous() for v in R.e4m3_operands(L, coutp))
+        else:
+            wp = mk(R.pack_weights(L["w"], coutp, kw["cin"], dtype), dtype)
         bias = None
         if L["bias"] is not None:
             bias = torch.zeros(E, coutp, dtype=F32)
             bias[:, :kw["cout"]] = L["bias"].to(F32)
             bias = bias.to(device)
-    t = {"x": mk(L["inp"], dtype), "w": wp, "out": mk(L["out_init"], dtype), "bias": bias, "bn_coef": mk(L["bn_coef"], F32)}
+    t = {"x": x8 if a8 else mk(L["inp"], dtype), "w": wp, "out": mk(L["out_init"], dtype), "bias": bias,
+         "bn_coef": mk(L["bn_coef"], F32), "out_scale": oscale}
     t["res"] = t["out"] if L["res_is_out"] else mk(L["res"], dtype)
     return t
 
@@ -57,7 +67,8 @@ def conv_prepare(L, t, stats=None):
         in_coff=kw["in_coff"], out_coff=kw["out_coff"], res=t["res"], res_coff=kw.get("res_coff", 0),
         res_mode=kw.get("res_mode", hip.RES_NONE), bias=t["bias"], act=kw.get("act", hip.ACT_NONE),
         drop_p=kw.get("drop_p", 0.0), seed=kw.get("seed", 0), stats=(True if stats is None else stats) if kw["stats"] else None,
-        bn_coef=t["bn_coef"], bn_ipe=kw.get("bn_ipe", 0), shuffle2_c=kw.get("shuffle_c", 0), shapes_only=t["x"].device.type == "meta")
+        bn_coef=t["bn_coef"], bn_ipe=kw.get("bn_ipe", 0), shuffle2_c=kw.get("shuffle_c", 0), out_scale=t["out_scale"],
+        in_scale=L.get("in_scale", 1.0), shapes_only=t["x"].device.type == "meta")
 
 
 def wgrad_desc(L):
@@ -104,7 +115,13 @@ IPES = (1, 2, 5)
 # tri-state ones also at their "always" value
 CONV_SWITCHES = (None, ("PMOE_CONV_C16", "0"), ("PMOE_RES_DMA", "0"), ("PMOE_RES_PIPE", "0"), ("PMOE_CONV_C1X1", "0"),
                  ("PMOE_CONV_DMA", "0"), ("PMOE_DMA_STREAM", "0"), ("PMOE_DMA_STREAM", "2"), ("PMOE_DMA_PRODUCER", "0"),
-                 ("PMOE_DMA_PRODUCER", "2"), ("PMOE_DMA_NARROW", "0"), ("PMOE_DMA_MF16", "0"), ("PMOE_DMA_MF16", "1"))
+                 ("PMOE_DMA_PRODUCER", "2"), ("PMOE_DMA_NARROW", "0"), ("PMOE_DMA_MF16", "0"), ("PMOE_DMA_MF16", "1"),
+                 ("PMOE_CONV_F8DMA", "0"))
+# the second, narrow sweep (no switch): many images per expert on small maps -- >= 4096 pixels per expert where neither the
+# LDS-DMA kernels nor the LITE tile fit (742 | 4742 | 8742) -- and 8-channel layers (float32 522 | 541 as plain launches)
+SMALL_SIDES = (2, 4, 8)
+MANY_IPES = (64, 256)
+CHANNELS_8 = (8,) + CHANNELS
 WGRAD_SWITCHES = (None, ("PMOE_WGRAD_DMA", "0"), ("PMOE_WGRAD_NARROW", "0"), ("PMOE_WGRAD_V2", "0"), ("PMOE_WGRAD_REQ", "0"),
                   ("PMOE_WGRAD_REQ", "2"), ("PMOE_WGRAD_PIPE", "0"))
 # request -> (keywords of ops._planning_desc, the launch is a data gradient, res == out)
@@ -127,17 +144,30 @@ REQUESTS = {
     "delu": (dict(res_mode=hip.RES_DELU), False), "dtanh": (dict(res_mode=hip.RES_DTANH), False),
     "dsigmoid": (dict(res_mode=hip.RES_DSIGMOID), False),
 }
+# e4m3 operands (bfloat16 output only: every other descriptor with w_fp8 is refused): e4m3 weights with bfloat16 input (f8) and
+# with e4m3 input bytes too (a8), each with the forms a forward layer asks for; and two MLP forms, for the no_copy rule
+_F8, _A8 = dict(w_fp8=True, in_scale=R.IN_SCALE), dict(w_fp8=True, in_fp8=True, in_scale=R.IN_SCALE)
+for _name, _kw in (("f8", _F8), ("a8", _A8)):
+    REQUESTS.update({
+        _name: (dict(_kw), False), f"{_name}+bias": (dict(_kw, bias=True), False),
+        f"{_name}+bias+relu": (dict(_kw, bias=True, act=hip.ACT_RELU), False), f"{_name}+stats": (dict(_kw, stats=True), False),
+        f"{_name}+add": (dict(_kw, res_mode=hip.RES_ADD), False), f"{_name}+drelu": (dict(_kw, res_mode=hip.RES_DRELU), False),
+        f"{_name}+shared": (dict(_kw, in_shared=True), False), f"{_name}+addin": (dict(_kw, res_mode=hip.RES_ADD), False), f"{_name}+inbn": (dict(_kw, res_mode=hip.RES_INBN), False),
+        f"{_name}+elu": (dict(_kw, act=hip.ACT_ELU), False), f"{_name}+drop": (dict(_kw, drop_p=R.DROP_P, seed=5), False)})
+E4M3_REQUESTS = tuple(n for n in REQUESTS if n.split("+")[0] in ("f8", "a8"))
 
 
 # the single-form requests of the grid -> the flag of conv_ref.CASES that runs the form.  A data gradient is the same kernel under
 # another descriptor, so a (code, dtype, form) counts as run whichever of a case's two conv launches carries it.
 FORM_OF = {"bias": "bias", "dgrad+bias": "bias", "bias+relu": "relu", "add": "add", "dgrad+add": "add", "dgrad+addin": "addin",
-           "drelu": "drelu", "dgrad+drelu": "drelu", "shared": "shared", "stats": "stats"}
+           "drelu": "drelu", "dgrad+drelu": "drelu", "shared": "shared", "stats": "stats",
+           **{n: n.split("+")[-1] for n in E4M3_REQUESTS if n.split("+")[-1] in ("f8", "a8", "bias", "relu", "stats", "add", "addin", "drelu", "shared")}}
 # the second, coarser rule: the requests that carry an MLP epilogue form -> the forms.  The form's code exists in three copies
 # (conv_ref.EPILOGUE_COPY); every (copy, dtype, form) the planner lets a descriptor reach has a case, whichever tile code runs it.
 MLP_FORMS_OF = {"elu": ("elu",), "tanh": ("tanh",), "sigmoid": ("sigmoid",), "drop": ("drop",), "bias+elu+drop": ("elu", "drop"),
                 "dgrad+delu": ("delu",), "dgrad+dtanh": ("dtanh",), "dgrad+dsigmoid": ("dsigmoid",), "dgrad+delu+drop": ("delu",),
-                "delu": ("delu",), "dtanh": ("dtanh",), "dsigmoid": ("dsigmoid",)}
+                "delu": ("delu",), "dtanh": ("dtanh",), "dsigmoid": ("dsigmoid",),
+                "f8+elu": ("elu",), "f8+drop": ("drop",), "a8+elu": ("elu",), "a8+drop": ("drop",)}
 
 
 def _grid_plan(lib, E, ipe, cin, cout, side, ks, stride, dtype, name):
@@ -152,31 +182,48 @@ def _grid_plan(lib, E, ipe, cin, cout, side, ks, stride, dtype, name):
         d = ops._planning_desc(N, side, side, so, so, cin, cout, R.r64(cout), ipe, ks, stride, pad, dtype, **kw)
     else:
         d = ops._planning_desc(N, so, so, side, side, cout, cin, R.r64(cin), ipe, ks, 1, ks - 1 - pad, dtype, dilate=stride == 2, **kw)
-        if name == "dgrad+addin":
-            d.res = d.out
+    if name.endswith("+addin"):                                             # accumulated in place: res == out
+        d.res = d.out
     return lib.pmoe_conv2d_plan(C.byref(d))
 
 
 def test_every_plan_code_of_the_grid_has_a_case(monkeypatch):
-    """plans only: channels x sides x images per expert x filter x stride x dtype x request x per-launch switch"""
+    """plans only: channels x sides x images per expert x filter x stride x dtype x request x per-launch switch, and a second, narrow
+    sweep (SMALL_SIDES x MANY_IPES, 8-channel layers) without switches.  Coverage is per (code, dtype): a code that float32
+    reaches needs a float32 case.  The requests with e4m3 operands go through the same rules as every other: no exclusion list."""
     lib = hip.load()
     seen, accepted, accepted_mlp, no_copy = {"conv": set(), "wgrad": set()}, set(), set(), set()
+    assert not hasattr(R, "EXCLUDED") and not hasattr(R, "is_excluded"), "there is no exclusion list"
+
+    def conv_sweep(channels, sides, ipes):
+        for dtype, cin, cout, side, ipe, ks, stride in itertools.product((torch.bfloat16, torch.float32), channels, channels,
+                                                                         sides, ipes, (1, 3), (1, 2)):
+            # (e4m3 operands: bfloat16 launches over whole 64-channel chunks; everything else is refused -- asserted below)
+            e4m3 = dtype == torch.bfloat16 and cin % 64 == 0
+            for name in REQUESTS:
+                if name in E4M3_REQUESTS and not e4m3:
+                    continue
+                code = _grid_plan(lib, 2, ipe, cin, cout, side, ks, stride, dtype, name)
+                if code is not None and code >= 0:
+                    seen["conv"].add((code, dtype))
+                    if name in FORM_OF:
+                        accepted.add((code, dtype, FORM_OF[name]))
+                    if name in MLP_FORMS_OF:
+                        if code not in R.EPILOGUE_COPY:
+                            no_copy.add((code, name))
+                        accepted_mlp.update((R.EPILOGUE_COPY.get(code), dtype, form) for form in MLP_FORMS_OF[name])
+                    assert "inbn" not in name or name not in E4M3_REQUESTS, (code, name)    # (no e4m3 kernel applies a BatchNorm)
+
     for sw in CONV_SWITCHES:
         with monkeypatch.context() as m:
             if sw:
                 m.setenv(*sw)
-            for dtype, cin, cout, side, ipe, ks, stride in itertools.product((torch.bfloat16, torch.float32), CHANNELS, CHANNELS,
-                                                                             SIDES, IPES, (1, 3), (1, 2)):
-                for name in REQUESTS:
-                    code = _grid_plan(lib, 2, ipe, cin, cout, side, ks, stride, dtype, name)
-                    if code is not None and code >= 0:
-                        seen["conv"].add(code)
-                        if name in FORM_OF and not R.is_excluded(code):
-                            accepted.add((code, dtype, FORM_OF[name]))
-                        if name in MLP_FORMS_OF:
-                            if code not in R.EPILOGUE_COPY:
-                                no_copy.add((code, name))
-                            accepted_mlp |= {(R.EPILOGUE_COPY.get(code), dtype, form) for form in MLP_FORMS_OF[name]}
+            conv_sweep(CHANNELS, SIDES, IPES)
+    conv_sweep(CHANNELS_8, SMALL_SIDES, MANY_IPES)
+    conv_sweep(CHANNELS_8, SIDES[:3], IPES[:2])
+    # what the e4m3 requests skip above is refused: float32, and reductions that are no whole 64-channel chunks
+    for name in E4M3_REQUESTS:
+        assert _grid_plan(lib, 2, 2, 64, 64, 8, 3, 1, torch.float32, name) < 0 and _grid_plan(lib, 2, 2, 32, 64, 8, 3, 1, torch.bfloat16, name) < 0
     for sw in WGRAD_SWITCHES:
         with monkeypatch.context() as m:
             if sw:
@@ -190,18 +237,19 @@ def test_every_plan_code_of_the_grid_has_a_case(monkeypatch):
                                         ipe, ks, stride, ks // 2, hip._TORCH_DT[dtype], per_image=per_image, bn_z_ld=0 if bn else None)
                     code = lib.pmoe_conv2d_wgrad_plan(C.byref(d))
                     if code >= 0:
-                        seen["wgrad"].add(code)
-    covered = {"conv": {c for case in R.CASES for c in case.codes[:2] if c is not None},
-               "wgrad": {case.codes[2] for case in R.CASES if case.codes[2] is not None}}
-    excluded = R.is_excluded
-    assert sorted(R.EXCLUDED) == [8000], "the exclusion list is the e4m3 codes, nothing else"
+                        seen["wgrad"].add((code, dtype))
+    covered = {"conv": {(c, case.dtype) for case in R.CASES for c in case.codes[:2] if c is not None},
+               "wgrad": {(case.codes[2], case.dtype) for case in R.CASES if case.codes[2] is not None}}
     for k in seen:
-        missing = sorted(c for c in seen[k] - covered[k] if not excluded(c))
-        assert not missing, f"{k} plan codes without a case: {missing}"
-        print(k, "codes seen:", sorted(seen[k]), "excluded:", sorted(c for c in seen[k] if excluded(c)))
+        missing = sorted((c, str(d)) for c, d in seen[k] - covered[k])
+        assert not missing, f"{k} (plan code, dtype) without a case: {missing}"
+        print(k, "codes seen:", sorted((c, str(d)) for c, d in seen[k]))
     # the table names nothing the grid does not know (a stale code would be a case that runs on something else)
-    assert covered["conv"] <= seen["conv"] and covered["wgrad"] <= seen["wgrad"]
-    assert covered["conv"] <= set(R.ROUNDING), sorted(covered["conv"] - set(R.ROUNDING))
+    assert covered["conv"] <= seen["conv"] and covered["wgrad"] <= seen["wgrad"], sorted(
+        (c, str(d)) for c, d in (covered["conv"] - seen["conv"]) | (covered["wgrad"] - seen["wgrad"]))
+    conv_codes = {c for c, _ in covered["conv"]}
+    assert conv_codes <= set(R.ROUNDING), sorted(conv_codes - set(R.ROUNDING))
+    assert {742, 4742, 8742, 8507, 8622, 8641, 8642, 8722, 8741, 10007} <= conv_codes
     # every form on every code (and dtype) whose planner accepts it, and channel windows on every code
     ran, windowed = set(), set()
     for case in R.CASES:
@@ -213,7 +261,7 @@ def test_every_plan_code_of_the_grid_has_a_case(monkeypatch):
                     windowed.add(case.codes[i])
     missing = sorted((c, str(d), f) for c, d, f in accepted - ran)
     assert not missing, f"(code, dtype, form) accepted by the planner and run by no case: {missing}"
-    unwindowed = sorted(c for c in covered["conv"] - windowed if not excluded(c))
+    unwindowed = sorted(conv_codes - windowed)
     assert not unwindowed, f"plan codes no case runs on channel windows: {unwindowed}"
     # the MLP epilogue forms: only the kernels that carry a copy of that epilogue ever answer a descriptor that asks for one, and
     # every (copy, dtype, form) the grid reaches is run by a case
@@ -240,7 +288,7 @@ def _representable(t, dtype):
     return torch.equal(t.to(dtype).to(F64)[~torch.isnan(t)], t[~torch.isnan(t)])
 
 
-def case_kinds(cases, kinds=R.KINDS + (R.DYADIC,)):
+def case_kinds(cases, kinds=R.KINDS + (R.DYADIC, R.SELECT)):
     """(case, kind) for every kind the case runs on, with the ids the two stacked parametrisations gave before the dyadic kind"""
     return dict(argnames="case,kind", argvalues=[(c, k) for k in kinds for c in cases if k in R.kinds_of(c)],
                 ids=[f"{R.case_id(c)}-{k}" for k in kinds for c in cases if k in R.kinds_of(c)])
@@ -261,6 +309,8 @@ def test_generator_properties(case, kind):
             assert L[name] is None or _representable(L[name], F32), (k, name)
         bound = R.abs_bound(L)
         assert bound < 2 ** 24, (k, bound)
+        if L.get("f8"):
+            check_e4m3_operands(L, fixed_point=True)
         ref = R.conv_reference(L)
         # float32 in two orders == float64, bit for bit (INBN: the operand is the reference's own)
         xw = L["inp"][..., kw["in_coff"]:kw["in_coff"] + kw["cin"]]
@@ -320,6 +370,122 @@ def test_generator_properties(case, kind):
         unit = 2048 if L["bn"] is not None else 1                           # (dz: multiples of 2^-11)
         assert mags.max() * unit < 2 ** 24, mags.max().item()
         assert torch.equal(R.wgrad_reference(L, evaluate=F32)["dw_ws"].to(F64), ref["dw_ws"])
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# e4m3 operands: the fixed-point property of the lattice and unit kinds, the operands the GPU test feeds, the select kind
+
+F8_CASES = [c for c in R.CASES if R.SELECT in R.kinds_of(c)]
+
+
+def _same_with_nan(a, b):
+    return torch.equal(torch.isnan(a), torch.isnan(b)) and torch.equal(a.nan_to_num(), b.nan_to_num())
+
+
+def check_e4m3_operands(L, fixed_point):
+    """what conv_ref.e4m3_operands hands the kernel decodes to what the reference convolves: bytes x scales == the quantised
+    operands (fixed_point: == the launch's own input and weights, the quantisers change nothing); pad rows zero, out_scale NaN
+    past cout, 0x7f outside the input window; in_scale a power of two under which nothing saturates unless the kind means it to"""
+    kw, s_in = L["kw"], L["in_scale"]
+    cin, cout, c0 = kw["cin"], kw["cout"], kw["in_coff"]
+    coutp = R.r64(cout)
+    qi, qw = R.operands(L)
+    if fixed_point:
+        assert _same_with_nan(qi, L["inp"]) and torch.equal(qw, L["w"]), "the generator is no fixed point of the e4m3 quantisers"
+        assert L["inp"][..., c0:c0 + cin].abs().max() * s_in <= 448
+    assert torch.equal(qw, R.qdq_weight(qw)) and _same_with_nan(qi, R.qdq_act(qi, s_in))
+    assert s_in > 0 and torch.frexp(torch.tensor(s_in))[0] == 0.5
+    wb, osc, xb = R.e4m3_operands(L, coutp)
+    E, ks = L["w"].shape[0], kw["ks"]
+    assert wb.shape == (E, coutp, ks * ks, cin) and wb[:, cout:].abs().sum() == 0
+    assert torch.isnan(osc[:, cout:]).all() and not torch.isnan(osc[:, :cout]).any()
+    assert torch.equal(torch.frexp(osc[:, :cout])[0], torch.full((E, cout), 0.5)), "out_scale: powers of two"
+    deq = wb[:, :cout].view(torch.float8_e4m3fn).to(F64) * (osc[:, :cout].to(F64) * s_in)[:, :, None, None]
+    assert torch.equal(deq.permute(0, 1, 3, 2).reshape(qw.shape), qw)
+    if L["a8"]:
+        outside = torch.ones(xb.shape[-1], dtype=torch.bool)
+        outside[c0:c0 + cin] = False
+        assert (xb[..., outside] == 0x7f).all() and xb.shape == L["inp"].shape
+        assert torch.equal(xb[..., c0:c0 + cin].view(torch.float8_e4m3fn).to(F64) / s_in, qi[..., c0:c0 + cin])
+    else:
+        assert xb is None
+
+
+def test_one_e4m3_case_runs_under_another_in_scale():
+    scales = {R.launches(c, "unit")["f"]["in_scale"] for c in F8_CASES}
+    assert R.IN_SCALE in scales and len(scales) > 1
+
+
+@pytest.mark.parametrize(**case_kinds(F8_CASES, (R.SELECT,)))
+def test_select_generator_properties(case, kind):
+    """what tests/test_conv_gpu.py assumes of the select kind: one non-zero +-2^j per filter row, e4m3-exact after its row scale; the
+    planted input classes all inside the channel window; the accumulator one product per element -- +-2^j times the converted
+    input at the shifted pixel, 0 in the padding -- exact in bfloat16, and every float32 sum of the tail behind it exact"""
+    L = R.launches(case, kind)["f"]
+    kw, s_in = L["kw"], L["in_scale"]
+    cin, cout, c0, ks, stride, pad = kw["cin"], kw["cout"], kw["in_coff"], kw["ks"], kw["stride"], kw["pad"]
+    for name in ("inp", "w", "out_init", "res"):
+        assert L[name] is None or _representable(L[name], BF16), name
+    assert L["bias"] is None or _representable(L["bias"], F32)
+    check_e4m3_operands(L, fixed_point=False)
+    w = L["w"]
+    E = w.shape[0]
+    flat = w.reshape(E, cout, -1)
+    assert ((flat != 0).sum(2) == 1).all(), "one non-zero per row"
+    val, at = flat.gather(2, flat.abs().argmax(2, keepdim=True))[..., 0], flat.abs().argmax(2)
+    assert torch.equal(torch.frexp(val.abs())[0], torch.full_like(val, 0.5)) and (val > 0).any() and (val < 0).any()
+    assert torch.equal(R.qdq_weight(w), w), "the scaled weight is e4m3-exact"
+    assert len(torch.unique(at % (ks * ks))) == ks * ks, "every tap is selected by some channel"
+    # the planted classes, inside the window; NaN outside it
+    outside = torch.ones(L["inp"].shape[-1], dtype=torch.bool)
+    outside[c0:c0 + cin] = False
+    assert torch.isnan(L["inp"][..., outside]).all()
+    xw = L["inp"][..., c0:c0 + cin]
+    s = xw * s_in
+    present = lambda vals: bool(torch.isin(vals, s).all())
+    if L["a8"]:
+        codes = torch.unique(R.e4m3_operands(L, R.r64(cout))[2][..., c0:c0 + cin])
+        assert codes.numel() == 254 and 0x7f not in codes and 0xff not in codes, "all 254 non-NaN byte codes"
+    else:
+        v = R.e4m3_values()
+        ties = (v[:-1] + v[1:]) / 2
+        for sign in (1, -1):
+            assert present(sign * v) and present(sign * ties), "every e4m3 value and every tie, both signs"
+            assert present(sign * R.bf16_neighbour(ties, 1)) and present(sign * R.bf16_neighbour(ties, -1)), "the ties' bf16 neighbours"
+            assert ((sign * s > 0) & (s.abs() < 2.0 ** -10)).any(), "below half the smallest subnormal"
+            assert (sign * s > 448).any() and (sign * s).max() >= 1.5e5, "beyond 448 up to 1e4 x 16"
+        assert (v[1:8] == torch.arange(1, 8) * 2.0 ** -9).all() and ties[0] == 2.0 ** -10, "seven subnormals; the first tie"
+        q = R.qdq_act(xw, s_in) * s_in
+        assert q.abs().max() == 448 and ((q == 0) & (xw != 0)).any() and present(torch.tensor([464.0], dtype=F64))
+    assert ((xw == 0) & torch.signbit(xw)).any() and ((xw == 0) & ~torch.signbit(xw)).any(), "both zeros"
+    # one product per element
+    ref = R.conv_reference(L)
+    acc = ref["acc"]
+    n, ho, wo = acc.shape[:3]
+    xq = R.qdq_act(xw, s_in)
+    span_y, span_x = (ho - 1) * stride + ks, (wo - 1) * stride + ks
+    xp = F.pad(xq, (0, 0, pad, max(span_x - xq.shape[2] - pad, 0), pad, max(span_y - xq.shape[1] - pad, 0)))
+    want = torch.empty_like(acc)
+    ipe = kw["ipe"]
+    for e in range(E):
+        xe = xp[:ipe] if kw["in_shared"] else xp[e * ipe:(e + 1) * ipe]
+        for co in range(cout):
+            ci, ky, kx = int(at[e, co]) // (ks * ks), int(at[e, co]) % (ks * ks) // ks, int(at[e, co]) % ks
+            want[e * ipe:(e + 1) * ipe, :, :, co] = val[e, co] * xe[:, ky:ky + (ho - 1) * stride + 1:stride, kx:kx + (wo - 1) * stride + 1:stride, ci]
+    assert torch.equal(acc, want), "the accumulator is not the selected, converted input"
+    assert torch.equal(R.round_to(acc, BF16), acc) and R.abs_bound(L) < 2 ** 24
+    assert (acc != 0).float().mean() > 0.5 and acc.abs().max() <= 448 / s_in * 4
+    # the float32 tail: out_scale (a power of two), bias, side input -- every sum exact, so the one rounding is the bfloat16 one
+    v = acc
+    if L["bias"] is not None:
+        v = v + L["bias"].repeat_interleave(ipe, 0)[:, None, None, :]
+        assert torch.equal(R._f32(v), v), "acc + bias rounds in float32"
+    if kw.get("res_mode") == R.RES_ADD:
+        res = L["out_init"] if L["res_is_out"] else L["res"]
+        v = v + res[..., kw["res_coff"]:kw["res_coff"] + cout]
+        assert torch.equal(R._f32(v), v), "acc + bias + res rounds in float32"
+    if kw["stats"]:
+        assert (ref["sums_abs"] > 0).all()
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -568,7 +734,8 @@ def test_skinny_row_limit():
 
 def test_every_mutant_is_told_apart():
     """each deliberately wrong variant of conv_ref.MUTANTS leaves the reference's interval of stored values on at least one launch
-    of the skinny-GEMM and MLP-form cases: the inputs can tell it from the kernel's contract"""
+    of the skinny-GEMM and MLP-form cases: the inputs can tell it from the kernel's contract.  And the select kind tells the two
+    mutants of the main loop apart on the cases with e4m3 operands"""
     cases = [c for c in R.CASES if 3000 in c.codes[:2] or c in DYADIC_CASES]
     caught = {}
     for case in cases:
@@ -590,6 +757,15 @@ def test_every_mutant_is_told_apart():
             break
     print("\n".join(f"{m}: {w}" for m, w in caught.items()))
     assert not set(R.MUTANTS) - set(caught), f"mutants no case tells apart: {sorted(set(R.MUTANTS) - set(caught))}"
+    # the select kind of the cases with e4m3 operands, where equality is the GPU test's criterion: a dropped k-slice and a tap that
+    # reads the first column in place of the zero border change stored elements on EVERY such 3x3 case -- channel 0 selects the
+    # last input channel at the left tap of the middle filter row.  (A 1x1 case has no border to get wrong.)
+    for case in F8_CASES:
+        L = R.launches(case, R.SELECT)["f"]
+        ref = R.conv_reference(L)["stored"]
+        for mut in ("kslice", "tapshift"):
+            n = int((R.conv_reference(L, mut=mut)["stored"] != ref).sum())
+            assert n or (mut == "tapshift" and case.ks == 1), f"{R.case_id(case)}-{R.SELECT}: {mut} stores what the reference stores"
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

@@ -3,7 +3,7 @@ conv_c16.hip, gemm_skinny.hip, conv_wgrad.hip), pmoe_mlp_wgrad and the weight pa
 operation (tests/conv_ref.py), at the smallest shapes that reach each plan code (conv_ref.CASES; tests/test_conv_cpu.py proves
 that the table covers every code the planners answer), through pmoe_amd.ops, the binding the engines use.
 
-Three kinds of input (tests/test_conv_cpu.py checks on the CPU what is assumed of them here):
+Four kinds of input (tests/test_conv_cpu.py checks on the CPU what is assumed of them here):
   lattice  integers with sum |x||w| < 2^24: a float32 accumulation is exact in any order, so every STORED element must equal the
            reference's, rounded in the order conv_ref.ROUNDING names for the kernel -- one missing or doubled term, a truncation, a
            second rounding or a residual left out all show as unequal elements.  Fused statistics: per-expert totals within
@@ -16,6 +16,12 @@ Three kinds of input (tests/test_conv_cpu.py checks on the CPU what is assumed o
            in [round(ref - allow), round(ref + allow)], which is one value for all but a per cent of the elements.  The dropout
            mask is compared element for element with the hash wherever the undropped value is non-zero.
            Continuous data stays in tests/test_ops_gpu.py for the K-long float32 sums only.
+  select   the cases with e4m3 operands, next to lattice and unit (both fixed points of the e4m3 quantisers, so the reference is
+           unchanged and equality holds): one non-zero weight +-2^j per output channel, inputs that hold every e4m3 value, tie,
+           underflow and overflow (bfloat16 input) or all 254 non-NaN byte codes (e4m3 input) -- every stored element equals
+           +-2^j times the policy's conversion of one input element, whatever the loader, chunk width and tap.  The operands of
+           such a launch (weight bytes, out_scale with NaN past cout, input bytes with 0x7f outside the window) come from
+           conv_ref.e4m3_operands, the reference's own statement.
 Every buffer is compared WHOLE: outputs are sentinel-filled before the launch, so pad channels, the other columns of out_ld, the
 untouched half of a concatenation buffer and the odd pixels of the in-place stride-2 1x1 gradient must come back unchanged;
 everything outside an input's channel window is NaN, so a read outside it poisons the output.  The plan code is asserted before
@@ -72,7 +78,9 @@ def check_conv_launch(L, code_expected, kind, what):
         neg = torch.signbit(t["out"].float().cpu()) != torch.signbit(ref["out"].to(F32))
         assert not neg.any(), f"{what}: code {code}: {int(neg.sum())} elements differ in sign only (a zero of the other sign); first {neg.nonzero()[:4].tolist()}"
     for name, src in (("x", L["inp"]), ("res", None if L["res_is_out"] else L["res"])):
-        if src is not None:                                            # inputs come back as they went in (NaN outside the windows)
+        if src is not None and t[name].dtype == torch.uint8:           # (e4m3 input bytes: 0x7f outside the window)
+            assert torch.equal(t[name].cpu(), R.e4m3_operands(L, coutp)[2]), f"{what}: {name} modified"
+        elif src is not None:                                          # inputs come back as they went in (NaN outside the windows)
             back = t[name].cpu().to(F64)
             assert torch.equal(torch.isnan(back), torch.isnan(src)) and torch.equal(back.nan_to_num(), src.nan_to_num()), f"{what}: {name} modified"
     if guard is None:

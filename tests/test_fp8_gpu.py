@@ -187,6 +187,112 @@ def test_bn_apply_fp8_side_output_is_the_policy_quantiser():
         assert torch.equal(y8.cpu(), want), int((y8.cpu() != want).sum())
 
 
+GUARD8 = 64          # sentinel elements before and after a buffer (a multiple of 16 bytes in every type used here)
+
+
+def _guarded(shape, dtype, fill):
+    """(a dense tensor of ``shape`` inside a flat buffer with GUARD8 sentinel elements on both sides, the flat buffer)"""
+    n = 1
+    for d in shape:
+        n *= d
+    flat = torch.full((n + 2 * GUARD8,), fill, dtype=dtype, device=DEV)
+    return flat[GUARD8:GUARD8 + n].view(shape), flat
+
+
+def _guards_intact(flat, fill, what):
+    g = torch.cat([flat[:GUARD8], flat[-GUARD8:]]).cpu()
+    assert torch.equal(g, torch.full_like(g, fill)), f"{what}: bytes around the buffer written"
+
+
+@pytest.mark.parametrize("shape", [(3, 130, 128, 1), (3, 8, 192, 3)], ids=lambda s: "x".join(map(str, s)))
+@pytest.mark.parametrize("in_scale", [P.IN_SCALE, 4.0])
+def test_weight_quantiser_whole_buffers(shape, in_scale):
+    """pmoe_pack_conv_weights_fp8 beyond the one shape of test_weight_quantiser_is_bit_exact: a 1x1 layer with a ragged last channel
+    block, a 3x3 layer with 8 outputs, three experts.  Bytes (modulo the sign of zero), wscale, oscale and the bf16 data-gradient
+    operand against the policy, bit for bit and WHOLE: pad rows and pad columns are zero (their scales: 1 and 1 / in_scale, the
+    policy's all-zero row), the sentinels around every buffer survive -- and the pack equals the operands tests/conv_ref.py builds
+    for the convolution cases from the same weights (conv_ref.e4m3_operands)."""
+    from tests import conv_ref as R
+    E, cout, cin, ks = shape
+    taps = ks * ks
+    g = torch.Generator().manual_seed(sum(shape))
+    ws = []
+    for e in range(E):
+        w = torch.randn(cout, cin, ks, ks, generator=g) * (2.0 / (cin * taps)) ** 0.5
+        w[0] = 0.0                                               # all-zero row: scale 1
+        w[1] *= 1e-4
+        w[2] = w[2] / w[2].abs().max() * 448.0 * 2.0 ** -5       # amax exactly on the power-of-two edge
+        w[3] = w[3] / w[3].abs().max() * 448.0 * 2.0 ** 3
+        w[4, 0, 0, 0] = w[4].abs().max() * 300                   # one dominant element: the rest falls into the subnormals
+        w[5] = torch.linspace(-1, 1, cin * taps).view(cin, ks, ks) * 2.0 ** -3
+        ws.append(w)
+    dev_ws = [w.to(DEV).contiguous() for w in ws]
+    tab = hip.ptr_table(dev_ws, DEV)
+    coutp, cinp, cinp2, coutp2 = r64(cout), r16(cin), r64(cin), r16(cout)
+    f8, f8_flat = _guarded((E, coutp, taps, cinp), torch.uint8, 0xAB)
+    dg, dg_flat = _guarded((E, cinp2, taps, coutp2), BF, -77.0)
+    wscale, ws_flat = _guarded((E, coutp), torch.float32, -77.0)
+    oscale, os_flat = _guarded((E, coutp), torch.float32, -77.0)
+    ops.pack_conv_weights_fp8(tab, f8, dg, wscale, oscale, in_scale, E, cout, cin, ks, coutp, cinp, cinp2, coutp2)
+    torch.cuda.synchronize()
+    for flat, fill, what in ((f8_flat, 0xAB, "bytes"), (dg_flat, -77.0, "data-gradient operand"), (ws_flat, -77.0, "wscale"), (os_flat, -77.0, "oscale")):
+        _guards_intact(flat, fill, what)
+    want_s, want_b, want_d = torch.ones(E, coutp), torch.zeros(E, coutp, taps, cinp, dtype=torch.uint8), torch.zeros(E, cinp2, taps, coutp2)
+    for e in range(E):
+        s = P.row_scale(ws[e])
+        want_s[e, :cout] = s
+        want_b[e, :cout, :, :cin] = P.e4m3_bytes(ws[e] / s.view(-1, 1, 1, 1)).reshape(cout, cin, taps).permute(0, 2, 1)
+        want_d[e, :cin, :, :cout] = P.qdq_weight(ws[e]).flip(2, 3).permute(1, 2, 3, 0).reshape(cin, taps, cout)
+    zero = lambda b: torch.where(b == 0x80, torch.zeros_like(b), b)                     # -0 and +0 are the same number
+    assert torch.equal(wscale.cpu(), want_s) and torch.equal(oscale.cpu(), want_s / in_scale)
+    assert torch.equal(zero(f8.cpu()), zero(want_b))
+    assert torch.equal(dg.float().cpu(), want_d)                                        # q * s is exact in bf16
+    for src, dev in zip(ws, dev_ws):
+        assert torch.equal(dev.cpu(), src), "weights modified"
+    wb, osc, xb = R.e4m3_operands({"w": torch.stack(ws).double(), "in_scale": in_scale, "a8": False, "kw": {}}, coutp)
+    assert xb is None and torch.equal(zero(f8.cpu()), zero(wb)) and torch.equal(oscale.cpu()[:, :cout], osc[:, :cout])
+
+
+@pytest.mark.parametrize("res,relu", [(False, True), (True, True), (False, False), (True, False)], ids=["relu", "res+relu", "plain", "res"])
+@pytest.mark.parametrize("E,rows,C_", [(2, 37, 128), (3, 5, 256), (2, 203, 512), (1, 8203, 512)], ids=lambda v: str(v))
+def test_bn_apply_fp8_side_output_shapes(E, rows, C_, res, relu):
+    """pmoe_bn_apply's e4m3 side output beyond the one shape above: 16, 32 and 64 channel vectors per row, row counts that are no
+    multiple of a block's rows (a ragged last block) and one that takes the grid-stride loop round again (more than 2048 blocks of
+    vectors), with and without residual and ReLU.  The bytes equal the policy's -- which are the input bytes tests/conv_ref.py
+    feeds conv3x3_dma_f8_kernel for the same activation -- the bf16 output is unchanged by asking for them, and the guard bytes
+    around y8 survive."""
+    from tests import conv_ref as R
+    g = torch.Generator().manual_seed(E + rows + C_)
+    x = rnd((E * rows, 1, 1, C_), g, BF, 6.0)
+    # the first channel vector of expert 0 passes through unchanged (scale 1, no shift, no residual): saturation at 28 = 448 / 16
+    # and beyond, the smallest e4m3 subnormal, the tie above it, the tie between it and zero, a value that underflows
+    x.view(-1)[:8] = torch.tensor([28.0, 1e4, -1e4, 2.0 ** -13, 3 * 2.0 ** -14, 2.0 ** -14, 2.0 ** -16, 27.9]).to(BF).float()
+    scale, shift, mean = torch.rand(E, C_, generator=g) + 0.5, torch.randn(E, C_, generator=g) * 0.2, torch.randn(E, C_, generator=g) * 0.1
+    scale[0, :8], shift[0, :8], mean[0, :8] = 1.0, 0.0, 0.0
+    scale, shift, mean = scale.to(DEV), shift.to(DEV), mean.to(DEV)
+    xd = x.to(BF).to(DEV)
+    rd = None
+    if res:
+        r = rnd((E * rows, 1, 1, C_), g, BF)
+        r[:, :, :, :8] = 0.0
+        rd = r.to(BF).to(DEV)
+    y0, y1 = torch.empty_like(xd), torch.empty_like(xd)
+    y8, y8_flat = _guarded(tuple(xd.shape), torch.uint8, 0xAB)
+    ops.bn_apply(xd, rd, y0, scale, shift, mean, rows, E, C_, relu)
+    ops.bn_apply(xd, rd, y1, scale, shift, mean, rows, E, C_, relu, y_fp8=y8, in_scale=P.IN_SCALE)
+    torch.cuda.synchronize()
+    assert torch.equal(y0, y1)
+    _guards_intact(y8_flat, 0xAB, "y8")
+    y = y1.float().cpu()
+    want = P.e4m3_bytes(y * P.IN_SCALE)
+    assert torch.equal(y8.cpu(), want), int((y8.cpu() != want).sum())
+    fed = R.e4m3_operands({"w": torch.zeros(1, 8, C_, 1, 1, dtype=torch.float64), "inp": y.double(), "in_scale": P.IN_SCALE, "a8": True,
+                           "kw": {"in_coff": 0}}, 64)[2]
+    assert torch.equal(y8.cpu(), fed)
+    assert torch.equal(y.view(-1)[:8], x.view(-1)[:8].clamp_min(0) if relu else x.view(-1)[:8]), "the probes pass through"
+    assert want.view(-1)[:8].tolist()[:2] == [0x7e, 0x7e] and want.view(-1)[3:7].tolist() == [0x01, 0x02, 0x00, 0x00]
+
+
 # Outputs are maxima over 8..128 values that inherit the feature noise of either side: since the policy covers only the dense
 # 3x3 stride-1 convolutions of layer2-4 (round 3) the emulation's own worst-of-14 error shrank to 0.8-3 % and one more
 # realisation of the same policy (the HIP path: other summation orders, bf16 rounding points of the fused passes) lands up to
